@@ -21,12 +21,21 @@ leaves every shard resident on its GPU (how a downstream regridder or a chunked 
 adds the gather to rank 0 over xGMI, chunked by cells so that a chunk's transfer overlaps the next chunk's kernels, and
 reports `value_with_gather`.
 
-Also in the line: `roofline` (algorithmic bytes / kernel time from HIP events on the engine's stream), `end_to_end` (the
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last step when --dump-outputs is given and
+prints the line (`value`, `ms_per_step`, ...).  Everything else is measured or checked only with --full:
+`roofline` (algorithmic bytes / kernel time from HIP events on the engine's stream), `end_to_end` (the
 host-buffer API on NumPy arrays: PCIe inclusive), `pointwise_end_to_end` (the same through
 PointWiseDownscaler on host grids), `cpu_baseline` (per config: plain-C port with OpenMP for the BCSD flavours, the NumPy restatement
 on one process per core for PureAnalog; one thread / process per physical core of one socket), `cpu_baseline_numpy` (the per-cell
 NumPy restatement on one core) and `cpu_baseline_numpy_socket` (the same on one process per physical core), all on bounded samples,
-rank 0 at N = 1 only; `parity_check` compares the engine's output for the first cells with the oracle's for every config.
+rank 0 at N = 1 only; `parity_check` compares the engine's output for the first cells with the oracle's for every config;
+`secondary` (the other BASELINE configs and analog kinds, default N = 1 run); at N > 1 the RCCL legs behind the timed loop
+(`rccl`, `value_with_gather`, `value_with_host_gather`, `baseline_config5`).
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it: `out.npy` (the predicted field,
+float64; [t, C] for BCSD, [t, 3, C] for PureAnalog) on a fixed sample of t time steps with every cell (all of them when it fits
+in 48 MiB), and `cell_status.npy` (per-cell status codes as float64).  N > 1: every rank writes its own shard's, named
+`out_rank<r>.npy` / `cell_status_rank<r>.npy`, within the same total.
 """
 from __future__ import annotations
 
@@ -86,8 +95,17 @@ def parse():
     ap.add_argument("--analog-k", type=int, default=30, help="n_analogs")
     ap.add_argument("--analog-features", type=int, default=1)
     ap.add_argument("--analog-estimator", default="pure", choices=["pure", "regression"], help="PureAnalog or AnalogRegression")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline figure: roofline (per-kernel HIP events), CPU baselines, parity check "
+                         "against the oracle, host-path end-to-end legs, the secondary configs (N = 1) and the RCCL legs (N > 1); the "
+                         "options above that tune those legs apply with --full only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (a fixed sample of time steps when large)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)  # internal: one process of the N-process NumPy leg
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 and not args.cpu_worker:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---- CPU baselines (rank 0, N = 1; outside every timed region) ------------------------------------------------------
@@ -429,6 +447,31 @@ def pointwise_end_to_end(index, seed, c_full, n_cells=8192):
                     "(estimator wrappers, validation, H2D of three fields, fitted state, D2H of the result), median of 3 timed passes"}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of the predicted field written (with the status codes: under 64 MB in all)
+DUMP_SEED = 0x5D0      # --dump-outputs: the time-step sample depends on this and the shape only
+
+
+def dump_outputs(ctx, out, status, rows_per_t, T, C, path, suffix="", budget=DUMP_BYTES):
+    """the last step's result, as the caller of the timed path receives it, to path/out<suffix>.npy ([t, C] or [t, rows_per_t, C]) and
+    path/cell_status<suffix>.npy; time steps (and, only when one of them is over the budget, cells) sampled to stay within `budget`"""
+    import ctypes as Cc
+
+    from skdownscale_amd import _lib
+
+    ncell = int(max(1, min(C, budget // (8 * rows_per_t))))
+    n_t = int(max(1, min(T, budget // (8 * rows_per_t * ncell))))
+    ts = np.arange(T) if n_t == T else np.sort(np.random.default_rng(DUMP_SEED).choice(T, n_t, replace=False))
+    got = np.empty((n_t, rows_per_t, ncell))
+    ctx.synchronize()
+    for i, t in enumerate(ts):
+        for j in range(rows_per_t):  # `out` is [T, C] or [T, rows_per_t, C], row-major: one contiguous copy per row
+            _lib.check(ctx.lib.sd_memcpy_d2h(ctx.handle, got[i, j].ctypes.data_as(Cc.c_void_p),
+                                             Cc.c_void_p(out.ptr + (int(t) * rows_per_t + j) * C * 8), ncell * 8))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"out{suffix}.npy"), got[:, 0] if rows_per_t == 1 else got)
+    np.save(os.path.join(path, f"cell_status{suffix}.npy"), np.asarray(status)[:ncell].astype(np.float64))
+
+
 # ---- the benchmark ----------------------------------------------------------------------------------------------------
 
 def main():
@@ -551,17 +594,23 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    ctx.prof_reset()
-    ctx.prof_enable(True)  # HIP events around every kernel launch, on the engine's stream
+    if args.full:
+        ctx.prof_reset()
+        ctx.prof_enable(True)  # HIP events around every kernel launch, on the engine's stream (roofline)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         status = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    ctx.prof_enable(False)
-    prof = ctx.prof()
+    prof = None
+    if args.full:
+        ctx.prof_enable(False)
+        prof = ctx.prof()
     if rdv is not None:
         elapsed = rdv.allreduce_max(elapsed)
+    if args.dump_outputs:  # before any leg below re-runs the step or frees `out`
+        dump_outputs(ctx, out, status, 3 if wl["kind"] == "analog" else 1, T, C, args.dump_outputs,
+                     suffix=f"_rank{rank}" if world > 1 else "", budget=DUMP_BYTES // world)
 
     # ---- everything below is outside the timed region.  N > 1: the legs that follow bring up RCCL and move fields between GPUs for
     # the first time on this node; a watchdog bounds them -- when they stall, rank 0 prints the line with what it has (the stalled
@@ -570,10 +619,8 @@ def main():
     parity = baseline = numpy_1 = numpy_n = e2e = pw_e2e = c_port = None
     rccl = None
     config5 = None
-    def build_line():
-        """the bench line from what has been measured so far (called once at the end -- or by the N > 1 watchdog while a leg stalls)"""
-        ms_per_step = elapsed * 1e3 / args.steps
-        value = C * world * args.steps / elapsed
+    def roofline_figures():
+        """per-kernel time from the HIP events of the timed loop (--full) against the algorithmic bytes"""
         hot = {k: v for k, v in prof.items() if "mask" not in k and "status" not in k and "nan_fill" not in k and "synth" not in k}
         kern = {k: v["ms"] / max(1, v["launches"]) for k, v in hot.items()}
         launches_per_step = {k: hot[k]["launches"] / args.steps for k in kern}
@@ -613,6 +660,12 @@ def main():
                     "traffic": traffic, "traffic_source": traffic_source, "kernel": "+".join(sorted(kern)), "dominant_kernel": dominant, "kernel_ms_per_step": kernel_ms,
                     "algorithmic_bytes_per_step": alg_bytes, "algorithmic_bytes_per_cell": T * wl["bytes_per_step"],
                     "per_kernel_avg_ms": kern, "launches_per_step": launches_per_step}
+        return roofline
+
+    def build_line():
+        """the bench line from what has been measured so far (called once at the end -- or by the N > 1 watchdog while a leg stalls)"""
+        ms_per_step = elapsed * 1e3 / args.steps
+        value = C * world * args.steps / elapsed
         line = {
             "metric": METRIC, "value": value, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
@@ -620,12 +673,13 @@ def main():
             "config": {"workload": wl["name"].format(C=C, T=T, Ct=C * world, N=world), "baseline_config": config, "cells_per_gpu": C,
                        "total_cells": C * world, "timesteps": T, "groups": 12, "shards": "resident on their GPUs (value); gathered to rank 0 "
                        "(value_with_gather)" if world > 1 else "single GPU", "device": info["name"]},
-            "roofline": roofline,
-            "parity_check": parity,
         }
+        if args.full:
+            line["roofline"] = roofline_figures()
+            line["parity_check"] = parity
         if gather is not None:
             line.update(gather)
-        if world > 1:
+        if world > 1 and args.full:
             line["rccl"] = rccl
             line["baseline_config5"] = config5
             line["scaling_claim"] = ("north_star's '>= 7x at 8 GPUs vs 1' is claimed on `value`: fit + predict of every rank's shard with the "
@@ -673,7 +727,7 @@ def main():
     if os.environ.get("SD_BENCH_FAKE_STALL") and world > 1:  # (test hook: a leg that never returns)
         leg["name"] = "fake stall (SD_BENCH_FAKE_STALL)"
         time.sleep(1e6)
-    if world > 1:
+    if world > 1 and args.full:
         leg["name"] = "RCCL communicator (ncclCommInitRank)"
         try:
             comm = Communicator.from_env(ctx, rendezvous=rdv)
@@ -730,13 +784,13 @@ def main():
                         b.free()
             except Exception:  # noqa: BLE001
                 pass
-    elif world > 1 and comm is None:
+    elif world > 1 and comm is None and args.full:
         gather = {"value_with_gather": None, "error": f"no RCCL communicator: {comm_error}"}
 
     # ---- N > 1: the other sink -- every rank copies its own shard to host memory over its own PCIe link (N links in
     # parallel instead of N - 1 xGMI links into one GPU); cell chunks through two alternating host buffers ----
     leg["name"] = "shards to host memory"
-    if world > 1 and wl["kind"] != "analog" and args.gather_steps > 0:
+    if world > 1 and args.full and wl["kind"] != "analog" and args.gather_steps > 0:
         host = None
         try:
             import ctypes as Cc
@@ -795,7 +849,7 @@ def main():
         return "ok" if ok else f"FAILED max_err={np.nanmax(err):.3e}"
 
     leg["name"] = "parity check of rank 0's shard"
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if rank == 0 and world > 1 and args.full and not args.no_cpu_baseline:
         # N > 1: rank 0's shard (cells 0 .. C-1 of the C * world grid) against the oracle, outside every timed region; the
         # cpu_baseline legs themselves stay with the N = 1 line
         try:
@@ -805,7 +859,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             parity = f"not run: {type(e).__name__}: {e}"
     leg["name"] = "baseline_config5 (125 000 cells per GPU)"
-    if world > 1 and wl.get("cells_config5") and not args.cells and wl["kind"] == "bcsd_tas":
+    if world > 1 and args.full and wl.get("cells_config5") and not args.cells and wl["kind"] == "bcsd_tas":
         # BASELINE configs[4] at its own size: 125 000 cells per GPU (1 M cells at N = 8), shards resident
         try:
             if rdv is not None:
@@ -837,7 +891,7 @@ def main():
                        f"({C5 * world} cells over {world} GPUs; 1 M at N = 8), shards resident"}
         except Exception as e:  # noqa: BLE001
             config5 = {"value": None, "error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             step()  # `out` holds the full-grid result again
             ctx.synchronize()
@@ -869,13 +923,13 @@ def main():
     line = build_line()
     # ---- the other single-GPU configurations of BASELINE.json, a few steps each, so that the driver's one run times them too:
     # each in a process of its own (this one has released its fields), full size, parity of the first cells against the oracle
-    if world == 1 and config == 2 and not args.no_cpu_baseline and not args.parity_only and not args.no_secondary and not args.cells \
+    if world == 1 and config == 2 and args.full and not args.no_cpu_baseline and not args.parity_only and not args.no_secondary and not args.cells \
             and args.times == 14_600:
         secondary = {}
         for c2, steps in ((3, 10), (4, 8)):
             try:
                 o = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", str(c2), "--steps", str(steps), "--warmup", "2",
-                                    "--parity-only", "--seed", str(args.seed)], capture_output=True, text=True, timeout=600)
+                                    "--parity-only", "--full", "--seed", str(args.seed)], capture_output=True, text=True, timeout=600)
                 d = json.loads(o.stdout.strip().splitlines()[-1])
                 secondary[f"config{c2}"] = {"workload": d["config"]["workload"], "value": d["value"], "unit": d["unit"], "steps": d["steps"],
                                             "ms_per_step": d["ms_per_step"], "parity_check": d["parity_check"],
@@ -888,7 +942,7 @@ def main():
         # neighbour search in three dimensions; cells sized to a few seconds)
         def analog_line(extra, steps, warmup):
             o = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "4", "--steps", str(steps), "--warmup", str(warmup),
-                                "--parity-only", "--seed", str(args.seed)] + extra, capture_output=True, text=True, timeout=900)
+                                "--parity-only", "--full", "--seed", str(args.seed)] + extra, capture_output=True, text=True, timeout=900)
             d = json.loads(o.stdout.strip().splitlines()[-1])
             r = {"workload": d["config"]["workload"], "value": d["value"], "unit": d["unit"], "steps": d["steps"], "ms_per_step": d["ms_per_step"],
                  "parity_check": d["parity_check"],

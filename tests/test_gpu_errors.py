@@ -216,7 +216,7 @@ def _bench_two_ranks(extra_env, extra_args, port):
     env = dict(os.environ, **extra_env)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--cells", "4096", "--times", "1461", "--no-cpu-baseline", "--gather-steps", "1"] + extra_args,
+                          "--cells", "4096", "--times", "1461", "--full", "--no-cpu-baseline", "--gather-steps", "1"] + extra_args,
                          capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -1,7 +1,9 @@
-"""Live cross-check of the oracles against the real reference -- runs only where ``/root/reference`` exists (the build
-container); on the GPU box the same behaviour is pinned by the golden vectors under tests/golden/ (generated by
-tests/golden/make_golden.py from this very import).  Fresh random inputs, so it also guards the goldens against
-having been tuned to."""
+"""Cross-check of the oracles against the real reference, on what the reference returned for these very inputs: every call
+into the reference (``ref.X(...).fit(...).predict(...)`` and the fitted attributes read) was recorded by
+tests/golden/make_golden.py (``g21_reference_calls``: ``SD_RECORD_REFERENCE=1`` runs this module against the live reference
+through ``ref_shim.Recorder``) and is replayed here by ``ref_shim.Replay``; the oracle side runs live.  Inputs of their own (not
+the golden cases'), so it also guards the goldens against having been tuned to."""
+import os
 import warnings
 
 import numpy as np
@@ -12,16 +14,56 @@ import analog_oracle as ao
 import bcsd_oracle as bo
 import qm_oracle as qo
 import ref_shim
-from _cases import assert_close
+from _cases import GOLDEN, assert_close
 
-pytestmark = pytest.mark.skipif(not ref_shim.available(), reason="reference tree not present (GPU box)")
+RECORD = os.environ.get("SD_RECORD_REFERENCE") == "1"  # make_golden.py: run on the live reference and store what it returned
+FUZZ = "test_random_sweep_of_the_oracles_against_the_live_reference"
+# golden file -> (which tests' recordings it holds, number of parts: members dealt round-robin, each part under 1 MiB)
+FILES = {"g21_reference_calls": (lambda name: name != FUZZ, 1), "g21_reference_fuzz": (lambda name: name == FUZZ, 2)}
+_recorded = {}
 
 
-@pytest.fixture(scope="module")
-def ref():
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return ref_shim.load()
+def _file_of(name):
+    return next(f for f, (takes, _) in FILES.items() if takes(name))
+
+
+def _parts(f):
+    n = FILES[f][1]
+    return [os.path.join(GOLDEN, f + ".npz")] if n == 1 else [os.path.join(GOLDEN, f"{f}_{i}.npz") for i in range(n)]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _store_recording():
+    yield
+    if RECORD:
+        for f in FILES:
+            arrays = {}
+            for name, rec in _recorded.items():
+                if _file_of(name) == f:
+                    arrays.update(rec.arrays(name))
+            paths = _parts(f)
+            for i, path in enumerate(paths):
+                np.savez_compressed(path, **{k: v for j, (k, v) in enumerate(sorted(arrays.items())) if j % len(paths) == i})
+
+
+@pytest.fixture
+def ref(request):
+    """the reference namespace: recorded results (default) or, with SD_RECORD_REFERENCE=1, the live reference being recorded"""
+    name = request.node.name
+    if RECORD:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            rec = ref_shim.Recorder(ref_shim.load())
+        _recorded[name] = rec
+        yield rec
+        return
+    stored = {}
+    for path in _parts(_file_of(name)):
+        with np.load(path, allow_pickle=False) as z:
+            stored.update({k: z[k] for k in z.files if k.startswith(name + "/")})
+    rep = ref_shim.Replay(stored, name)
+    yield rep
+    assert rep.finished(), f"{name}: fewer reference calls than recorded"
 
 
 def frame(a, index):
@@ -143,12 +185,12 @@ def test_trend_aware_regressor(ref, model):
     assert_close(out, exp, what=f"trend-aware {model}")
 
 
-def test_random_sweep_of_the_oracles_against_the_live_reference():
-    """tools/dev/fuzz_oracle_vs_reference.py: 120 random cases over all eight case types (38 216 passed at the end of round 3)"""
-    import os
+def test_random_sweep_of_the_oracles_against_the_live_reference(ref):
+    """tools/dev/fuzz_oracle_vs_reference.py: 120 random cases over all eight case types (38 216 passed at the end of round 3), the
+    reference's side as recorded from the live reference"""
     import sys
 
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "dev"))
     import fuzz_oracle_vs_reference
 
-    assert fuzz_oracle_vs_reference.main(300.0, 70000, None, 120) == 0
+    assert fuzz_oracle_vs_reference.main(float("inf"), 70000, None, 120, ref=ref) == 0

@@ -3,7 +3,7 @@
 export SD_DOWNSCALE_LIB=$PWD/scikit-downscale_amd/lib/libsd_downscale_dev.so
 mkdir -p gpurun_out/r6
 run() {
-  timeout 200 python bench.py --steps ${STEPS:-15} --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --steps ${STEPS:-15} --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.readline());r=d['roofline'];print('$1', round(d['ms_per_step'],3), round(r['frac'],4), {k: round(v*r['launches_per_step'][k],3) for k,v in r['per_kernel_avg_ms'].items() if 'rs_' not in k})"
 }
 for rep in 1 2 3; do

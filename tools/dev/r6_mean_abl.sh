@@ -1,6 +1,6 @@
 run() {  # label, lib
   local label=$1; shift
-  SD_ANALOG_NOBUCKETS=1 SD_DOWNSCALE_LIB=$PWD/scikit-downscale_amd/lib/$1 timeout 300 python bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline --analog-kind weight_analogs --parity-only 2>/dev/null | python -c "
+  SD_ANALOG_NOBUCKETS=1 SD_DOWNSCALE_LIB=$PWD/scikit-downscale_amd/lib/$1 timeout 300 python bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline --analog-kind weight_analogs --parity-only 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.readline());r=d['roofline'];print('$label', round(d['ms_per_step'],2), 'ms', {k: round(v*r['launches_per_step'][k],2) for k,v in r['per_kernel_avg_ms'].items() if 'mean' in k})"
 }
 run "runs full               " libsd_downscale_dev.so

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r6
 run() {
   local label=$1; shift
-  timeout 300 python bench.py --config 4 --steps 4 --warmup 1 --no-cpu-baseline --parity-only "$@" 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --config 4 --steps 4 --warmup 1 --no-cpu-baseline --parity-only "$@" 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.readline());r=d['roofline'];print('$label', round(d['ms_per_step'],2), 'ms', round(d['value']/1e6,3), 'M cells/s', d.get('parity_check'), {k: round(v*r['launches_per_step'][k],2) for k,v in r['per_kernel_avg_ms'].items() if v*r['launches_per_step'][k] > 0.5})"
 }
 for rep in 1 2; do
