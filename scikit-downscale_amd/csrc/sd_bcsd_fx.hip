@@ -840,7 +840,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fx_kernel(const Params) {
 }
 
 // ---- round 6: the tiles land by LDS-DMA, time-major ------------------------------------------------------------------------
-// bcsd_fd_kernel<K>: the whole-lane BcsdTemperature fit + predict pass of bcsd_fx_kernel<K, true, true> (same reference
+// bcsd_fd_kernel<K, EARLY, RAG>: the BcsdTemperature fit + predict pass of bcsd_fx_kernel<K, true, *> (round 7: ragged segments too; same reference
 // semantics, bcsd.py:197-269, quantile.py:81-147, 438-545; same keys, sort and work list) with a different life of the tile:
 //
 //   landing   global_load_lds_dwordx4: one wave instruction fetches 16 rows x 64 B (the 8 cells of the tile) and the hardware
@@ -868,7 +868,8 @@ namespace tmj {
 // (the source address is per lane).  Lane l of the wave that owns a cell works on rows 20 l .. 20 l + 19 of the segment:
 //   chunk l             rows 20 l .. 20 l + 15          (slot i = row 20 l + i)
 //   chunk nl + t(l)     the tails, rows 20 l + 16 + e    (slot s2(l) + 4 e), t(l) = (l & 7) + 8 (l >> 5), s2(l) = (l >> 3) & 3
-// (nl = lanes with data = m / 20), and chunk bases are 1 032 B apart -- 8 bytes of skew, which the DMA accepts (measured:
+// (nl = lanes with data = ceil(m / 20): a ragged last lane keeps the same slots, those past the segment hold copies of its last row),
+// and chunk bases are 1 032 B apart -- 8 bytes of skew, which the DMA accepts (measured:
 // csrc/microbench/tile_dma).  A column read of a wave (its cell, the same row number i in every lane) then touches
 // (base + 1 032 l + 64 i) / 8 mod 32 = (l + 8 i) mod 32: 32 consecutive lanes on 32 different bank pairs, conflict-free for
 // ds_read_b64 and ds_read2_b64 alike; the tails likewise ((nl + t) + 8 s2 = nl + l mod 32).  (Rows in time order with the
@@ -876,7 +877,8 @@ namespace tmj {
 // phases ran at half the speed of the old cell-major rows.)  A sample's tag = its position 16 chunk + slot (11 bits).
 constexpr int kChunkStride = 1024 + 8;
 constexpr int kBlock = 20;  // rows per lane (the kernel's K)
-__host__ __device__ constexpr int chunks_of(int n) { return n / kBlock + 16; }  // n = whole lanes of 20, more than 32 of them
+__host__ __device__ constexpr int lanes_of(int n) { return (n + kBlock - 1) / kBlock; }
+__host__ __device__ constexpr int chunks_of(int n) { return lanes_of(n) + 16; }  // n: more than 32 lanes of 20
 __device__ __forceinline__ int tail_chunk(int l) { return (l & 7) + 8 * (l >> 5); }
 __device__ __forceinline__ int tail_slot(int l) { return (l >> 3) & 3; }
 // row of the segment that slot S of chunk Q holds (n - 1 where the slot holds none)
@@ -901,7 +903,7 @@ struct RowIdx {
 template <int NREG>
 __device__ __forceinline__ RowIdx<NREG> rows_of_wave(const int32_t* __restrict__ ord, int n, int q0, int wave, int lane) {
     RowIdx<NREG> t;
-    const int nl = n / kBlock;
+    const int nl = lanes_of(n);
 #pragma unroll
     for (int j = 0; j < NREG; ++j) {
         const int e = 64 * j + lane;
@@ -985,7 +987,12 @@ __device__ __forceinline__ Tags tags_of(int lane, int nl) {
 // keys + second-level keys of the shifted series: t = (v - lo) * sc + 1 in [1, kQD - 1]; t + 2^21 has the exponent of 2^21, so its
 // mantissa is t in units of 2^-31: 21 bits of q above 31 further bits.  Monotone in v (fma, add: correctly rounded).
 // key = (q << 11) | sample index; u2 = the low mantissa word (bit 31 = the lowest bit of q: equal wherever q is).
-template <int K, class GetU>
+// u = -0.0 and u = +0.0 give the same t (no +0.0 canonicalisation needed): with sc finite, fma(+-0, sc, off) = off unless off is a
+// zero, and +-0 + 2^21 = 2^21; with sc infinite (hi == lo, or hi - lo = -0.0 when the extremes are zeros of both signs) off is
+// +-inf or NaN and t is NaN for every sample, whose q (2^20) and u2 (0) do not see the sign.  The extremes themselves: a zero
+// of either sign as lo gives off = 1 and the same hi - lo.
+// RAG: the segment ends inside the last data lane: pads from its first sample past m (one compare per sample).
+template <int K, bool RAG, class GetU>
 __device__ __forceinline__ void keys_u2(const GetU& u_of, double lo, double hi, int m, int lane, const Tags& tg, unsigned (&key)[K], unsigned (&u2)[K]) {
     const double sc = (double)(kQD - 2u) / (hi - lo);  // +inf when every sample is equal: t = NaN everywhere, all keys and u2 tie
     const double off = -lo * sc + 1.0;
@@ -1000,12 +1007,13 @@ __device__ __forceinline__ void keys_u2(const GetU& u_of, double lo, double hi, 
         q = q < kQD ? q : kQD;
         const unsigned dk = (q << kTagBits) | tg.of(i);
         const unsigned pk = pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
-        key[i] = lane_in ? dk : pk;
+        key[i] = (RAG ? K * lane + i < m : lane_in) ? dk : pk;
         u2[i] = w0;
     }
 }
-// keys of the observations (the cvt path of keys_from_range, whole lanes) with position tags
-template <int K>
+// keys of the observations (the cvt path of keys_from_range) with position tags.  The extremes need no mask: the slots of a
+// ragged last lane past the segment hold copies of its last row, lanes past the segment lane 0's block.
+template <int K, bool RAG>
 __device__ __forceinline__ void keys_pos(const double (&v)[K], int m, int lane, const Tags& tg, unsigned (&key)[K]) {
     double lo = __builtin_inf(), hi = -__builtin_inf();
 #pragma unroll
@@ -1026,7 +1034,7 @@ __device__ __forceinline__ void keys_pos(const double (&v)[K], int m, int lane, 
         q = q < kQD ? q : kQD;
         const unsigned dk = (q << kTagBits) | tg.of(i);
         const unsigned pk = pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
-        key[i] = lane_in ? dk : pk;
+        key[i] = (RAG ? K * lane + i < m : lane_in) ? dk : pk;
     }
 }
 
@@ -1087,7 +1095,13 @@ inline size_t fd_lds_bytes(int nmax) { return (size_t)kHeadDoubles * sizeof(doub
 // EARLY: half of the y tile is requested ahead of the sort of u (the second-level keys are compacted into the other half behind a
 // workgroup barrier); !EARLY: the second-level keys stay in the wave's own column (low words of its slots: no barrier), the whole y
 // tile is requested behind the vote.
-template <int K, bool EARLY>
+// RAG: segments of any length the launcher admits (February and December of a daily series: 1 130 / 1 230 samples, m % 20 = 10).
+// The last data lane holds r = m % 20 samples in the slots of a whole lane (r = 17 .. 19 reach its tail slots); the slots past the
+// segment hold copies of its last row (row_of_slot), so the finite checks and the extremes of the observations need no mask.
+// Per-sample predicates where a position past m would change a result: the rolling window and its count (the last two lanes),
+// the extremes of u, the pad keys, the y climatology sum, the scatter and the stores; the other lanes compute the same values
+// as the whole-lane instantiation.  The x_hist rows are predicated like the general kernel's (segments below full_min_len).
+template <int K, bool EARLY, bool RAG>
 __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     ParamsPtr p = (ParamsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1101,9 +1115,11 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     constexpr int abl = 0;
 #endif
     double* const scratch = reinterpret_cast<double*>(smem_raw);
+    double* const rcp = scratch + 64;  // (RAG) 16 doubles: correctly rounded 1/c, c = 1..9
     int* const bad_cell = reinterpret_cast<int*>(scratch + 64 + 16);
     int* const redo_flag = bad_cell + kW;
     const unsigned tile_b = lds_addr(smem_raw) + (unsigned)(kHeadDoubles * sizeof(double));
+    if (RAG) fill_rcp_table(rcp);
     if (threadIdx.x >= 32 && threadIdx.x < 32 + kW) bad_cell[threadIdx.x - 32] = 0;
 #ifdef SD_DEV
     const bool traced = (abl & 0x800) != 0 && blockIdx.x % kTraceStride == 7 && blockIdx.x / kTraceStride < (unsigned)kTraceWgs;
@@ -1122,10 +1138,10 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     const int64_t c = c0 + wave;
     const bool cell_ok = c < p->C;
     const int begf = p->off_f[g];
-    const int m = p->off_f[g + 1] - begf;  // == the predict segment's length (whole-lane groups of equal length)
+    const int m = p->off_f[g + 1] - begf;  // == the predict segment's length (groups of equal length)
     const int begp = p->off_p[g];
     if (m == 0) return;
-    const int nl = m / K;                     // lanes with data
+    const int nl = RAG ? tmj::lanes_of(m) : m / K;  // lanes with data
     const int nch = tmj::chunks_of(m);
     const int RSU = p->RS;                    // 32-bit words per cell of the u2 area
     const int nlate = fd_late_chunks(RSU) < nch ? fd_late_chunks(RSU) : nch;  // chunks under the u2 area: the late half of y
@@ -1146,7 +1162,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         tmj::RowIdx<3> rp = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, lane);  // (in one batch with the rows of the x_hist tile)
         TileRegs<NR> xh;
         int tf[NR];
-        rows_load<NR, true>(p->ord_f + begf, m, tf);
+        rows_load<NR, !RAG>(p->ord_f + begf, m, tf);
         // the DMA requests first, the register loads of x_hist behind them (the compiler's waits for the latter then cover both;
         // in the other order it drains its own loads before the first request goes out)
         tmj::rows_ready(rp);
@@ -1166,7 +1182,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
                 xh.v1[k] = v.y;
             }
         }
-        if (!(abl & 4)) tile_reduce_partials<NR, true>(xh, m, c0, p->C, scratch, p->status_fit, wave, lane, bad_cell);
+        if (!(abl & 4)) tile_reduce_partials<NR, !RAG>(xh, m, c0, p->C, scratch, p->status_fit, wave, lane, bad_cell);
         SDT(1);  // x_hist summed, x_fut requested
         tmj::dma_wait_all();
     }
@@ -1189,6 +1205,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         const bool has = K * lane < m;
         const int bl = has ? lane : 0;
         const bool first_lane = bl == 0, last_lane = K * (bl + 1) == m;
+        const int rl = m - K * bl;  // (RAG) samples from the lane's first to the end of the segment: below K + 4 in the last two lanes only
         const tmj::Col cz = tmj::col_of(tile_b, col, bl, nl);
         // (the shifted samples themselves are not kept -- 40 registers beside the 40 of the shifts --: their extremes are taken
         // here, the key generation below re-reads the samples from the column and subtracts the kept shifts again)
@@ -1203,7 +1220,8 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
                 // (every lane reads, also where the row lies before or behind the segment -- some other slot of the tile -- and
                 // drops the value: a select on the address made the compiler wrap every such read in a divergent branch)
                 const double x = cz.get(idx);
-                w[t] = idx < 0 ? (first_lane ? 0.0 : x) : idx >= K ? (last_lane ? 0.0 : x) : x;
+                if (RAG) w[t] = idx < 0 ? (first_lane ? 0.0 : x) : idx >= rl ? 0.0 : x;
+                else w[t] = idx < 0 ? (first_lane ? 0.0 : x) : idx >= K ? (last_lane ? 0.0 : x) : x;
             }
 #pragma unroll
             for (int ii = 0; ii < CH; ++ii) {
@@ -1213,22 +1231,33 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
                 const int i = cbeg + ii;
                 constexpr double kRc[10] = {0.0, 1.0, 0.5, 1.0 / 3.0, 0.25, 0.2, 1.0 / 6.0, 1.0 / 7.0, 0.125, 1.0 / 9.0};
                 double cd = 9.0, rc = kRc[9];
-                if (i < 4) {
-                    cd = first_lane ? (double)(5 + i) : cd;
-                    rc = first_lane ? kRc[5 + i] : rc;
-                }
-                if (i >= K - 4) {
-                    cd = last_lane ? (double)(K + 4 - i) : cd;
-                    rc = last_lane ? kRc[K + 4 - i] : rc;
+                if constexpr (RAG) {
+                    // the general kernel's count min(j + 5, m) - max(j - 4, 0) of sample j = K bl + i (m > 640: one lane never
+                    // holds both ends); positions past the segment get some count in 1 .. 9, their values are dropped
+                    int cnt = rl + 4 - i;
+                    cnt = cnt < 9 ? (cnt > 1 ? cnt : 1) : 9;
+                    if (i < 4) cnt = first_lane ? 5 + i : cnt;
+                    cd = (double)cnt;
+                    rc = rcp[cnt];
+                } else {
+                    if (i < 4) {
+                        cd = first_lane ? (double)(5 + i) : cd;
+                        rc = first_lane ? kRc[5 + i] : rc;
+                    }
+                    if (i >= K - 4) {
+                        cd = last_lane ? (double)(K + 4 - i) : cd;
+                        rc = last_lane ? kRc[K + 4 - i] : rc;
+                    }
                 }
                 const double q = s * rc;
                 const double mean = __builtin_fma(__builtin_fma(-cd, q, s), rc, q);  // correctly rounded s / count
                 const double sh = mean - xc;                                           // bcsd.py:253
                 shift[i] = sh;
                 bad |= nonfinite64(w[ii + 4]);
-                const double ui = (w[ii + 4] - sh) + 0.0;  // bcsd.py:256; -0.0 -> +0.0
-                ulo = vmin(ulo, ui);
-                uhi = vmax(uhi, ui);
+                const double ui = w[ii + 4] - sh;  // bcsd.py:256 (-0.0 and +0.0 give the same keys: keys_u2)
+                const bool in = !RAG || i < rl;
+                ulo = vmin(ulo, in ? ui : ulo);
+                uhi = vmax(uhi, in ? ui : uhi);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1247,8 +1276,8 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         {
             ulo = wave_min_f64(ulo);
             uhi = wave_max_f64(uhi);
-            const auto u_of = [&](int i) { return (cz.get(i) - shift[i]) + 0.0; };
-            tmj::keys_u2<K>(u_of, ulo, uhi, m, lane, tmj::tags_of(lane, nl), ku, u2);
+            const auto u_of = [&](int i) { return cz.get(i) - shift[i]; };
+            tmj::keys_u2<K, RAG>(u_of, ulo, uhi, m, lane, tmj::tags_of(lane, nl), ku, u2);
         }
         tmj::rows_ready(ry_late);
         unsigned ub;
@@ -1334,15 +1363,16 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
             for (int i = 0; i < K; ++i) v[i] = cz.get(i);
             double s = 0.0;
             bool bad = false;
+            const int rl = m - K * bl;
 #pragma unroll
             for (int i = 0; i < K; ++i) {
-                s += v[i];
+                s += !RAG || i < rl ? v[i] : 0.0;  // (RAG: the sum of the general kernel)
                 bad |= nonfinite64(v[i]);
             }
             s = has ? s : 0.0;
             yc = wave_sum_f64(s) / (double)m;  // bcsd.py:223
             if (__any(bad && has) && lane == 0 && cell_ok) atomicOr(&p->status_fit[c], SDI_NONFINITE);
-            tmj::keys_pos<K>(v, m, lane, tmj::tags_of(lane, nl), ky);
+            tmj::keys_pos<K, RAG>(v, m, lane, tmj::tags_of(lane, nl), ky);
         }
         SDT(10);  // y_climo, keys
         SDPH("y_sort");
@@ -1366,8 +1396,11 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         SDPH("map_scatter");
         wave_fence();  // every lane has read what it needs of the column
         if (has) {
+            // (RAG: the ranks of the last data lane past m hold its own pad keys, whose tags K lane + i name other samples' slots:
+            // those values go to the lane's own slots past the segment, which the stores skip)
+            const tmj::Tags tg = tmj::tags_of(lane, nl);
 #pragma unroll
-            for (int i = 0; i < K; ++i) lds_store_f64(colb + tmj::tag_off(ku[i] & kTagMask), t[i]);
+            for (int i = 0; i < K; ++i) lds_store_f64(colb + tmj::tag_off(!RAG || K * lane + i < m ? ku[i] & kTagMask : tg.of(i)), t[i]);
         }
         wave_fence();
         SDPH("restore");
@@ -1407,8 +1440,9 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         for (int k = 0; k < NKX; ++k) {
             const int qc = wave + kW * k;
             const int S = lane >> 2;
-            // (a tail slot of a lane without data holds no row)
-            const bool row_in = qc < nl ? K * qc + S < m : (((qc - nl) & 7) + 8 * (S & 3) + 32 * ((qc - nl) >> 3)) < nl;
+            // (a tail slot of a lane without data holds no row; RAG: nor one past the segment in the last data lane)
+            const int lt = ((qc - nl) & 7) + 8 * (S & 3) + 32 * ((qc - nl) >> 3);
+            const bool row_in = qc < nl ? K * qc + S < m : RAG ? K * lt + 16 + (S >> 2) < m : lt < nl;
             const int ti = tmj::row_of_request(ro, k, lane);
             if (qc < nch && row_in && keep) {
                 typedef double __attribute__((ext_vector_type(2))) f64x2;
@@ -2054,32 +2088,52 @@ int launch_ki(sd_ctx* ctx, Params p, int nmax, const int* group_len) {
     }
 #endif
     if constexpr (IDENT && K == 20) {
-        // Round 6: the whole-lane months of BcsdTemperature fit + predict take the kernel whose tiles land by LDS-DMA
-        // (bcsd_fd_kernel) when the fields allow 16-byte requests of whole cell pairs and two workgroups still fit a CU
-        int nfull = 0;
-        for (int g = 0; g < p.G && group_len != nullptr && p.G <= 64; ++g)
-            if ((full >> g) & 1ull) nfull = group_len[g] > nfull ? group_len[g] : nfull;
+        // The months of BcsdTemperature fit + predict take the kernel whose tiles land by LDS-DMA (bcsd_fd_kernel) when the fields
+        // allow 16-byte requests of whole cell pairs and two workgroups still fit a CU: the whole-lane months in one launch, the
+        // others (February, December) in a second one of the RAG instantiation -- each set checked on its own longest and shortest
+        // group; a set that does not qualify takes the register-tile kernel
+        int nmx[2] = {0, 0}, nmn[2] = {1 << 30, 1 << 30};
+        for (int g = 0; g < p.G && group_len != nullptr && p.G <= 64; ++g) {
+            const int s = ((full >> g) & 1ull) ? 0 : ((rest >> g) & 1ull) ? 1 : -1;
+            if (s < 0) continue;
+            nmx[s] = group_len[g] > nmx[s] ? group_len[g] : nmx[s];
+            nmn[s] = group_len[g] < nmn[s] ? group_len[g] : nmn[s];
+        }
         const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const size_t lds_fd = fd_lds_bytes(nfull);
-        const bool ok = full != 0ull && p.kind == SD_BCSD_TAS && !p.from_state && p.X != nullptr && p.C >= kW && p.C % 2 == 0 && p.ld % 2 == 0 &&
-                        p.ld_p % 2 == 0 && p.ld_out % 2 == 0 && al16(p.X) && al16(p.y) && al16(p.Xp) && al16(p.out) && 2 * lds_fd <= ctx->lds_max &&
-                        nfull % 20 == 0 && nfull > 640 && tmj::chunks_of(nfull) <= 80 && fd_late_chunks(fd_u2_stride(nfull)) <= 40 &&
-                        tmj::chunks_of(nfull) - fd_late_chunks(fd_u2_stride(nfull)) <= 40 && sd_dev_env("SD_FX_NODMA") == nullptr;
-        if (ok) {
+        const bool fields = p.kind == SD_BCSD_TAS && !p.from_state && p.X != nullptr && p.C >= kW && p.C % 2 == 0 && p.ld % 2 == 0 &&
+                            p.ld_p % 2 == 0 && p.ld_out % 2 == 0 && al16(p.X) && al16(p.y) && al16(p.Xp) && al16(p.out) &&
+                            sd_dev_env("SD_FX_NODMA") == nullptr;
+        const auto fits = [&](int s) {  // (more than 32 lanes of data in every group, at most 64; the u2 area under 40 chunks)
+            const int n = nmx[s];
+            return nmn[s] > 640 && tmj::chunks_of(n) <= 80 && fd_late_chunks(fd_u2_stride(n)) <= 40 &&
+                   tmj::chunks_of(n) - fd_late_chunks(fd_u2_stride(n)) <= 40 && 2 * fd_lds_bytes(n) <= ctx->lds_max;
+        };
+        const bool late = sd_dev_env("SD_FD_LATE") != nullptr;  // (development: the variant without the early half of the y tile)
+        const auto launch_fd = [&](unsigned long long mask, int s, auto kern, const char* name) -> int {
             Params q = p;
-            q.gmask = full;
-            q.RS = fd_u2_stride(nfull);
-            const int64_t nb = 8 * ((p.ntiles + 7) / 8) * __builtin_popcountll(full);
+            q.gmask = mask;
+            q.RS = fd_u2_stride(nmx[s]);
+            const size_t lds_fd = fd_lds_bytes(nmx[s]);
+            const int64_t nb = 8 * ((p.ntiles + 7) / 8) * __builtin_popcountll(mask);
             SD_CHECK_ARG(nb < ((int64_t)1 << 31), "grid too large");
-            if (sd_dev_env("SD_FD_LATE") != nullptr) {  // (development: the variant without the early half of the y tile)
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fd_kernel<K, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fd));
-                SD_LAUNCH(ctx, "bcsd_fd_kernel", (bcsd_fd_kernel<K, false>), dim3((unsigned)nb), dim3(kThreads), lds_fd, q);
-            } else {
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fd_kernel<K, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fd));
-                SD_LAUNCH(ctx, "bcsd_fd_kernel", (bcsd_fd_kernel<K, true>), dim3((unsigned)nb), dim3(kThreads), lds_fd, q);
+            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fd));
+            SD_LAUNCH(ctx, name, kern, dim3((unsigned)nb), dim3(kThreads), lds_fd, q);
+            return SD_OK;
+        };
+        const bool fd_full = fields && full != 0ull && fits(0), fd_rest = fields && rest != 0ull && fits(1);
+        if (fd_full || fd_rest) {
+            if (fd_full) {
+                SD_TRY(late ? launch_fd(full, 0, &bcsd_fd_kernel<K, false, false>, "bcsd_fd_kernel")
+                            : launch_fd(full, 0, &bcsd_fd_kernel<K, true, false>, "bcsd_fd_kernel"));
+            } else if (full != 0ull) {
+                Params q = p;
+                q.gmask = full;
+                SD_TRY((launch_one<K, IDENT, IDENT>(ctx, q, lds)));
             }
+            if (fd_rest) return late ? launch_fd(rest, 1, &bcsd_fd_kernel<K, false, true>, "bcsd_fd_kernel_ragged")
+                                     : launch_fd(rest, 1, &bcsd_fd_kernel<K, true, true>, "bcsd_fd_kernel_ragged");
             if (rest == 0ull) return SD_OK;
-            q = p;
+            Params q = p;
             q.gmask = rest;
             return launch_one<K, IDENT, false>(ctx, q, lds);
         }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Randomised sweep of bcsd_fd_kernel (round 6: whole-lane months, tiles by LDS-DMA) -- development library:
-random calendars whose groups are whole lanes of 20 samples (1 160 .. 1 240, mixed with groups that are not), even cell counts with
+"""Randomised sweep of bcsd_fd_kernel (round 6: whole-lane months, tiles by LDS-DMA; round 7: ragged segments) -- development library:
+random calendars whose groups are whole lanes of 20 samples (1 160 .. 1 240) or ragged (1 130, 1 230, any length 641 .. 1 280: the RAG
+instantiation; 300 .. 640: the register-tile kernel in the same call), even cell counts with
 ragged last tiles, cell views of wider fields, continuous / dyadic (exact ties) / nearly tied / constant-stretch data, masked and
 non-finite cells; the result must equal the register-tile kernel (SD_FX_NODMA) bit for bit, both schedules of the DMA kernel, and the
 NumPy oracle within 1e-6 relative for a few cells.   usage: fuzz_fd.py [cases] [seed]"""
@@ -22,13 +23,16 @@ def main(n_cases, seed):
     ctx = Context(0, lib_path=_lib.DEV_LIB_PATH)
     rng = np.random.default_rng(seed)
     t0 = time.time()
-    stats = {"cases": 0, "dma_launches": 0, "worklist_styles": 0, "views": 0}
+    stats = {"cases": 0, "dma_launches": 0, "ragged_launches": 0, "worklist_styles": 0, "views": 0}
     for it in range(n_cases):
         G = int(rng.integers(1, 13))
-        lens = [int(rng.choice([1160, 1180, 1200, 1220, 1240, 1240, 1200])) for _ in range(G)]
-        for g in range(G):  # some groups that are not whole lanes (they take the general kernel in the same call)
-            if rng.random() < 0.25:
-                lens[g] = int(rng.integers(900, 1280))
+        lens = [int(rng.choice([1160, 1180, 1200, 1220, 1240, 1240, 1200, 1130, 1230])) for _ in range(G)]
+        for g in range(G):  # groups that are not whole lanes (the ragged instantiation), rarely one too short for the DMA kernel
+            u = rng.random()
+            if u < 0.35:
+                lens[g] = int(rng.integers(641, 1281))
+            elif u < 0.4:
+                lens[g] = int(rng.integers(300, 641))
         T = sum(lens)
         gid = np.repeat(np.arange(G), lens).astype(np.int32)
         if rng.random() < 0.5:
@@ -69,8 +73,10 @@ def main(n_cases, seed):
             _, st = ctx.bcsd_fit_predict(0, dev["X"].cells(c0, c0 + C), dev["y"].cells(c0, c0 + C), gid, G, dev["Xp"].cells(c0, c0 + C), gid_p,
                                          out=big.cells(c0, c0 + C))
             ctx.prof_enable(False)
-            if name == "dma" and "bcsd_fd_kernel" in ctx.prof():
-                stats["dma_launches"] += 1
+            if name == "dma":
+                kernels = ctx.prof()
+                stats["dma_launches"] += int("bcsd_fd_kernel" in kernels)
+                stats["ragged_launches"] += int("bcsd_fd_kernel_ragged" in kernels)
             res[name] = (big.to_host(), st)
             for k in env:
                 del os.environ[k]
