@@ -364,20 +364,6 @@ __global__ void __launch_bounds__(256) bcsd_trend_restore_kernel(double* __restr
     }
 }
 
-int pick_tile_width(size_t lds_max, int nmax, int tiles, int* W, int* stride) {
-    // LDS need: tiles * W * stride * 8 (+ W*64*8 staging when tiles == 2)
-    const int st = nmax | 1;  // odd stride: rows of different cells start on different banks
-    for (int w = 8; w >= 1; w >>= 1) {
-        size_t need = (size_t)tiles * w * st * sizeof(double) + (tiles == 2 ? (size_t)w * 64 * sizeof(double) : 0);
-        if (need <= lds_max) {
-            *W = w;
-            *stride = st;
-            return SD_OK;
-        }
-    }
-    return sd_set_error(SD_ERR_UNSUPPORTED, "BCSD segment of %d samples does not fit the %zu-byte LDS", nmax, lds_max);
-}
-
 struct DevPtr {
     void* p = nullptr;
 };
@@ -457,17 +443,6 @@ int upload_group_table(sd_ctx* ctx, const int32_t* gid, int64_t T, int G, DevGro
     return SD_OK;
 }
 
-// BcsdTemperature and BcsdPrecipitation take the fused kernels of sd_bcsd_fx.hip (x side, y side, inverse CDF and shift /
-// ratio of a segment in one workgroup pass, sorts on 32-bit keys in registers); the segments they hand back (work list:
-// exactly tied samples, runs of equal keys too long for the fix-up) take RANK + APPLY, and so does every segment of
-// more than 1 536 samples and QuantileMapper(detrend=True).
-bool use_fused_path(int nmax, bool detrend) {
-    const char* e = sd_dev_env("SD_BCSD_FUSED");  // "0": RANK + APPLY for every segment (A/B measurements)
-    if (e && e[0] == '0') return false;
-    if (detrend) return false;  // QuantileMapper(detrend=True): RANK / APPLY carry the trend lines
-    return sd_bcsd_fx_supported(nmax);
-}
-
 // Hand-off / work-list workspace of one predict call, carved from the context workspace.
 struct RsWorkspace {
     uint32_t* ranks = nullptr;
@@ -505,37 +480,6 @@ int carve_workspace(sd_ctx* ctx, int nmax, int64_t C, int G, bool fused, bool wa
         SD_HIP(hipMemsetAsync(w->work_count, 0, 2 * sizeof(int), ctx->stream));
     }
     return SD_OK;
-}
-
-// the kernels of one predict call: fused kernel + RANK / APPLY over its work list, or RANK + APPLY over everything
-int run_predict_kernels(sd_ctx* ctx, sdrs::Params& p, bool fused, int nmax_all, const std::vector<int>& glen) {
-    if (fused) {
-        if (const char* e = sd_dev_env("SD_FZ_ABLATE")) p.dev_flags = atoi(e);
-        SD_TRY(sd_bcsd_fx_launch(ctx, p, nmax_all, glen.data()));
-        p.use_worklist = 1;
-        p.shift = nullptr;
-    }
-    SD_TRY(sd_bcsd_rs_launch(ctx, sdrs::MODE_RANK, p, nmax_all, glen.data()));
-    SD_TRY(sd_bcsd_rs_launch(ctx, sdrs::MODE_APPLY, p, nmax_all, glen.data()));
-    return SD_OK;
-}
-
-// longest segment of every group over one or two group tables (host offsets [G+1])
-std::vector<int> group_lengths(const std::vector<int64_t>& a, const std::vector<int64_t>* b, int G) {
-    std::vector<int> n((size_t)G);
-    for (int g = 0; g < G; ++g) {
-        int64_t v = a[g + 1] - a[g];
-        if (b) v = std::max(v, (*b)[g + 1] - (*b)[g]);
-        n[g] = (int)v;
-    }
-    return n;
-}
-
-bool use_rs_path(int nmax, int64_t ld_max) {
-    const char* e = sd_dev_env("SD_BCSD_PATH");  // "v1" forces the generic LDS-bitonic kernels (A/B testing)
-    if (e && e[0] == 'v' && e[1] == '1') return false;
-    if (ld_max >= ((int64_t)1 << 29)) return false;  // the fast kernels address rows with a 32-bit byte pitch
-    return sd_bcsd_rs_supported(nmax);
 }
 
 double h_pp_denom(int n) { return ((double)n + 1.0 - kAlpha) - kBeta; }
@@ -587,30 +531,23 @@ int build_q_tables(sd_ctx* ctx, const std::vector<int64_t>& off_f, const std::ve
     return SD_OK;
 }
 
+// The generic kernels of a plan's records (operands: p's fit / predict fields; st: the state written or read)
 template <int W>
-int launch_fit(sd_ctx* ctx, int kind, const double* X, const double* y, int64_t ld, const DevGroupTable& gt, int G,
-               int64_t T, int64_t C, int stride, int return_anoms, sd_bcsd_state* st) {
-    const size_t lds = (size_t)W * stride * sizeof(double);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fit_kernel<W>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((unsigned)((C + W - 1) / W), (unsigned)G);
-    SD_LAUNCH(ctx, "bcsd_fit_kernel", bcsd_fit_kernel<W>, grid, dim3(64 * W), lds, kind, X, y, ld,
-              (const int32_t*)gt.order.p, (const int32_t*)gt.off.p, G, T, C, stride, return_anoms, st->ys, st->x_climo,
-              st->y_climo, st->status);
+int launch_fit(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p, const sd_bcsd_state* st) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fit_kernel<W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, L.name, bcsd_fit_kernel<W>, dim3((unsigned)L.grid_x, (unsigned)L.grid_y), dim3(L.block), L.lds, p.kind, p.X, p.y, p.ld,
+              p.ord_f, p.off_f, p.G, p.Tf, p.C, L.rs, p.return_anoms, st->ys, st->x_climo, st->y_climo, st->status);
     return SD_OK;
 }
 
 template <int W>
-int launch_predict(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, int64_t ld, const DevGroupTable& gt,
-                   int stride, int32_t* status_p, double* out, int64_t ld_out) {
-    const size_t lds = (size_t)2 * W * stride * sizeof(double) + (size_t)W * 64 * sizeof(double);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_predict_kernel<W>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid((unsigned)((st->C + W - 1) / W), (unsigned)st->G);
-    SD_LAUNCH(ctx, "bcsd_predict_kernel", bcsd_predict_kernel<W>, grid, dim3(64 * W), lds, st->kind, Xp, ld,
-              (const int32_t*)gt.order.p, (const int32_t*)gt.off.p, (const int32_t*)st->goff_dev, st->G, st->T, st->C,
-              stride, st->return_anoms, (const double*)st->ys, (const double*)st->x_climo, (const double*)st->y_climo,
-              (const int32_t*)st->status, status_p, out, ld_out, st->qt_tails, st->qt_endpoints);
+int launch_predict(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p, const sd_bcsd_state* st) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_predict_kernel<W>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)L.lds));
+    SD_LAUNCH(ctx, L.name, bcsd_predict_kernel<W>, dim3((unsigned)L.grid_x, (unsigned)L.grid_y), dim3(L.block), L.lds, st->kind, p.Xp,
+              p.ld_p, p.ord_p, p.off_p, (const int32_t*)st->goff_dev, st->G, st->T, st->C, L.rs, st->return_anoms, (const double*)st->ys,
+              (const double*)st->x_climo, (const double*)st->y_climo, (const int32_t*)st->status, p.status_p, p.out, p.ld_out, st->qt_tails,
+              st->qt_endpoints);
     return SD_OK;
 }
 
@@ -836,40 +773,23 @@ __global__ void __launch_bounds__(1024) bcsd_long_predict_kernel(
     }
 }
 
-// register widths of the workgroup sort: n <= 1024 * K and the keys fit the LDS
-int long_width(int nmax, size_t lds_max) {
-    const int widths[] = {3, 5, 9, 13, 15, 17, 19};
-    for (int K : widths) {
-        const int64_t np = ((int64_t)nmax + K - 1) / K * K;
-        if (nmax <= 1024 * K && sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025 + 64 <= lds_max) return K;
-    }
-    return 0;
-}
-
 template <int K>
-int launch_long_fit(sd_ctx* ctx, int kind, const double* X, const double* y, int64_t ld, const DevGroupTable& gt, int G, int64_t T,
-                    int64_t C, int return_anoms, sd_bcsd_state* st) {
-    const int np = (gt.nmax + K - 1) / K * K;
-    const size_t lds = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
+int launch_long_fit(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p, const sd_bcsd_state* st) {
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_long_fit_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    SD_LAUNCH(ctx, "bcsd_long_fit_kernel", bcsd_long_fit_kernel<K>, dim3((unsigned)C, (unsigned)G), dim3(1024), lds, kind, X, y, ld,
-              (const int32_t*)gt.order.p, (const int32_t*)gt.off.p, G, T, C, return_anoms, st->ys, st->x_climo, st->y_climo,
-              st->status, st->detrend, st->y_trend);
+                               (int)L.lds));
+    SD_LAUNCH(ctx, L.name, bcsd_long_fit_kernel<K>, dim3((unsigned)L.grid_x, (unsigned)L.grid_y), dim3(L.block), L.lds, p.kind, p.X, p.y,
+              p.ld, p.ord_f, p.off_f, p.G, p.Tf, p.C, p.return_anoms, st->ys, st->x_climo, st->y_climo, st->status, st->detrend, st->y_trend);
     return SD_OK;
 }
 
 template <int K>
-int launch_long_predict(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, int64_t ld, const DevGroupTable& gt,
-                        int32_t* status_p, double* out, int64_t ld_out) {
-    const int np = (gt.nmax + K - 1) / K * K;
-    const size_t lds = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
+int launch_long_predict(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p, const sd_bcsd_state* st) {
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_long_predict_kernel<K>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    SD_LAUNCH(ctx, "bcsd_long_predict_kernel", bcsd_long_predict_kernel<K>, dim3((unsigned)st->C, (unsigned)st->G), dim3(1024), lds,
-              st->kind, Xp, ld, (const int32_t*)gt.order.p, (const int32_t*)gt.off.p, (const int32_t*)st->goff_dev, st->G, st->T,
-              st->C, st->return_anoms, (const double*)st->ys, (const double*)st->x_climo, (const double*)st->y_climo,
-              (const int32_t*)st->status, status_p, out, ld_out, st->detrend, (const double*)st->y_trend, st->qt_tails, st->qt_endpoints);
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, L.name, bcsd_long_predict_kernel<K>, dim3((unsigned)L.grid_x, (unsigned)L.grid_y), dim3(L.block), L.lds, st->kind, p.Xp,
+              p.ld_p, p.ord_p, p.off_p, (const int32_t*)st->goff_dev, st->G, st->T, st->C, st->return_anoms, (const double*)st->ys,
+              (const double*)st->x_climo, (const double*)st->y_climo, (const int32_t*)st->status, p.status_p, p.out, p.ld_out, st->detrend,
+              (const double*)st->y_trend, st->qt_tails, st->qt_endpoints);
     return SD_OK;
 }
 
@@ -883,12 +803,13 @@ int launch_long_predict(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, 
         case 17: SD_TRY(fn<17>(__VA_ARGS__)); break;       \
         default: SD_TRY(fn<19>(__VA_ARGS__)); break;       \
     }
-
-bool use_long_path(int nmax, size_t lds_max) {
-    const char* e = sd_dev_env("SD_BCSD_PATH");  // "v1" keeps the generic LDS-bitonic kernels
-    if (e && e[0] == 'v' && e[1] == '1') return false;
-    return nmax > 64 * 33 && long_width(nmax, lds_max) != 0;
-}
+#define SD_TILE_DISPATCH(W, fn, ...)                       \
+    switch (W) {                                           \
+        case 8: SD_TRY(fn<8>(__VA_ARGS__)); break;         \
+        case 4: SD_TRY(fn<4>(__VA_ARGS__)); break;         \
+        case 2: SD_TRY(fn<2>(__VA_ARGS__)); break;         \
+        default: SD_TRY(fn<1>(__VA_ARGS__)); break;        \
+    }
 
 // options = SD_BCSD_RETURN_ANOMS | SD_BCSD_QM_DETREND bits (the public `return_anoms` argument of the fit entry points)
 int alloc_state(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int options, sd_bcsd_state** out) {
@@ -916,14 +837,98 @@ int alloc_state(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int options,
     return SD_OK;
 }
 
+// samples of every group (host offsets [G+1])
+std::vector<int> group_lengths(const std::vector<int64_t>& off, int G) {
+    std::vector<int> n((size_t)G);
+    for (int g = 0; g < G; ++g) n[g] = (int)(off[g + 1] - off[g]);
+    return n;
+}
+
+// the facts the launch plan (sd_bcsd_plan.h) decides on; predict_off: nullptr for a fit; fields: the X, y, Xp, out pointers
+BcsdCall bcsd_call(const sd_ctx* ctx, BcsdOp op, int kind, bool detrend, int G, const std::vector<int64_t>& fit_off,
+                   const std::vector<int64_t>* predict_off, int64_t C, int64_t ld, int64_t ld_p, int64_t ld_out,
+                   std::initializer_list<const void*> fields) {
+    BcsdCall c;
+    c.op = op;
+    c.kind = kind;
+    c.detrend = detrend;
+    c.G = G;
+    c.fit_len = group_lengths(fit_off, G);
+    if (predict_off) c.predict_len = group_lengths(*predict_off, G);
+    c.C = C;
+    c.ld = ld;
+    c.ld_p = ld_p;
+    c.ld_out = ld_out;
+    for (const void* f : fields) c.aligned16 = c.aligned16 && (reinterpret_cast<uintptr_t>(f) & 15) == 0;
+    c.lds_max = ctx->lds_max;
+    c.cu_count = ctx->cu_count;
+    c.dev = sd_bcsd_dev_switches();
+    return c;
+}
+
+int plan_call(const BcsdCall& c, BcsdPlan* plan) {
+    *plan = bcsd_plan(c);
+    return plan->error == SD_OK ? SD_OK : sd_set_error(plan->error, "%s", plan->message.c_str());
+}
+
+// Params fields every register-sort / fused launch of a call shares: sizes, options and the operands of the sides the call has
+// (gf / gp nullptr: no fit / predict table); the records add gmask, RS, use_worklist and the slab strides
+sdrs::Params call_params(const BcsdPlan& plan, int kind, int G, int return_anoms, int detrend, int64_t C, int64_t Tf, int n_endpoints,
+                         const double* X, const double* y, int64_t ld, const DevGroupTable* gf, const double* Xp, int64_t ld_p,
+                         const DevGroupTable* gp, double* out, int64_t ld_out, int32_t* status_p) {
+    sdrs::Params p = {};
+    p.kind = kind; p.G = G; p.return_anoms = return_anoms; p.detrend = detrend;
+    p.C = C; p.Tf = Tf; p.ntiles = (C + 7) / 8;
+    p.n_endpoints = n_endpoints > 0 ? n_endpoints : 10;  // quantile.py:426
+    p.X = X; p.y = y; p.ld = ld;
+    if (gf) { p.ord_f = (const int32_t*)gf->order.p; p.off_f = (const int32_t*)gf->off.p; }
+    p.Xp = Xp; p.ld_p = ld_p; p.out = out; p.ld_out = ld_out; p.status_p = status_p;
+    if (gp) { p.ord_p = (const int32_t*)gp->order.p; p.off_p = (const int32_t*)gp->off.p; }
+    if (plan.fused)
+        if (const char* e = sd_dev_env("SD_FZ_ABLATE")) p.dev_flags = atoi(e);
+    return p;
+}
+
+// RANK / APPLY of a predict: the inverse-CDF tables (unless identity), the hand-off workspace and the work lists
+int attach_rank_apply(sd_ctx* ctx, const BcsdPlan& plan, QTables& qt, bool want_x_climo, sdrs::Params& p) {
+    p.qidx = qt.idx.as<int32_t>(); p.qval = qt.val.as<double>();
+    p.identity = plan.identity ? 1 : 0;
+    RsWorkspace w;
+    SD_TRY(carve_workspace(ctx, plan.nmax, p.C, p.G, plan.fused, want_x_climo, p.detrend != 0, &w));
+    p.ranks = w.ranks; p.shift = w.shift; p.trend_u = w.trend_u;
+    if (want_x_climo) p.x_climo = w.x_climo;
+    p.worklist = w.worklist; p.work_count = w.work_count; p.work_cap = w.work_cap;
+    p.worklist2 = w.worklist2; p.work_count2 = w.work_count2;
+    return SD_OK;
+}
+
+// the launches of one stage of a plan: the fit stage writes st, the predict stage reads it (the fused fit + predict: no state)
+int run_launches(sd_ctx* ctx, const BcsdPlan& plan, bool fit_stage, const sdrs::Params& p, const sd_bcsd_state* st) {
+    for (const BcsdLaunch& L : plan.launches) {
+        if (bcsd_fit_stage(L.kernel) != fit_stage) continue;
+        switch (L.kernel) {
+            case BcsdKernel::RsFit:
+            case BcsdKernel::RsRank:
+            case BcsdKernel::RsApply: SD_TRY(sd_bcsd_rs_run(ctx, L, p)); break;
+            case BcsdKernel::LongFit: SD_LONG_DISPATCH(L.width, launch_long_fit, ctx, L, p, st); break;
+            case BcsdKernel::LongPredict: SD_LONG_DISPATCH(L.width, launch_long_predict, ctx, L, p, st); break;
+            case BcsdKernel::Fit: SD_TILE_DISPATCH(L.width, launch_fit, ctx, L, p, st); break;
+            case BcsdKernel::Predict: SD_TILE_DISPATCH(L.width, launch_predict, ctx, L, p, st); break;
+            default: SD_TRY(sd_bcsd_fx_run(ctx, L, p)); break;
+        }
+    }
+    if (plan.fused && !fit_stage) SD_TRY(sd_bcsd_fx_trace(ctx));
+    return SD_OK;
+}
+
 }  // namespace
 
 static int fit_with_table(sd_ctx* ctx, int kind, const double* X_dev, const double* y_dev, int64_t ld, const DevGroupTable& gt, int G,
-                          int64_t T_rows, int64_t C, int return_anoms, sd_bcsd_state** out);
-static int predict_with_table(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_dev, int64_t ld, const DevGroupTable& gt, int64_t Tp,
-                              double* out_dev, int64_t ld_out, int32_t* status_p);
-static int finish_predict(sd_ctx* ctx, const sd_bcsd_state* st, const int32_t* status_p, int64_t Tp, double* out_dev, int64_t ld_out,
-                          int32_t* cell_status);
+                          int64_t C, int options, sd_bcsd_state** out, const BcsdPlan* plan = nullptr);
+static int predict_with_table(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_dev, int64_t ld, const DevGroupTable& gt,
+                              double* out_dev, int64_t ld_out, int32_t* status_p, const BcsdPlan* plan = nullptr);
+static int finish_predict(sd_ctx* ctx, int64_t C, const int32_t* status_f, const int32_t* status_p, int64_t Tp, double* out_dev,
+                          int64_t ld_out, int32_t* cell_status);
 
 extern "C" {
 
@@ -954,93 +959,66 @@ int sd_bcsd_fit_dev(sd_ctx* ctx, int kind, const double* X_dev, const double* y_
     SD_HIP(hipSetDevice(ctx->device));
     DevGroupTable gt;
     SD_TRY(upload_group_table(ctx, group_id, T, G, &gt));
-    return fit_with_table(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, return_anoms, out);
+    return fit_with_table(ctx, kind, X_dev, y_dev, ld, gt, G, C, return_anoms, out);
 }
 
 }  // extern "C"
 
-// the kernels of a predict call on an uploaded predict group table (status_p: device [C], zeroed)
-static int predict_with_table(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_dev, int64_t ld, const DevGroupTable& gt, int64_t Tp,
-                              double* out_dev, int64_t ld_out, int32_t* status_p) {
-    const int64_t C = st->C;
-    int W = 0, stride = 0;
-    const int nmax_all = gt.nmax > st->nmax ? gt.nmax : st->nmax;
-    const bool rs = use_rs_path(nmax_all, ld > ld_out ? ld : ld_out);
-    const bool lng = !rs && use_long_path(nmax_all, ctx->lds_max) && long_width(gt.nmax, ctx->lds_max) != 0;
-    if (st->detrend && !rs && !lng)
-        return sd_set_error(SD_ERR_UNSUPPORTED, "detrended quantile mapping serves group segments of up to %d samples (longest here: %d)",
-                            1024 * 19, nmax_all);
-    if (!rs && !lng) SD_TRY(pick_tile_width(ctx->lds_max, gt.nmax, 2, &W, &stride));
-    QTables qt;
-    if (rs) {
-        const bool identity = st->goff == gt.host_off;  // equal fit / predict group lengths: no inverse-CDF tables needed
-        if (!identity) SD_TRY(build_q_tables(ctx, st->goff, gt.host_off, st->G, &qt, st->qt_tails));
-        sdrs::Params p = {};
-        p.n_endpoints = st->qt_endpoints;
-        p.kind = st->kind; p.G = st->G; p.return_anoms = st->return_anoms; p.RS = sd_bcsd_rs_row_stride(nmax_all);
-        p.C = C; p.Tf = st->T; p.ntiles = (C + 7) / 8;
-        p.Xp = Xp_dev; p.ld_p = ld; p.out = out_dev; p.ld_out = ld_out;
-        p.off_f = (const int32_t*)st->goff_dev;
-        p.ord_p = (const int32_t*)gt.order.p; p.off_p = (const int32_t*)gt.off.p;
-        p.qidx = qt.idx.as<int32_t>(); p.qval = qt.val.as<double>();
-        p.ys = st->ys; p.x_climo = st->x_climo; p.y_climo = st->y_climo;
-        p.status_fit = st->status; p.status_p = status_p;
-        p.identity = identity ? 1 : 0;
-        p.from_state = 1;
-        p.detrend = st->detrend; p.y_trend = st->y_trend;
-        const bool fused = use_fused_path(nmax_all, st->detrend != 0);
-        RsWorkspace w;
-        SD_TRY(carve_workspace(ctx, nmax_all, C, st->G, fused, false, st->detrend != 0, &w));
-        p.ranks = w.ranks; p.shift = w.shift; p.trend_u = w.trend_u;
-        p.worklist = w.worklist; p.work_count = w.work_count; p.work_cap = w.work_cap;
-        p.worklist2 = w.worklist2; p.work_count2 = w.work_count2;
-        const std::vector<int> glen = group_lengths(st->goff, &gt.host_off, st->G);
-        SD_TRY(run_predict_kernels(ctx, p, fused, nmax_all, glen));
-        SD_HIP(hipStreamSynchronize(ctx->stream));  // the inverse-CDF tables go back to the block cache
-    } else if (lng) {
-        SD_LONG_DISPATCH(long_width(gt.nmax, ctx->lds_max), launch_long_predict, ctx, st, Xp_dev, ld, gt, status_p, out_dev, ld_out);
-    } else
-    switch (W) {
-        case 8: SD_TRY(launch_predict<8>(ctx, st, Xp_dev, ld, gt, stride, status_p, out_dev, ld_out)); break;
-        case 4: SD_TRY(launch_predict<4>(ctx, st, Xp_dev, ld, gt, stride, status_p, out_dev, ld_out)); break;
-        case 2: SD_TRY(launch_predict<2>(ctx, st, Xp_dev, ld, gt, stride, status_p, out_dev, ld_out)); break;
-        default: SD_TRY(launch_predict<1>(ctx, st, Xp_dev, ld, gt, stride, status_p, out_dev, ld_out)); break;
+// The kernels of a predict call on an uploaded predict group table (status_p: device [C], zeroed).  plan: the predict stage of a
+// fit + predict plan, or nullptr to plan this predict.
+static int predict_with_table(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_dev, int64_t ld, const DevGroupTable& gt,
+                              double* out_dev, int64_t ld_out, int32_t* status_p, const BcsdPlan* plan) {
+    BcsdPlan own;
+    if (plan == nullptr) {
+        SD_TRY(plan_call(bcsd_call(ctx, BcsdOp::Predict, st->kind, st->detrend != 0, st->G, st->goff, &gt.host_off, st->C, 0, ld, ld_out,
+                                   {Xp_dev, out_dev}),
+                         &own));
+        plan = &own;
     }
+    QTables qt;
+    if (plan->rank_apply && !plan->identity) SD_TRY(build_q_tables(ctx, st->goff, gt.host_off, st->G, &qt, st->qt_tails));
+    sdrs::Params p = call_params(*plan, st->kind, st->G, st->return_anoms, st->detrend, st->C, st->T, st->qt_endpoints, nullptr, nullptr, 0,
+                                 nullptr, Xp_dev, ld, &gt, out_dev, ld_out, status_p);
+    p.off_f = (const int32_t*)st->goff_dev;
+    p.ys = st->ys; p.x_climo = st->x_climo; p.y_climo = st->y_climo; p.y_trend = st->y_trend;
+    p.status_fit = st->status;
+    p.from_state = 1;
+    if (plan->rank_apply) SD_TRY(attach_rank_apply(ctx, *plan, qt, false, p));
+    SD_TRY(run_launches(ctx, *plan, false, p, st));
+    if (plan->rank_apply) SD_HIP(hipStreamSynchronize(ctx->stream));  // the inverse-CDF tables go back to the block cache
     return SD_OK;
 }
 
-// cells that are masked / failed in fit or non-finite in predict -> NaN columns; public status codes to the host
-static int finish_predict(sd_ctx* ctx, const sd_bcsd_state* st, const int32_t* status_p, int64_t Tp, double* out_dev, int64_t ld_out,
-                          int32_t* cell_status) {
-    const int64_t C = st->C;
+// cells that are masked / failed in fit (status_f) or non-finite in predict (status_p) -> NaN columns; public status codes to the host
+static int finish_predict(sd_ctx* ctx, int64_t C, const int32_t* status_f, const int32_t* status_p, int64_t Tp, double* out_dev,
+                          int64_t ld_out, int32_t* cell_status) {
     sd_scratch status_pub;
-    SD_LAUNCH(ctx, "nan_fill_kernel", nan_fill_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, out_dev, ld_out, Tp, C,
-              (const int32_t*)st->status, status_p);
+    SD_LAUNCH(ctx, "nan_fill_kernel", nan_fill_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, out_dev, ld_out, Tp, C, status_f,
+              status_p);
     if (cell_status) {
         SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
-        SD_LAUNCH(ctx, "status_public_kernel", status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0,
-                  (const int32_t*)st->status, status_p, C, status_pub.as<int32_t>());
+        SD_LAUNCH(ctx, "status_public_kernel", status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, status_f, status_p, C,
+                  status_pub.as<int32_t>());
         SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
     }
     SD_HIP(hipStreamSynchronize(ctx->stream));
     return SD_OK;
 }
 
-// fit on an uploaded group table; the state's series length is the table's entry count (= T unless groups overlap)
+// Fit on an uploaded group table; the state's series length is the table's entry count (= T unless groups overlap).  plan: the fit
+// stage of a fit + predict plan, or nullptr to plan this fit.
 static int fit_with_table(sd_ctx* ctx, int kind, const double* X_dev, const double* y_dev, int64_t ld, const DevGroupTable& gt, int G,
-                          int64_t T_rows, int64_t C, int options, sd_bcsd_state** out) {
+                          int64_t C, int options, sd_bcsd_state** out, const BcsdPlan* plan) {
     const int64_t T = gt.host_off[G];
-    (void)T_rows;
-    const int return_anoms = options & SD_BCSD_RETURN_ANOMS;
-    int W = 0, stride = 0;
-    const bool rs = use_rs_path(gt.nmax, ld);
-    const bool lng = !rs && use_long_path(gt.nmax, ctx->lds_max);
-    if (!rs && !lng) SD_TRY(pick_tile_width(ctx->lds_max, gt.nmax, 1, &W, &stride));
+    BcsdPlan own;
+    if (plan == nullptr) {
+        SD_TRY(plan_call(bcsd_call(ctx, BcsdOp::Fit, kind, (options & SD_BCSD_QM_DETREND) != 0, G, gt.host_off, nullptr, C, ld, 0, 0,
+                                   {X_dev, y_dev}),
+                         &own));
+        plan = &own;
+    }
     sd_bcsd_state* st = nullptr;
     int rc = alloc_state(ctx, kind, G, T, C, options, &st);
-    if (rc == SD_OK && st->detrend && !rs && !lng)
-        rc = sd_set_error(SD_ERR_UNSUPPORTED, "detrended quantile mapping serves group segments of up to %d samples (longest here: %d)",
-                          1024 * 19, gt.nmax);
     if (rc != SD_OK) {
         sd_bcsd_state_destroy(st);
         return rc;
@@ -1052,24 +1030,11 @@ static int fit_with_table(sd_ctx* ctx, int kind, const double* X_dev, const doub
         const double* first = X_dev ? X_dev : y_dev;
         SD_LAUNCH(ctx, "bcsd_mask_kernel", bcsd_mask_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, first, C,
                   st->status);
-        if (rs) {
-            sdrs::Params p = {};
-            p.kind = kind; p.G = G; p.return_anoms = return_anoms; p.RS = sd_bcsd_rs_row_stride(gt.nmax);
-            p.C = C; p.Tf = T; p.ntiles = (C + 7) / 8;
-            p.X = X_dev; p.y = y_dev; p.ld = ld;
-            p.ord_f = (const int32_t*)gt.order.p; p.off_f = (const int32_t*)gt.off.p;
-            p.ys = st->ys; p.x_climo = st->x_climo; p.y_climo = st->y_climo; p.status_fit = st->status;
-            p.detrend = st->detrend; p.y_trend = st->y_trend;
-            SD_TRY(sd_bcsd_rs_launch(ctx, sdrs::MODE_FIT, p, gt.nmax, group_lengths(gt.host_off, nullptr, G).data()));
-        } else if (lng) {
-            SD_LONG_DISPATCH(long_width(gt.nmax, ctx->lds_max), launch_long_fit, ctx, kind, X_dev, y_dev, ld, gt, G, T, C, return_anoms, st);
-        } else
-        switch (W) {
-            case 8: SD_TRY(launch_fit<8>(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, stride, return_anoms, st)); break;
-            case 4: SD_TRY(launch_fit<4>(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, stride, return_anoms, st)); break;
-            case 2: SD_TRY(launch_fit<2>(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, stride, return_anoms, st)); break;
-            default: SD_TRY(launch_fit<1>(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, stride, return_anoms, st)); break;
-        }
+        sdrs::Params p = call_params(*plan, kind, G, options & SD_BCSD_RETURN_ANOMS, st->detrend, C, T, 0, X_dev, y_dev, ld, &gt, nullptr, 0,
+                                     nullptr, nullptr, 0, nullptr);
+        p.ys = st->ys; p.x_climo = st->x_climo; p.y_climo = st->y_climo; p.y_trend = st->y_trend;
+        p.status_fit = st->status;
+        SD_TRY(run_launches(ctx, *plan, true, p, st));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
     };
@@ -1095,8 +1060,8 @@ int sd_bcsd_predict_dev(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_d
     sd_scratch status_p;
     SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
     SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
-    SD_TRY(predict_with_table(ctx, st, Xp_dev, ld, gt, Tp, out_dev, ld_out, status_p.as<int32_t>()));
-    return finish_predict(ctx, st, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
+    SD_TRY(predict_with_table(ctx, st, Xp_dev, ld, gt, out_dev, ld_out, status_p.as<int32_t>()));
+    return finish_predict(ctx, C, st->status, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
 }
 
 int sd_bcsd_predict_trend_dev(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_dev, int64_t ld, const int32_t* group_id_p,
@@ -1127,12 +1092,12 @@ int sd_bcsd_predict_trend_dev(sd_ctx* ctx, const sd_bcsd_state* st, const double
     sd_bcsd_state qm = *st;
     qm.kind = SD_BCSD_PR;
     qm.return_anoms = 0;
-    SD_TRY(predict_with_table(ctx, &qm, u.as<double>(), C, gq, Tp, out_dev, ld_out, status_p.as<int32_t>()));
+    SD_TRY(predict_with_table(ctx, &qm, u.as<double>(), C, gq, out_dev, ld_out, status_p.as<int32_t>()));
     // restore the shift (bcsd.py:263), remove the target climatology (bcsd.py:266-267)
     SD_LAUNCH(ctx, "bcsd_trend_restore_kernel", bcsd_trend_restore_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)((Tp + 63) / 64)),
               dim3(256), 0, out_dev, ld_out, shift.as<double>(), (const int32_t*)gidq.p, st->G, (const double*)st->y_climo,
               st->return_anoms, Tp, C);
-    return finish_predict(ctx, st, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
+    return finish_predict(ctx, C, st->status, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
 }
 
 int sd_bcsd_fit_predict_dev(sd_ctx* ctx, int kind, const double* X_dev, const double* y_dev, int64_t ld,
@@ -1147,62 +1112,44 @@ int sd_bcsd_fit_predict_dev(sd_ctx* ctx, int kind, const double* X_dev, const do
     DevGroupTable gf, gp;
     SD_TRY(upload_group_table(ctx, group_id, T, G, &gf));
     SD_TRY(upload_group_table(ctx, group_id_p, Tp, G, &gp));
-    const int nmax_all = gf.nmax > gp.nmax ? gf.nmax : gp.nmax;
     SD_CHECK_ARG(return_anoms >= 0 && return_anoms <= 3, "sd_bcsd_fit_predict: options %d", return_anoms);
     const bool detrend = (return_anoms & SD_BCSD_QM_DETREND) != 0;
-    if (!use_rs_path(nmax_all, std::max(ld, std::max(ld_p, ld_out)))) {
-        // generic path: fit then predict through a transient state
+    BcsdPlan plan;
+    SD_TRY(plan_call(bcsd_call(ctx, BcsdOp::FitPredict, kind, detrend, G, gf.host_off, &gp.host_off, C, ld, ld_p, ld_out,
+                               {X_dev, y_dev, Xp_dev, out_dev}),
+                     &plan));
+    if (plan.via_state) {  // the fit's launches into a transient state, then the predict's from it
         sd_bcsd_state* st = nullptr;
-        SD_TRY(sd_bcsd_fit_dev(ctx, kind, X_dev, y_dev, ld, group_id, G, T, C, return_anoms, &st));
-        int rc = sd_bcsd_predict_dev(ctx, st, Xp_dev, ld_p, group_id_p, Tp, out_dev, ld_out, cell_status);
+        SD_TRY(fit_with_table(ctx, kind, X_dev, y_dev, ld, gf, G, C, return_anoms, &st, &plan));
+        const auto predict = [&]() -> int {
+            sd_scratch status_p;
+            SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
+            SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+            SD_TRY(predict_with_table(ctx, st, Xp_dev, ld_p, gp, out_dev, ld_out, status_p.as<int32_t>(), &plan));
+            return finish_predict(ctx, C, st->status, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
+        };
+        const int rc = predict();
         sd_bcsd_state_destroy(st);
         return rc;
     }
-    // fused register/LDS path: no persisted quantile state, HBM traffic = 3 reads + 1 write per sample
-    sd_scratch status_f, status_p, status_pub;
+    // No persisted sorted state.  One fused kernel per segment (no hand-off at all); for the segments it hands back RANK writes
+    // 2 bytes/sample (rank of every x_fut sample in its shifted segment) + x_climo, APPLY sorts y_obs on chip, maps the ranks and
+    // restores the shift.
+    sd_scratch status_f, status_p;
     SD_HIP(status_f.alloc(ctx, sizeof(int32_t) * C));
     SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
     SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
     QTables qt;
-    const bool identity = gf.host_off == gp.host_off;  // equal fit / predict group lengths: no inverse-CDF tables needed
-    if (!identity) SD_TRY(build_q_tables(ctx, gf.host_off, gp.host_off, G, &qt));
+    if (!plan.identity) SD_TRY(build_q_tables(ctx, gf.host_off, gp.host_off, G, &qt));
     const double* first = X_dev ? X_dev : y_dev;
     SD_LAUNCH(ctx, "bcsd_mask_kernel", bcsd_mask_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, first, C,
               status_f.as<int32_t>());
-    sdrs::Params p = {};
-    p.kind = kind; p.G = G; p.return_anoms = return_anoms & SD_BCSD_RETURN_ANOMS; p.RS = sd_bcsd_rs_row_stride(nmax_all);
-    p.C = C; p.Tf = T; p.ntiles = (C + 7) / 8;
-    p.X = X_dev; p.y = y_dev; p.ld = ld;
-    p.detrend = detrend ? 1 : 0;
-    p.Xp = Xp_dev; p.ld_p = ld_p; p.out = out_dev; p.ld_out = ld_out;
-    p.ord_f = (const int32_t*)gf.order.p; p.off_f = (const int32_t*)gf.off.p;
-    p.ord_p = (const int32_t*)gp.order.p; p.off_p = (const int32_t*)gp.off.p;
-    p.qidx = qt.idx.as<int32_t>(); p.qval = qt.val.as<double>();
-    p.status_fit = status_f.as<int32_t>(); p.status_p = status_p.as<int32_t>();
-    p.identity = identity ? 1 : 0;
-    {
-        // No persisted sorted state.  One fused kernel per segment (no hand-off at all); for the segments it hands back
-        // RANK writes 2 bytes/sample (rank of every x_fut sample in its shifted
-        // segment) + x_climo, APPLY sorts y_obs on chip, maps the ranks and restores the shift.
-        const bool fused = use_fused_path(nmax_all, detrend);
-        RsWorkspace w;
-        SD_TRY(carve_workspace(ctx, nmax_all, C, G, fused, true, detrend, &w));
-        p.ranks = w.ranks; p.shift = w.shift; p.x_climo = w.x_climo; p.trend_u = w.trend_u;
-        p.worklist = w.worklist; p.work_count = w.work_count; p.work_cap = w.work_cap;
-        p.worklist2 = w.worklist2; p.work_count2 = w.work_count2;
-        const std::vector<int> glen = group_lengths(gf.host_off, &gp.host_off, G);
-        SD_TRY(run_predict_kernels(ctx, p, fused, nmax_all, glen));
-    }
-    SD_LAUNCH(ctx, "nan_fill_kernel", nan_fill_kernel, dim3((unsigned)((C + 31) / 32)), dim3(256), 0, out_dev, ld_out, Tp, C,
-              (const int32_t*)status_f.p, (const int32_t*)status_p.p);
-    if (cell_status) {
-        SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
-        SD_LAUNCH(ctx, "status_public_kernel", status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0,
-                  (const int32_t*)status_f.p, (const int32_t*)status_p.p, C, status_pub.as<int32_t>());
-        SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    sdrs::Params p = call_params(plan, kind, G, return_anoms & SD_BCSD_RETURN_ANOMS, detrend ? 1 : 0, C, T, 0, X_dev, y_dev, ld, &gf, Xp_dev,
+                                 ld_p, &gp, out_dev, ld_out, status_p.as<int32_t>());
+    p.status_fit = status_f.as<int32_t>();
+    SD_TRY(attach_rank_apply(ctx, plan, qt, true, p));
+    SD_TRY(run_launches(ctx, plan, false, p, nullptr));
+    return finish_predict(ctx, C, status_f.as<int32_t>(), status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
 }
 
 int sd_bcsd_fit(sd_ctx* ctx, int kind, const double* X, const double* y, const int32_t* group_id, int G, int64_t T,
@@ -1308,7 +1255,7 @@ int sd_bcsd_fit_groups_dev(sd_ctx* ctx, int kind, const double* X_dev, const dou
     SD_HIP(hipSetDevice(ctx->device));
     DevGroupTable gt;
     SD_TRY(upload_explicit_table(ctx, group_order, group_offsets, G, T, &gt));
-    return fit_with_table(ctx, kind, X_dev, y_dev, ld, gt, G, T, C, return_anoms, out);
+    return fit_with_table(ctx, kind, X_dev, y_dev, ld, gt, G, C, return_anoms, out);
 }
 
 int sd_bcsd_fit_groups(sd_ctx* ctx, int kind, const double* X, const double* y, const int32_t* group_order,

@@ -59,28 +59,10 @@ using sdrs::Params;
 
 typedef const Params __attribute__((address_space(4)))* ParamsPtr;
 
-constexpr int kFront = 4;
 constexpr unsigned kTagBits = 11, kTagMask = 2047u;
 constexpr unsigned kQD = (1u << 21) - 2048u;  // data keys use q <= kQD; pads q = kQD + 1 + slot
 
-constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
-
-template <int K>
-struct Lay {
-    static constexpr int P = 64 / cgcd(2 * K, 64);
-    static constexpr int KP = K * P;
-    __device__ __host__ static int slot(int j) { return kFront + j + j / KP; }  // j >= 0
-    __device__ static int own(int lane) { return kFront + K * lane + lane / P; }  // slot of sample K * lane
-};
-
-// slots a row needs: a partly filled lane reads its whole block and the rolling window behind it, so the row reaches
-// sample K * ceil(len / K) + 3 of the longest group; one spare slot takes the stores of positions past the segment
-template <int K>
-int row_slots(int nmax) {
-    int need = Lay<K>::slot((nmax + K - 1) / K * K + 3) + 2;
-    while (need % 4 != 2) ++need;  // cell rows land 8 or 24 banks apart: conflict-free transposing stores
-    return need;
-}
+// (kFront, Lay<K> -- the slot of a sample in its row -- and row_slots: sd_bcsd_plan.h)
 
 __device__ __forceinline__ unsigned lds_u32(unsigned a) { return *reinterpret_cast<__attribute__((address_space(3))) unsigned*>((uintptr_t)a); }
 
@@ -151,8 +133,7 @@ __device__ __forceinline__ bool nonfinite64(double v) { return __builtin_amdgcn_
 // FULL (template parameter of the kernels): every segment the launch serves has a multiple of K samples -- a lane is all
 // data or all pad -- and at least kRowsPerPass * (K / 2 - 1) + 1 of them -- every thread's first K / 2 - 1 rows of a tile
 // exist, only the last pass is predicated.  10 of the 12 months of a daily series qualify at K = 20 (1 200 / 1 240 samples).
-template <int K>
-constexpr int full_min_len() { return kRowsPerPass * (K / 2 - 1) + 1; }
+// (full_min_len: sd_bcsd_plan.h)
 
 // slot of row r (< 2 048) without the division by K * P: floor(r / d) = (r * ceil(2^21 / d)) >> 21 for the divisors in use
 // (checked exhaustively by the static_assert below); one 24-bit multiply, one shift
@@ -840,7 +821,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fx_kernel(const Params) {
 }
 
 // ---- round 6: the tiles land by LDS-DMA, time-major ------------------------------------------------------------------------
-// bcsd_fd_kernel<K, EARLY, RAG>: the BcsdTemperature fit + predict pass of bcsd_fx_kernel<K, true, *> (round 7: ragged segments too; same reference
+// bcsd_fd_kernel<K, RAG>: the BcsdTemperature fit + predict pass of bcsd_fx_kernel<K, true, *> (round 7: ragged segments too; same reference
 // semantics, bcsd.py:197-269, quantile.py:81-147, 438-545; same keys, sort and work list) with a different life of the tile:
 //
 //   landing   global_load_lds_dwordx4: one wave instruction fetches 16 rows x 64 B (the 8 cells of the tile) and the hardware
@@ -875,10 +856,7 @@ namespace tmj {
 // ds_read_b64 and ds_read2_b64 alike; the tails likewise ((nl + t) + 8 s2 = nl + l mod 32).  (Rows in time order with the
 // chunks skewed by 16 B -- the first version -- put lanes 16 chunks apart on the same banks: 3-way conflicts, and the column
 // phases ran at half the speed of the old cell-major rows.)  A sample's tag = its position 16 chunk + slot (11 bits).
-constexpr int kChunkStride = 1024 + 8;
-constexpr int kBlock = 20;  // rows per lane (the kernel's K)
-__host__ __device__ constexpr int lanes_of(int n) { return (n + kBlock - 1) / kBlock; }
-__host__ __device__ constexpr int chunks_of(int n) { return lanes_of(n) + 16; }  // n: more than 32 lanes of 20
+// (kChunkStride, kBlock, lanes_of, chunks_of: sd_bcsd_plan.h)
 __device__ __forceinline__ int tail_chunk(int l) { return (l & 7) + 8 * (l >> 5); }
 __device__ __forceinline__ int tail_slot(int l) { return (l >> 3) & 3; }
 // row of the segment that slot S of chunk Q holds (n - 1 where the slot holds none)
@@ -1086,22 +1064,16 @@ __device__ __forceinline__ int fix_equal_q_by(unsigned (&k)[K], int lane, const 
 }
 }  // namespace tmj
 
-// LDS of a workgroup: [head: kHeadDoubles][tile: chunks_of(nmax) x 1 032 B]; the u2 area (8 cells x RSU 32-bit words, indexed by
-// tag) overlays the first chunks of the tile
-__host__ __device__ constexpr int fd_u2_stride(int nmax) { return 16 * tmj::chunks_of(nmax); }
-__host__ __device__ constexpr int fd_late_chunks(int rsu) { return (kW * 4 * rsu + tmj::kChunkStride - 1) / tmj::kChunkStride; }  // rsu = fd_u2_stride(nmax)
-inline size_t fd_lds_bytes(int nmax) { return (size_t)kHeadDoubles * sizeof(double) + (size_t)tmj::chunks_of(nmax) * tmj::kChunkStride; }
-
-// EARLY: half of the y tile is requested ahead of the sort of u (the second-level keys are compacted into the other half behind a
-// workgroup barrier); !EARLY: the second-level keys stay in the wave's own column (low words of its slots: no barrier), the whole y
-// tile is requested behind the vote.
+// (LDS of a workgroup, fd_u2_stride, fd_late_chunks, fd_lds_bytes: sd_bcsd_plan.h)
+// Half of the y tile is requested ahead of the sort of u (the second-level keys are compacted into the other half behind a
+// workgroup barrier); the other half behind the vote.
 // RAG: segments of any length the launcher admits (February and December of a daily series: 1 130 / 1 230 samples, m % 20 = 10).
 // The last data lane holds r = m % 20 samples in the slots of a whole lane (r = 17 .. 19 reach its tail slots); the slots past the
 // segment hold copies of its last row (row_of_slot), so the finite checks and the extremes of the observations need no mask.
 // Per-sample predicates where a position past m would change a result: the rolling window and its count (the last two lanes),
 // the extremes of u, the pad keys, the y climatology sum, the scatter and the stores; the other lanes compute the same values
 // as the whole-lane instantiation.  The x_hist rows are predicated like the general kernel's (segments below full_min_len).
-template <int K, bool EARLY, bool RAG>
+template <int K, bool RAG>
 __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     ParamsPtr p = (ParamsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1155,7 +1127,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     // ---- x climatology (bcsd.py:222) from registers; the x_fut tile by DMA ------------------------------------------------
     SDPH("x_tiles");
     double xc = 0.0;
-    tmj::RowIdx<EARLY ? 2 : 3> ry_late;
+    tmj::RowIdx<2> ry_late;
     tmj::RowIdx<2> ry_early;
     {
         SD_LANE();
@@ -1269,8 +1241,8 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         }
         SDT(3);  // rolling mean
         // the rows of the y requests (the loads return under the key generation)
-        ry_late = tmj::rows_of_wave<EARLY ? 2 : 3>(p->ord_f + begf, m, 0, wave, lane);
-        if (EARLY) ry_early = tmj::rows_of_wave<2>(p->ord_f + begf, m, nlate, wave, lane);
+        ry_late = tmj::rows_of_wave<2>(p->ord_f + begf, m, 0, wave, lane);
+        ry_early = tmj::rows_of_wave<2>(p->ord_f + begf, m, nlate, wave, lane);
         SDPH("u_keys");
         unsigned u2[K];
         {
@@ -1280,24 +1252,12 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
             tmj::keys_u2<K, RAG>(u_of, ulo, uhi, m, lane, tmj::tags_of(lane, nl), ku, u2);
         }
         tmj::rows_ready(ry_late);
-        unsigned ub;
-        if constexpr (EARLY) {
-            // every wave has read its column for the last time: the tile is dead, the y requests and the u2 area may overwrite it
-            tmj::rows_ready(ry_early);
-            __syncthreads();
-            if (!(abl & 32)) tmj::dma_chunks<5, 2>(p->y, p->ld, ry_early, nlate, nch, cfetch, tile_b, wave, lane);
-            ub = tile_b + 4u * (unsigned)(col * RSU);
-        } else {
-            wave_fence();  // every lane of the wave has read its rows: their low words take the second-level keys
-            ub = 0u;
-        }
-        if (!EARLY) {
-            if (has) {
-                const tmj::Col cw = tmj::col_of(tile_b, col, lane, nl);
-#pragma unroll
-                for (int i = 0; i < K; ++i) *reinterpret_cast<__attribute__((address_space(3))) unsigned*>((uintptr_t)cw.at(i)) = u2[i];
-            }
-        } else if (has) {  // by tag: the lane's chunk is 16 consecutive words, its tail four words 16 bytes apart
+        // every wave has read its column for the last time: the tile is dead, the y requests and the u2 area may overwrite it
+        tmj::rows_ready(ry_early);
+        __syncthreads();
+        if (!(abl & 32)) tmj::dma_chunks<5, 2>(p->y, p->ld, ry_early, nlate, nch, cfetch, tile_b, wave, lane);
+        const unsigned ub = tile_b + 4u * (unsigned)(col * RSU);
+        if (has) {  // by tag: the lane's chunk is 16 consecutive words, its tail four words 16 bytes apart
             const tmj::Tags tg = tmj::tags_of(lane, nl);
             typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
             __attribute__((address_space(3))) u32x4* um = reinterpret_cast<__attribute__((address_space(3))) u32x4*>((uintptr_t)(ub + 4u * tg.main0));
@@ -1313,9 +1273,8 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         if (!(abl & 1)) sdws::wave_sort<K>(ku, lane, (m + K - 1) / K);
         SDT(5);  // sort of u
         SDPH("u_fix");
-        const unsigned colb_u = tile_b + 8u * (unsigned)col;
-        const auto cmp_u2 = [ub, colb_u](unsigned ta, unsigned tb, bool* gt, bool* eq) {
-            const unsigned a = lds_u32(EARLY ? ub + 4u * ta : colb_u + tmj::tag_off(ta)), b = lds_u32(EARLY ? ub + 4u * tb : colb_u + tmj::tag_off(tb));
+        const auto cmp_u2 = [ub](unsigned ta, unsigned tb, bool* gt, bool* eq) {
+            const unsigned a = lds_u32(ub + 4u * ta), b = lds_u32(ub + 4u * tb);
             *gt = a > b;
             *eq = a == b;
         };
@@ -1346,7 +1305,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     bool redo_y = false;
     {
         SD_LANE();
-        if (!(abl & 32)) tmj::dma_chunks<EARLY ? 5 : NKX, EARLY ? 2 : 3>(p->y, p->ld, ry_late, 0, EARLY ? nlate : nch, cfetch, tile_b, wave, lane);
+        if (!(abl & 32)) tmj::dma_chunks<5, 2>(p->y, p->ld, ry_late, 0, nlate, cfetch, tile_b, wave, lane);
         SDT(8);  // late half requested
         tmj::dma_wait_all();
         __syncthreads();
@@ -1751,8 +1710,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fxp_kernel(const Params) {
 // time slot re-walks its wet flags.  A wave whose segment has more than 64 * KC wet days -- or a tie among them, or a negative
 // value -- hands the (tile, group) over: too many wet days to `worklist2` (bcsd_fxp_kernel<K, true, true> in list mode), the
 // others to RANK / APPLY as before.
-template <int K>
-constexpr int compact_width() { return K == 20 ? 12 : K == 24 ? 16 : 0; }
+// (compact_width: sd_bcsd_plan.h)
 
 template <int K, int KC, bool FULL>
 __global__ void __launch_bounds__(kThreads, 4) bcsd_fxc_kernel(const Params) {
@@ -2020,166 +1978,57 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fxc_kernel(const Params) {
 #undef SD_LANE
 }
 
-template <int K, bool IDENT, bool FULL>
-int launch_one(sd_ctx* ctx, const Params& p, size_t lds) {
-    const int64_t tx = (p.ntiles + 7) / 8;
-    const int64_t nblocks = 8 * tx * (p.gmask ? __builtin_popcountll(p.gmask) : p.G);
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "grid too large");
-    if (p.kind == SD_BCSD_TAS) {
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fx_kernel<K, IDENT, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        SD_LAUNCH(ctx, FULL ? "bcsd_fx_kernel_full" : "bcsd_fx_kernel", (bcsd_fx_kernel<K, IDENT, FULL>), dim3((unsigned)nblocks),
-                  dim3(kThreads), lds, p);
-    } else {
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fxp_kernel<K, IDENT, FULL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        SD_LAUNCH(ctx, FULL ? "bcsd_fxp_kernel_full" : "bcsd_fxp_kernel", (bcsd_fxp_kernel<K, IDENT, FULL>), dim3((unsigned)nblocks),
-                  dim3(kThreads), lds, p);
-    }
+int launch_rec(sd_ctx* ctx, const BcsdLaunch& L, const Params& p, void (*kern)(const Params)) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, L.name, kern, dim3((unsigned)L.grid_x), dim3(kThreads), L.lds, p);
     return SD_OK;
 }
 
-template <int K, bool IDENT>
-int launch_ki(sd_ctx* ctx, Params p, int nmax, const int* group_len) {
-    p.RS = row_slots<K>(nmax);
-    const size_t lds = ((size_t)kW * p.RS + kHeadDoubles) * sizeof(double);
-    if (lds > ctx->lds_max) return sd_set_error(SD_ERR_UNSUPPORTED, "segment of %d samples needs %zu bytes of LDS", nmax, lds);
-    // Groups whose segments are whole lanes of K samples (10 of the 12 months of a daily series at K = 20) take the FULL
-    // instantiation -- no per-sample predicates --, the others a second launch of the general one.
-    unsigned long long full = 0ull, rest = 0ull;
-#ifndef SD_FX_NOFULL
-    if (IDENT && group_len != nullptr && p.G <= 64 && sd_dev_env("SD_FX_NOFULL") == nullptr) {
-        for (int g = 0; g < p.G; ++g) {
-            const bool f = group_len[g] % K == 0 && group_len[g] >= full_min_len<K>();
-            (f ? full : rest) |= 1ull << g;
-        }
-    }
-#endif
-#ifndef SD_FX_NOCOMPACT
-    if constexpr (IDENT && compact_width<K>() != 0) {
-        if (p.kind == SD_BCSD_PR && !p.from_state && p.work_count2 != nullptr && p.G <= 64 && group_len != nullptr &&
-            sd_dev_env("SD_FX_NOCOMPACT") == nullptr) {
-            // BcsdPrecipitation fit + predict: only the wet days are sorted; segments with too many of them for the narrow
-            // network come back on the second list and take the K-wide kernel
-            constexpr int KC = compact_width<K>();
-            Params q = p;
-            if ((full | rest) == 0ull) rest = p.G == 64 ? ~0ull : (1ull << p.G) - 1ull;  // (no split into whole-lane groups: all of them)
-            if (full != 0ull) {
-                q.gmask = full;
-                const int64_t nb = 8 * ((p.ntiles + 7) / 8) * __builtin_popcountll(full);
-                SD_CHECK_ARG(nb < ((int64_t)1 << 31), "grid too large");
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fxc_kernel<K, KC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                SD_LAUNCH(ctx, "bcsd_fxc_kernel_full", (bcsd_fxc_kernel<K, KC, true>), dim3((unsigned)nb), dim3(kThreads), lds, q);
-            }
-            if (rest != 0ull) {  // the months that are not whole lanes: the same kernel with its per-sample predicates
-                q.gmask = rest;
-                const int64_t nb = 8 * ((p.ntiles + 7) / 8) * __builtin_popcountll(rest);
-                SD_CHECK_ARG(nb < ((int64_t)1 << 31), "grid too large");
-                SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fxc_kernel<K, KC, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                SD_LAUNCH(ctx, "bcsd_fxc_kernel", (bcsd_fxc_kernel<K, KC, false>), dim3((unsigned)nb), dim3(kThreads), lds, q);
-            }
-            Params r = p;
-            r.use_worklist = 2;  // (the general instantiation: segments of either kind may come back)
-            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_fxp_kernel<K, IDENT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            SD_LAUNCH(ctx, "bcsd_fxp_kernel_list", (bcsd_fxp_kernel<K, IDENT, false>), dim3((unsigned)(2 * (ctx->cu_count > 0 ? ctx->cu_count : 256))),
-                      dim3(kThreads), lds, r);
-            return SD_OK;
-        }
-    }
-#endif
-    if constexpr (IDENT && K == 20) {
-        // The months of BcsdTemperature fit + predict take the kernel whose tiles land by LDS-DMA (bcsd_fd_kernel) when the fields
-        // allow 16-byte requests of whole cell pairs and two workgroups still fit a CU: the whole-lane months in one launch, the
-        // others (February, December) in a second one of the RAG instantiation -- each set checked on its own longest and shortest
-        // group; a set that does not qualify takes the register-tile kernel
-        int nmx[2] = {0, 0}, nmn[2] = {1 << 30, 1 << 30};
-        for (int g = 0; g < p.G && group_len != nullptr && p.G <= 64; ++g) {
-            const int s = ((full >> g) & 1ull) ? 0 : ((rest >> g) & 1ull) ? 1 : -1;
-            if (s < 0) continue;
-            nmx[s] = group_len[g] > nmx[s] ? group_len[g] : nmx[s];
-            nmn[s] = group_len[g] < nmn[s] ? group_len[g] : nmn[s];
-        }
-        const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        const bool fields = p.kind == SD_BCSD_TAS && !p.from_state && p.X != nullptr && p.C >= kW && p.C % 2 == 0 && p.ld % 2 == 0 &&
-                            p.ld_p % 2 == 0 && p.ld_out % 2 == 0 && al16(p.X) && al16(p.y) && al16(p.Xp) && al16(p.out) &&
-                            sd_dev_env("SD_FX_NODMA") == nullptr;
-        const auto fits = [&](int s) {  // (more than 32 lanes of data in every group, at most 64; the u2 area under 40 chunks)
-            const int n = nmx[s];
-            return nmn[s] > 640 && tmj::chunks_of(n) <= 80 && fd_late_chunks(fd_u2_stride(n)) <= 40 &&
-                   tmj::chunks_of(n) - fd_late_chunks(fd_u2_stride(n)) <= 40 && 2 * fd_lds_bytes(n) <= ctx->lds_max;
-        };
-        const bool late = sd_dev_env("SD_FD_LATE") != nullptr;  // (development: the variant without the early half of the y tile)
-        const auto launch_fd = [&](unsigned long long mask, int s, auto kern, const char* name) -> int {
-            Params q = p;
-            q.gmask = mask;
-            q.RS = fd_u2_stride(nmx[s]);
-            const size_t lds_fd = fd_lds_bytes(nmx[s]);
-            const int64_t nb = 8 * ((p.ntiles + 7) / 8) * __builtin_popcountll(mask);
-            SD_CHECK_ARG(nb < ((int64_t)1 << 31), "grid too large");
-            SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fd));
-            SD_LAUNCH(ctx, name, kern, dim3((unsigned)nb), dim3(kThreads), lds_fd, q);
-            return SD_OK;
-        };
-        const bool fd_full = fields && full != 0ull && fits(0), fd_rest = fields && rest != 0ull && fits(1);
-        if (fd_full || fd_rest) {
-            if (fd_full) {
-                SD_TRY(late ? launch_fd(full, 0, &bcsd_fd_kernel<K, false, false>, "bcsd_fd_kernel")
-                            : launch_fd(full, 0, &bcsd_fd_kernel<K, true, false>, "bcsd_fd_kernel"));
-            } else if (full != 0ull) {
-                Params q = p;
-                q.gmask = full;
-                SD_TRY((launch_one<K, IDENT, IDENT>(ctx, q, lds)));
-            }
-            if (fd_rest) return late ? launch_fd(rest, 1, &bcsd_fd_kernel<K, false, true>, "bcsd_fd_kernel_ragged")
-                                     : launch_fd(rest, 1, &bcsd_fd_kernel<K, true, true>, "bcsd_fd_kernel_ragged");
-            if (rest == 0ull) return SD_OK;
-            Params q = p;
-            q.gmask = rest;
-            return launch_one<K, IDENT, false>(ctx, q, lds);
-        }
-    }
-    if (IDENT && full != 0ull) {
-        Params q = p;
-        q.gmask = full;
-        SD_TRY((launch_one<K, IDENT, IDENT>(ctx, q, lds)));  // (FULL exists for IDENT only)
-        if (rest == 0ull) return SD_OK;
-        q.gmask = rest;
-        return launch_one<K, IDENT, false>(ctx, q, lds);
-    }
-    return launch_one<K, IDENT, false>(ctx, p, lds);
-}
-
 template <int K>
-int launch_k(sd_ctx* ctx, const Params& p, int nmax, const int* gl) {
-    return p.identity ? launch_ki<K, true>(ctx, p, nmax, gl) : launch_ki<K, false>(ctx, p, nmax, gl);
-}
-
-int launch_width(sd_ctx* ctx, const Params& p, int nmax, const int* gl) {
-#ifdef SD_FX_ONLY_K  // development: one width only (fast compiles for ISA inspection)
-    if (true) return launch_k<SD_FX_ONLY_K>(ctx, p, nmax, gl);
-#else
-    if (nmax <= 64 * 4) return launch_k<4>(ctx, p, nmax, gl);
-    if (nmax <= 64 * 8) return launch_k<8>(ctx, p, nmax, gl);
-    if (nmax <= 64 * 12) return launch_k<12>(ctx, p, nmax, gl);
-    if (nmax <= 64 * 16) return launch_k<16>(ctx, p, nmax, gl);
-    if (nmax <= 64 * 20) return launch_k<20>(ctx, p, nmax, gl);
-    if (nmax <= 64 * 24) return launch_k<24>(ctx, p, nmax, gl);
-#endif
-    return sd_set_error(SD_ERR_UNSUPPORTED, "segment of %d samples exceeds the fused register-sort path", nmax);
+int run_k(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
+    switch (L.kernel) {
+        case BcsdKernel::FxFull: return launch_rec(ctx, L, p, &bcsd_fx_kernel<K, true, true>);
+        case BcsdKernel::FxGeneral:
+            return launch_rec(ctx, L, p, L.ident ? &bcsd_fx_kernel<K, true, false> : &bcsd_fx_kernel<K, false, false>);
+        case BcsdKernel::FxpFull: return launch_rec(ctx, L, p, &bcsd_fxp_kernel<K, true, true>);
+        case BcsdKernel::FxpGeneral:
+            return launch_rec(ctx, L, p, L.ident ? &bcsd_fxp_kernel<K, true, false> : &bcsd_fxp_kernel<K, false, false>);
+        case BcsdKernel::FxpList: return launch_rec(ctx, L, p, &bcsd_fxp_kernel<K, true, false>);  // (segments of either kind come back)
+        case BcsdKernel::FxcFull:
+            if constexpr (compact_width(K) != 0) return launch_rec(ctx, L, p, &bcsd_fxc_kernel<K, compact_width(K), true>);
+            break;
+        case BcsdKernel::FxcGeneral:
+            if constexpr (compact_width(K) != 0) return launch_rec(ctx, L, p, &bcsd_fxc_kernel<K, compact_width(K), false>);
+            break;
+        case BcsdKernel::FdWhole:
+            if constexpr (K == tmj::kBlock) return launch_rec(ctx, L, p, &bcsd_fd_kernel<K, false>);
+            break;
+        case BcsdKernel::FdRagged:
+            if constexpr (K == tmj::kBlock) return launch_rec(ctx, L, p, &bcsd_fd_kernel<K, true>);
+            break;
+        default: break;
+    }
+    return sd_set_error(SD_ERR_INVALID, "not a fused launch: kernel %d at K = %d", (int)L.kernel, K);
 }
 
 }  // namespace sdfx
 
-bool sd_bcsd_fx_supported(int nmax) { return nmax >= 1 && nmax <= 64 * 24; }
+int sd_bcsd_fx_run(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p0) {
+    sdrs::Params p = p0;
+    p.gmask = L.gmask;
+    p.use_worklist = L.use_worklist;
+    p.RS = L.rs;
+    switch (L.width) {
+        case 4: return sdfx::run_k<4>(ctx, L, p);
+        case 8: return sdfx::run_k<8>(ctx, L, p);
+        case 12: return sdfx::run_k<12>(ctx, L, p);
+        case 16: return sdfx::run_k<16>(ctx, L, p);
+        case 20: return sdfx::run_k<20>(ctx, L, p);
+        default: return sdfx::run_k<24>(ctx, L, p);
+    }
+}
 
-// One launch per call: the K = 20 kernel serves every month of a daily series (1 130 .. 1 240 samples), a narrower
-// kernel only pays when the longest group allows it.
-int sd_bcsd_fx_launch(sd_ctx* ctx, const sdrs::Params& p, int nmax, const int* group_len) {
-    sdrs::Params q = p;
-    q.gmask = 0ull;
-    q.use_worklist = 0;
-    if (q.n_endpoints <= 0) q.n_endpoints = 10;
-    SD_TRY(sdfx::launch_width(ctx, q, nmax, group_len));
+int sd_bcsd_fx_trace(sd_ctx* ctx) {
 #ifdef SD_DEV
     if (const char* path = sd_dev_env("SD_FX_TRACE")) {  // raw phase clocks of the sampled workgroups -> file (tools/dev/trace_fx.py)
         SD_HIP(hipStreamSynchronize(ctx->stream));
@@ -2190,6 +2039,8 @@ int sd_bcsd_fx_launch(sd_ctx* ctx, const sdrs::Params& p, int nmax, const int* g
             fclose(f);
         }
     }
+#else
+    (void)ctx;
 #endif
     return SD_OK;
 }

@@ -1,6 +1,7 @@
 // Register-sort BCSD paths (sd_bcsd_fx.hip: one fused kernel per segment; sd_bcsd_rs.hip: the
 // RANK / APPLY / FIT kernels): parameters and launchers.
 #pragma once
+#include "sd_bcsd_plan.h"
 #include "sd_internal.h"
 
 namespace sdrs {
@@ -27,7 +28,7 @@ struct Params {
     int from_state;  // 1 = predict from a fitted state (x_climo, y_climo, ys given), 0 = fit on the fly from X, y
     int identity;    // 1: every group has equal fit / predict length (inverse CDF = identity on ranks)
     long long* trace;  // SD_RS_TRACING builds: per-phase wall-clock stamps of sampled workgroups
-    // set by the launchers: groups served by this launch (0 = all; bit g otherwise) and the per-segment strides of the
+    // set from the plan's record: groups served by this launch (0 = all; bit g otherwise) and the per-segment strides of the
     // hand-off slabs (those of the widest kernel of the call, so that launches of different widths share the slabs)
     unsigned long long gmask;
     int slab_nr, slab_k;
@@ -48,23 +49,19 @@ struct Params {
     int detrend;
     double* trend_u;       // RANK -> APPLY: [C*G][2] slope, intercept of the predict segment's line
     double* y_trend;       // state [C][G][2]: slope, intercept of the fitted segment's line
-    int n_endpoints;  // points of the OLS tail lines (quantile.py:426, 537-541); the launchers turn 0 into the default 10
+    int n_endpoints;  // points of the OLS tail lines (quantile.py:426, 537-541); 0 is taken as the default 10 (sd_bcsd.hip: call_params)
     int dev_flags;  // development library only (SD_FZ_ABLATE): phases skipped to time the rest; results are then wrong
 };
 
 }  // namespace sdrs
 
-bool sd_bcsd_rs_supported(int nmax);
-int sd_bcsd_rs_width(int nmax);  // samples per lane (K) of the kernels serving segments of up to nmax samples
-int sd_bcsd_rs_row_stride(int nmax);
 // workspace bytes of the RANK -> APPLY hand-off slabs (both multiples of 256)
 void sd_bcsd_rs_handoff_bytes(int nmax, int64_t C, int G, size_t* rank_bytes, size_t* shift_bytes);
-// group_len (host, [G], may be NULL): longest segment (fit or predict) of every group.  When the call needs the 21-wide
-// kernels but some groups fit 19 samples per lane (30-day months of a daily series), those groups get their own launch
-// of the narrower, ~10 % cheaper kernels.
-int sd_bcsd_rs_launch(sd_ctx* ctx, int mode, const sdrs::Params& p, int nmax, const int* group_len = nullptr);
-// Fused kernels (sd_bcsd_fx.hip; BcsdTemperature and BcsdPrecipitation, segments of up to 1 536 samples): x side, y side,
-// inverse CDF and shift / ratio of a segment in one workgroup pass on the register-resident 32-bit key sort of sd_wsort.h;
-// segments they cannot serve are appended to p.worklist (the caller then runs RANK + APPLY with use_worklist).
-bool sd_bcsd_fx_supported(int nmax);
-int sd_bcsd_fx_launch(sd_ctx* ctx, const sdrs::Params& p, int nmax, const int* group_len = nullptr);
+// The launch a record of the call's plan (sd_bcsd_plan.h) names: sd_bcsd_rs.hip serves RsFit / RsRank / RsApply, sd_bcsd_fx.hip
+// the fused kernels (x side, y side, inverse CDF and shift / ratio of a segment in one workgroup pass on the register-resident
+// 32-bit key sort of sd_wsort.h; segments they cannot serve are appended to p.worklist for RANK + APPLY).  p: the call's common
+// fields; the record sets gmask, RS, use_worklist and the slab strides.
+int sd_bcsd_rs_run(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p);
+int sd_bcsd_fx_run(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p);
+// development library (SD_FX_TRACE): phase clocks of the sampled workgroups of the fused kernels to a file; a no-op otherwise
+int sd_bcsd_fx_trace(sd_ctx* ctx);

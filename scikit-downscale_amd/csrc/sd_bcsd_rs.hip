@@ -352,105 +352,59 @@ __global__ void __launch_bounds__(kThreads, OCC) bcsd_rs_kernel(const Params) {
     segment_body<K, MODE, KIND, IDENT>(p, tile_id, g, smem_raw);
 }
 
-template <int K, int MODE, int OCC, int KIND, bool IDENT>
-int launch_koki(sd_ctx* ctx, const Params& p, const char* name) {
-    const size_t lds = ((size_t)kW * p.RS + sdw::kHeadDoubles) * sizeof(double);
+template <int K, int MODE, int KIND, bool IDENT>
+int launch_koki(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
+    constexpr int OCC = K > 21 ? 2 : 4;
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bcsd_rs_kernel<K, MODE, OCC, KIND, IDENT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t tx = (p.ntiles + 7) / 8;
-    int64_t nblocks = 8 * tx * (p.gmask ? __builtin_popcountll(p.gmask) : p.G);
-    if (p.use_worklist) nblocks = 2 * (int64_t)(ctx->cu_count > 0 ? ctx->cu_count : 256);
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "grid too large");
-    SD_LAUNCH(ctx, name, (bcsd_rs_kernel<K, MODE, OCC, KIND, IDENT>), dim3((unsigned)nblocks), dim3(kThreads), lds, p);
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, L.name, (bcsd_rs_kernel<K, MODE, OCC, KIND, IDENT>), dim3((unsigned)L.grid_x), dim3(kThreads), L.lds, p);
     return SD_OK;
 }
 
-template <int K, int MODE, int OCC, int KIND>
-int launch_kok(sd_ctx* ctx, const Params& p, const char* name) {
+template <int K, int MODE, int KIND>
+int launch_kok(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
     if constexpr (MODE == MODE_APPLY) {  // IDENT only changes MODE_APPLY code
-        if (p.identity) return launch_koki<K, MODE, OCC, KIND, true>(ctx, p, name);
+        if (L.ident) return launch_koki<K, MODE, KIND, true>(ctx, L, p);
     }
-    return launch_koki<K, MODE, OCC, KIND, false>(ctx, p, name);
+    return launch_koki<K, MODE, KIND, false>(ctx, L, p);
 }
 
 template <int K, int MODE>
-int launch_k(sd_ctx* ctx, const Params& p, const char* name) {
-    constexpr int OCC = K > 21 ? 2 : 4;
-    return p.kind == SD_BCSD_TAS ? launch_kok<K, MODE, OCC, SD_BCSD_TAS>(ctx, p, name)
-                                 : launch_kok<K, MODE, OCC, SD_BCSD_PR>(ctx, p, name);
+int launch_k(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
+    return p.kind == SD_BCSD_TAS ? launch_kok<K, MODE, SD_BCSD_TAS>(ctx, L, p) : launch_kok<K, MODE, SD_BCSD_PR>(ctx, L, p);
 }
 
 template <int MODE>
-int launch_mode(sd_ctx* ctx, const Params& p, int nmax, const char* name) {
-    if (nmax <= 64 * 5) return launch_k<5, MODE>(ctx, p, name);
-    if (nmax <= 64 * 13) return launch_k<13, MODE>(ctx, p, name);
-    if (nmax <= 64 * 19) return launch_k<19, MODE>(ctx, p, name);
-    if (nmax <= 64 * 21) return launch_k<21, MODE>(ctx, p, name);
-    if (nmax <= 64 * 33) return launch_k<33, MODE>(ctx, p, name);
-    return sd_set_error(SD_ERR_UNSUPPORTED, "segment of %d samples exceeds the register-sort path", nmax);
+int launch_mode(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
+    switch (L.width) {
+        case 5: return launch_k<5, MODE>(ctx, L, p);
+        case 13: return launch_k<13, MODE>(ctx, L, p);
+        case 19: return launch_k<19, MODE>(ctx, L, p);
+        case 21: return launch_k<21, MODE>(ctx, L, p);
+        default: return launch_k<33, MODE>(ctx, L, p);
+    }
 }
 
 }  // namespace sdrs
 
 // Entry points used by sd_bcsd.hip ---------------------------------------------------------------
-bool sd_bcsd_rs_supported(int nmax) { return nmax >= 1 && nmax <= 64 * 33; }
-
-int sd_bcsd_rs_width(int nmax) { return nmax <= 64 * 5 ? 5 : nmax <= 64 * 13 ? 13 : nmax <= 64 * 19 ? 19 : nmax <= 64 * 21 ? 21 : 33; }  // as in launch_mode
-
-int sd_bcsd_rs_row_stride(int nmax) {
-    const int K = sd_bcsd_rs_width(nmax);
-    const int CH = K >= 14 ? (K + 2) / 3 : K;
-    int rs = (nmax + K - 1) / K * K + 1;  // the sort stores the pads of the last run; one readable slot past the end
-    const int roll = sdw::kPadFront + nmax + CH + 4;  // time-ordered segment with zero pads for the rolling windows
-    if (rs < roll) rs = roll;
-    while (rs % 4 != 2) ++rs;  // cell rows land 8 or 24 banks apart: conflict-free transposing stores
-    return rs;
-}
-
 void sd_bcsd_rs_handoff_bytes(int nmax, int64_t C, int G, size_t* rank_bytes, size_t* shift_bytes) {
     const size_t K = (size_t)sd_bcsd_rs_width(nmax), segs = (size_t)C * (size_t)G;
     *rank_bytes = segs * ((K + 1) / 2) * 64 * sizeof(uint32_t);
     *shift_bytes = segs * K * 64 * sizeof(double);
 }
 
-static int rs_launch_one(sd_ctx* ctx, int mode, const sdrs::Params& p, int nmax) {
-    switch (mode) {
-        case sdrs::MODE_FIT: return sdrs::launch_mode<sdrs::MODE_FIT>(ctx, p, nmax, "bcsd_rs_fit_kernel");
-        case sdrs::MODE_RANK: return sdrs::launch_mode<sdrs::MODE_RANK>(ctx, p, nmax, "bcsd_rs_rank_kernel");
-        case sdrs::MODE_APPLY: return sdrs::launch_mode<sdrs::MODE_APPLY>(ctx, p, nmax, "bcsd_rs_apply_kernel");
-        default: return sd_set_error(SD_ERR_INVALID, "unknown register-sort mode %d", mode);
+int sd_bcsd_rs_run(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p0) {
+    sdrs::Params p = p0;
+    p.gmask = L.gmask;
+    p.use_worklist = L.use_worklist;
+    p.RS = L.rs;
+    p.slab_nr = (L.slab_k + 1) / 2;
+    p.slab_k = L.slab_k;
+    switch (L.kernel) {
+        case BcsdKernel::RsFit: return sdrs::launch_mode<sdrs::MODE_FIT>(ctx, L, p);
+        case BcsdKernel::RsRank: return sdrs::launch_mode<sdrs::MODE_RANK>(ctx, L, p);
+        case BcsdKernel::RsApply: return sdrs::launch_mode<sdrs::MODE_APPLY>(ctx, L, p);
+        default: return sd_set_error(SD_ERR_INVALID, "not a register-sort launch: %d", (int)L.kernel);
     }
-}
-
-// The groups of a call that needs the 21-wide kernels but has groups fitting 19 samples per lane (30-day months of a
-// daily series) are split over two launches: narrow = groups for the 19-wide kernels (0 when no split applies).
-void sd_bcsd_rs_width_split(int nmax, int G, const int* group_len, unsigned long long* wide, unsigned long long* narrow) {
-    *wide = *narrow = 0ull;
-    if (sd_bcsd_rs_width(nmax) != 21 || group_len == nullptr || G > 64) return;
-    const char* e = sd_dev_env("SD_RS_SPLIT");  // "0": one launch of the widest kernels for every group (A/B measurements)
-    if (e && e[0] == '0') return;
-    unsigned long long nw = 0ull, wd = 0ull;
-    for (int g = 0; g < G; ++g) (group_len[g] <= 64 * 19 ? nw : wd) |= 1ull << g;
-    if (nw != 0ull && wd != 0ull) {
-        *wide = wd;
-        *narrow = nw;
-    }
-}
-
-int sd_bcsd_rs_launch(sd_ctx* ctx, int mode, const sdrs::Params& p, int nmax, const int* group_len) {
-    sdrs::Params q = p;
-    if (q.n_endpoints <= 0) q.n_endpoints = 10;
-    const int kmax = sd_bcsd_rs_width(nmax);
-    q.gmask = 0ull;
-    q.slab_nr = (kmax + 1) / 2;
-    q.slab_k = kmax;
-    unsigned long long wide = 0ull, narrow = 0ull;
-    if (!p.use_worklist) sd_bcsd_rs_width_split(nmax, p.G, group_len, &wide, &narrow);
-    if (narrow != 0ull) {
-        q.gmask = wide;
-        SD_TRY(rs_launch_one(ctx, mode, q, nmax));
-        q.gmask = narrow;
-        return rs_launch_one(ctx, mode, q, 64 * 19);
-    }
-    return rs_launch_one(ctx, mode, q, nmax);
 }

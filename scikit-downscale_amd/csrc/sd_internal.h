@@ -6,12 +6,14 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <unordered_map>
 #include <string>
 #include <vector>
 
 #include "../../include/sd_downscale.h"
+#include "sd_bcsd_plan.h"
 
 // Internal per-cell status is a bitmask (atomicOr from many workgroups, order independent); it is
 // folded into the public SD_CELL_* code with the reference's precedence on the way out.
@@ -23,6 +25,21 @@ static inline const char* sd_dev_env(const char* name) { return getenv(name); }
 #else
 static inline const char* sd_dev_env(const char*) { return nullptr; }
 #endif
+// the BCSD path switches of the launch plan (sd_bcsd_plan.h): a switch is on when its variable starts with the given text
+static inline BcsdDevSwitches sd_bcsd_dev_switches() {
+    const auto on = [](const char* name, const char* prefix) {
+        const char* e = sd_dev_env(name);
+        return e != nullptr && strncmp(e, prefix, strlen(prefix)) == 0;
+    };
+    BcsdDevSwitches d;
+    d.path_v1 = on("SD_BCSD_PATH", "v1");
+    d.no_fused = on("SD_BCSD_FUSED", "0");
+    d.no_rs_split = on("SD_RS_SPLIT", "0");
+    d.no_dma = on("SD_FX_NODMA", "");
+    d.no_full = on("SD_FX_NOFULL", "");
+    d.no_compact = on("SD_FX_NOCOMPACT", "");
+    return d;
+}
 
 #define SDI_MASKED 1
 #define SDI_NONFINITE 2

@@ -3,19 +3,11 @@
 #pragma once
 #include "sd_internal.h"
 #include "sd_sortnet.h"
+#include "sd_wave_consts.h"
 
 namespace sdw {
 
 using namespace sdsort;
-
-constexpr int kWave = 64;
-constexpr int kW = 8;          // cells per workgroup
-constexpr int kThreads = 512;  // 8 waves
-constexpr int kRowsPerPass = kThreads / 4;  // 4 lanes (16 B each) cover the 8 cells of one row
-// LDS layout of a workgroup: [column-sum exchange: 64 doubles][1/c table: 16][per-cell flags: 8][tile: kW rows of RS].
-// The small areas come first so that no row starts at LDS address 0: the searches keep "address of element - 1"
-// positions and compare them as unsigned numbers.
-constexpr int kHeadDoubles = 64 + 16 + 8;
 
 // The thread index behind an opaque barrier: keeps the compiler from hoisting everything derived from it to the
 // top of the kernel (and keeping it alive in registers across the sorts).
@@ -386,8 +378,7 @@ __device__ __forceinline__ void load_blocked(const double* row, int cnt, int lan
 // 9-sample centred rolling means (bcsd.py:247-250) for CH consecutive samples j0..j0+CH-1 of the wave's
 // segment, which sits in its LDS row in time order *at offset 4 with zeros on both sides* (zero_pads): the
 // CH+8 window values are plain reads at immediate offsets (lane stride K is odd: conflict-free), samples
-// outside [0, m) contribute 0 and the divisor is the clipped window length.
-constexpr int kPadFront = 4;
+// outside [0, m) contribute 0 and the divisor is the clipped window length (kPadFront: sd_wave_consts.h).
 __device__ __forceinline__ void zero_pads(double* row, int m, int lane, int nback) {
     if (lane < kPadFront) row[lane] = 0.0;
     if (lane < nback) row[kPadFront + m + lane] = 0.0;

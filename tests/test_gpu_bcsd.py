@@ -945,8 +945,7 @@ def test_dma_tile_kernel_against_the_register_tile_kernel(dev_ctx, monkeypatch, 
     through registers into per-cell rows): same arithmetic in the same order, so the fields must agree BIT FOR BIT -- for grids
     whose last tile is ragged (even cell counts: the tile is fetched shifted back over its predecessor), cell views of a wider
     resident field (leading dimension > cells, even offsets), a masked cell, a cell with a non-finite sample in each field,
-    and cells with exactly tied shifted samples (work list).  Both variants of the kernel (SD_FD_LATE: the whole y tile behind
-    the vote, second-level keys in the wave's own column).  Against the oracle for the first cells (bcsd.py:197-269)."""
+    and cells with exactly tied shifted samples (work list).  Against the oracle for the first cells (bcsd.py:197-269)."""
     ctx = dev_ctx
     rng = np.random.default_rng(100 + C)
     T = 14600
@@ -965,7 +964,7 @@ def test_dma_tile_kernel_against_the_register_tile_kernel(dev_ctx, monkeypatch, 
     dev = {k: ctx.to_device(v) for k, v in full.items()}
     args = lambda: (dev["X"].cells(c0, c0 + C), dev["y"].cells(c0, c0 + C), gid, 12, dev["Xp"].cells(c0, c0 + C), gid)  # noqa: E731
     res = {}
-    for name, env in (("dma", {}), ("dma_late", {"SD_FD_LATE": "1"}), ("regs", {"SD_FX_NODMA": "1"})):
+    for name, env in (("dma", {}), ("regs", {"SD_FX_NODMA": "1"})):
         for k_, v_ in env.items():
             monkeypatch.setenv(k_, v_)
         big = ctx.to_device(np.full((T, Ct), -777.0))
@@ -979,10 +978,9 @@ def test_dma_tile_kernel_against_the_register_tile_kernel(dev_ctx, monkeypatch, 
         for k_ in env:
             monkeypatch.delenv(k_)
     ref, st_ref = res["regs"]
-    for name in ("dma", "dma_late"):
-        got, st = res[name]
-        assert np.array_equal(st, st_ref), name
-        assert np.array_equal(got, ref, equal_nan=True), f"{name}: differs from the register-tile kernel"
+    got, st = res["dma"]
+    assert np.array_equal(st, st_ref)
+    assert np.array_equal(got, ref, equal_nan=True), "dma: differs from the register-tile kernel"
     assert (np.delete(ref, np.s_[c0:c0 + C], axis=1) == -777.0).all()  # neighbours of the view untouched
     n = min(C, 8)
     exp, est = bo.pointwise_fit_predict(0, X[:, :n], y[:, :n], Xp[:, :n], gid, gid)

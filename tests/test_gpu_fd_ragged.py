@@ -9,7 +9,7 @@ from _cases import assert_close, month_gid
 
 pytestmark = pytest.mark.gpu
 
-ENVS = (("dma", {}), ("dma_late", {"SD_FD_LATE": "1"}), ("regs", {"SD_FX_NODMA": "1"}))
+ENVS = (("dma", {}), ("regs", {"SD_FX_NODMA": "1"}))
 
 
 def _run_variants(ctx, monkeypatch, full, c0, C, gid, G, gid_p=None):
@@ -39,12 +39,11 @@ def _run_variants(ctx, monkeypatch, full, c0, C, gid, G, gid_p=None):
 def _check(res, c0, C, what):
     ref, st_ref, kr = res["regs"]
     assert not any(k.startswith("bcsd_fd_kernel") for k in kr), kr
-    for name in ("dma", "dma_late"):
-        got, st, kernels = res[name]
-        assert "bcsd_fd_kernel_ragged" in kernels, (name, kernels)
-        assert not any(k.startswith("bcsd_fx_kernel") for k in kernels), (name, kernels)
-        assert np.array_equal(st, st_ref), (what, name)
-        assert np.array_equal(got, ref, equal_nan=True), f"{what}: {name} differs from the register-tile kernel"
+    got, st, kernels = res["dma"]
+    assert "bcsd_fd_kernel_ragged" in kernels, kernels
+    assert not any(k.startswith("bcsd_fx_kernel") for k in kernels), kernels
+    assert np.array_equal(st, st_ref), what
+    assert np.array_equal(got, ref, equal_nan=True), f"{what}: dma differs from the register-tile kernel"
     assert (np.delete(ref, np.s_[c0:c0 + C], axis=1) == -777.0).all()  # neighbours of the view untouched
     return ref, st_ref
 

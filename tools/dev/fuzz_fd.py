@@ -65,7 +65,7 @@ def main(n_cases, seed):
             y[int(rng.integers(0, T)), int(rng.integers(0, C))] = np.nan
         dev = {k: ctx.to_device(v) for k, v in full.items()}
         res = {}
-        for name, env in (("dma", {}), ("late", {"SD_FD_LATE": "1"}), ("regs", {"SD_FX_NODMA": "1"})):
+        for name, env in (("dma", {}), ("regs", {"SD_FX_NODMA": "1"})):
             os.environ.update(env)
             big = ctx.to_device(np.full((T, Ct), -777.0))
             ctx.prof_reset()
@@ -84,10 +84,9 @@ def main(n_cases, seed):
         for d in dev.values():
             d.free()
         ref, st_ref = res["regs"]
-        for name in ("dma", "late"):
-            got, st = res[name]
-            assert np.array_equal(st, st_ref), (it, name, "status")
-            assert np.array_equal(got, ref, equal_nan=True), (it, name, style, G, lens, C, c0, Ct)
+        got, st = res["dma"]
+        assert np.array_equal(st, st_ref), (it, "status")
+        assert np.array_equal(got, ref, equal_nan=True), (it, style, G, lens, C, c0, Ct)
         n = min(C, 4)
         exp, est = bo.pointwise_fit_predict(0, X[:, :n].copy(), y[:, :n].copy(), Xp[:, :n].copy(), gid, gid_p, G=G)
         assert np.array_equal(st_ref[:n], est), (it, "oracle status")
