@@ -12,6 +12,10 @@
  *   sd_analog_fit*          <- AnalogBase.fit (gard.py:58-87)
  *   sd_analog_predict*      <- PureAnalog.predict (gard.py:273-364)
  *   sd_analogreg_predict*   <- AnalogRegression.predict, thresh=None (gard.py:152-224)
+ *   sd_zscore_fit*          <- ZScoreRegressor.fit (zscore.py:32-69: _reshape / _calc_stats / _get_params, 123-238)
+ *   sd_zscore_predict*      <- ZScoreRegressor.predict (zscore.py:71-112: _get_fut_stats / _expand_params /
+ *                              _correct_fut_stats, 241-354)
+ *   sd_zscore_state_*       <- the fitted shift_ / scale_ / fit_stats_dict_ (zscore.py:24, 56-67)
  *
  * Conventions
  *   - Plain pointers and sizes only.  All fields are float64, time-major with the cell axis
@@ -38,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SD_VERSION 103  /* bump on every change of an exported signature: the Python loader refuses other versions */
+#define SD_VERSION 104  /* bump on every change of an exported signature: the Python loader refuses other versions */
 
 /* return codes */
 #define SD_OK 0
@@ -88,6 +92,7 @@ typedef struct sd_bcsd_state sd_bcsd_state;
 typedef struct sd_analog_state sd_analog_state;
 typedef struct sd_qm_state sd_qm_state;
 typedef struct sd_linreg_state sd_linreg_state;
+typedef struct sd_zscore_state sd_zscore_state;
 typedef struct sd_comm sd_comm;
 #define SD_COMM_ID_BYTES 128 /* RCCL's ncclUniqueId */
 
@@ -284,6 +289,31 @@ int sd_linreg_state_export(const sd_linreg_state* st, double* coef, double* inte
 int sd_linreg_state_import(sd_ctx* ctx, int64_t T, int F, int64_t C, const double* coef, const double* intercept, const double* fit_error,
                            const double* logistic, const int32_t* thresh_dropped, const int32_t* cell_status, sd_linreg_state** out);
 int sd_linreg_state_destroy(sd_linreg_state* st);
+
+/* ---- ZScoreRegressor -----------------------------------------------------------------------------------
+ * fit: X, y [T, C].  day_idx: host int32[T], the position of each sample's day of year in the sorted union of the days that
+ * occur (D of them, each with a sample); year: host int32[T], the sample's calendar year (two samples on one (year, day) are
+ * refused like the reference's alignment does).  Per cell the mean and population std of X and of y over the kept day windows
+ * of width window_width (K of them: sd_zscore_plan.h), shift = y_mean - X_mean, scale = y_std / X_std.
+ * predict: out [Tp, C] = z * (std * scale) + (mean + shift) with pandas' centred rolling mean / std (ddof = 1) of Xp and the
+ * parameters expanded by position (entry t % min(Tp, 364); SD_ERR_INVALID past K).  meani / stdi / meanf / stdf [Tp, C]
+ * (predict_stats_dict_) are written when not NULL, with the pitch ld_out in the _dev variant. */
+int sd_zscore_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t C, int window_width, const int32_t* day_idx,
+                  const int32_t* year, int D, sd_zscore_state** out);
+int sd_zscore_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, int window_width,
+                      const int32_t* day_idx, const int32_t* year, int D, sd_zscore_state** out);
+int sd_zscore_predict(sd_ctx* ctx, const sd_zscore_state* st, const double* Xp, int64_t Tp, double* out, double* meani, double* stdi,
+                      double* meanf, double* stdf, int32_t* cell_status);
+int sd_zscore_predict_dev(sd_ctx* ctx, const sd_zscore_state* st, const double* Xp_dev, int64_t ld, int64_t Tp, double* out_dev,
+                          int64_t ld_out, double* meani_dev, double* stdi_dev, double* meanf_dev, double* stdf_dev, int32_t* cell_status);
+int sd_zscore_state_info(const sd_zscore_state* st, int64_t* K, int64_t* C, int* window_width);
+/* [K][C] planes (any pointer may be NULL) and the per-cell status: pickling and get_attr */
+int sd_zscore_state_export(const sd_zscore_state* st, double* x_mean, double* x_std, double* y_mean, double* y_std, double* shift,
+                           double* scale, int32_t* cell_status);
+int sd_zscore_state_import(sd_ctx* ctx, int64_t K, int64_t C, int window_width, const double* x_mean, const double* x_std,
+                           const double* y_mean, const double* y_std, const double* shift, const double* scale,
+                           const int32_t* cell_status, sd_zscore_state** out);
+int sd_zscore_state_destroy(sd_zscore_state* st);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

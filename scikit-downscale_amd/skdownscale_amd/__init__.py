@@ -10,6 +10,7 @@ from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
+from .zscore import ZScoreGridModel, ZScoreRegressor
 
 __all__ = [
     "AnalogRegression",
@@ -34,5 +35,7 @@ __all__ = [
     "PureRegression",
     "LinearTrendTransformer",
     "RegressionGridModel",
+    "ZScoreRegressor",
+    "ZScoreGridModel",
 ]
 __version__ = "0.1.0"

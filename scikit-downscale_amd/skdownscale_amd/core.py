@@ -21,6 +21,7 @@ from .bcsd import BcsdBase, check_supported
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .quantile import (CunnaneGridModel, CunnaneTransformer, QmGridModel, QuantileMapper, QuantileMapperGridModel,
                        QuantileMappingReressor, check_extrapolate)
+from .zscore import ZScoreGridModel, ZScoreRegressor
 
 DEFAULT_FEATURE_DIM = "variable"
 
@@ -244,7 +245,7 @@ class _BatchedModels:
     """Fitted state of a whole grid held by the engine (replaces the object array of estimators)."""
 
     def __init__(self, kind, grid_model, mask, spatial_dims, spatial_shape, coords):
-        self.kind = kind  # 'bcsd' | 'analog' | 'qm' | 'cunnane' | 'qmapper' | 'loop'
+        self.kind = kind  # 'bcsd' | 'analog' | 'linreg' | 'qm' | 'cunnane' | 'qmapper' | 'zscore' | 'loop'
         self.grid_model = grid_model
         self.mask = mask
         self.spatial_dims = spatial_dims
@@ -406,6 +407,8 @@ class PointWiseDownscaler:
         if isinstance(m, QuantileMapper):
             m._check()
             return "qmapper"
+        if isinstance(m, ZScoreRegressor):
+            return "zscore"
         return None
 
     # ------------------------------------------------------------------------------------------
@@ -470,6 +473,13 @@ class PointWiseDownscaler:
                 gm.fit(np.ascontiguousarray(Xg.values).reshape(T, C), np.ascontiguousarray(yg.values).reshape(T, C), index)
             else:
                 gm.fit(Xv[:, 0, :], yv, index)
+            self._raise_for_status(gm.status_, Xv[:, 0, :], yv)
+        elif kind == "zscore":
+            if F != 1:
+                raise ValueError(f"Zscore only supports 1 feature, found {F}")
+            if T == 1:  # zscore.py:51-52: X.squeeze() of one sample is a scalar
+                raise TypeError("X.squeeze() must be a pd.Series, got float64")
+            gm = ZScoreGridModel(m.window_width).fit(Xv[:, 0, :], yv, index)
             self._raise_for_status(gm.status_, Xv[:, 0, :], yv)
         elif kind == "qm":
             if F != 1:
@@ -572,6 +582,13 @@ class PointWiseDownscaler:
                 out, status = mdl.grid_model.predict(np.ascontiguousarray(Xg.values).reshape(T, C), index, out_dtype=np.float32)
             else:
                 out, status = mdl.grid_model.predict(Xv[:, 0, :], index)
+            self._raise_for_status(status, Xv[:, 0, :], Xv[:, 0, :])
+            vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
+            res = GridArray(vals, (self._dim,) + spatial_dims, coords)
+        elif mdl.kind == "zscore":
+            if F != 1:
+                raise ValueError(f"X must have exactly 1 feature, got {F}")
+            out, status, _ = mdl.grid_model.predict(Xv[:, 0, :])
             self._raise_for_status(status, Xv[:, 0, :], Xv[:, 0, :])
             vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
             res = GridArray(vals, (self._dim,) + spatial_dims, coords)
@@ -691,6 +708,11 @@ class PointWiseDownscaler:
                 est.thresh = None  # gard.py:437
             est._adopt(e, c)
             return est
+        if mdl.kind == "zscore":
+            e = cache.setdefault("e", mdl.grid_model.export())
+            est = copy.deepcopy(m)
+            est._adopt(e, c, e["labels"])
+            return est
         if mdl.kind == "analog":
             est = copy.deepcopy(m)
             est.k_ = mdl.grid_model.k_
@@ -730,7 +752,8 @@ class PointWiseDownscaler:
         """Get attribute values specified in ``key`` from each of the pointwise models (core.py:405-425, 174-197): an array
         shaped like the model grid, or like ``template_output`` (whose non-spatial dims receive array-valued attributes).
         Engine-batched grids rebuild the per-cell fitted attributes from the exported state.  Extension: without a template,
-        the BCSD climatologies ``y_climo_`` / ``_x_climo`` come back as [group, *spatial] fields."""
+        the BCSD climatologies ``y_climo_`` / ``_x_climo`` come back as [group, *spatial] fields, and the ZScoreRegressor
+        parameters ``shift_`` / ``scale_`` as [day, *spatial] fields."""
         mdl = self._models
         if mdl is None:
             raise ValueError("PointWiseDownscaler is not fitted: call fit() first")
@@ -743,6 +766,12 @@ class PointWiseDownscaler:
             coords = dict(mdl.coords)
             coords["group"] = e["keys"]
             return GridArray(a.reshape((a.shape[0],) + tuple(mdl.spatial_shape)), ("group",) + tuple(mdl.spatial_dims), coords)
+        if mdl.kind == "zscore" and key in ("shift_", "scale_") and template_output is None:
+            e = mdl.grid_model.export()
+            a = np.where(mdl.mask[None, :], e[key[:-1]], np.nan).astype(dtype)  # [K, C]
+            coords = dict(mdl.coords)
+            coords["day"] = e["labels"]
+            return GridArray(a.reshape((a.shape[0],) + tuple(mdl.spatial_shape)), ("day",) + tuple(mdl.spatial_dims), coords)
         sp_dims, sp_shape = tuple(mdl.spatial_dims), tuple(mdl.spatial_shape)
         was_x = False
         if template_output is None:

@@ -162,6 +162,28 @@ class LinregState(_State):
         return out
 
 
+class ZscoreState(_State):
+    STATS = ("x_mean", "x_std", "y_mean", "y_std", "shift", "scale")
+
+    def info(self):
+        K, Cc, w = C.c_int64(), C.c_int64(), C.c_int()
+        check(self.ctx.lib.sd_zscore_state_info(self.vptr, C.byref(K), C.byref(Cc), C.byref(w)))
+        return dict(K=K.value, C=Cc.value, window_width=w.value)
+
+    def status(self):
+        status = np.empty(self.info()["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_zscore_state_export(self.vptr, None, None, None, None, None, None, ptr(status)))
+        return status
+
+    def export(self):
+        """x_mean, x_std, y_mean, y_std, shift, scale [K, C] (kept day windows x cells), status [C], window_width"""
+        i = self.info()
+        planes = {k: np.empty((i["K"], i["C"])) for k in self.STATS}
+        status = np.empty(i["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_zscore_state_export(self.vptr, *[ptr(planes[k]) for k in self.STATS], ptr(status)))
+        return dict(planes, status=status, window_width=i["window_width"])
+
+
 class QmState(_State):
     def info(self):
         T, Cc = C.c_int64(), C.c_int64()
@@ -675,6 +697,56 @@ class Context:
             out = np.empty((Tq, 3, Cc))
             check(self.lib.sd_linreg_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(out), ptr(status)))
         return out, status
+
+    # ---- ZScoreRegressor ----
+    def zscore_fit(self, X, y, window_width, day_idx, year, D):
+        """X, y [T, C] (numpy or DeviceArray); day_idx / year: host [T] (sd_zscore_fit) -> ZscoreState"""
+        X = self._field2("X", X)
+        y = self._field2("y", y, *X.shape)
+        T, Cc = X.shape
+        day_idx, year = _lib.as_i32(day_idx), _lib.as_i32(year)
+        if day_idx.shape != (T,) or year.shape != (T,):
+            raise ValueError(f"day_idx and year: expected {T} entries, got {day_idx.shape} and {year.shape}")
+        h = C.c_void_p()
+        if isinstance(X, DeviceArray):
+            if not isinstance(y, DeviceArray) or X.ld != y.ld:
+                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
+            check(self.lib.sd_zscore_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(window_width), ptr(day_idx), ptr(year), int(D),
+                                             C.byref(h)))
+        else:
+            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
+            check(self.lib.sd_zscore_fit(self.handle, ptr(X), ptr(y), T, Cc, int(window_width), ptr(day_idx), ptr(year), int(D), C.byref(h)))
+        return ZscoreState(self, h.value, self.lib.sd_zscore_state_destroy)
+
+    def zscore_import(self, exported):
+        """device state from ``ZscoreState.export()`` (pickling)"""
+        planes = [_lib.as_f64(exported[k]) for k in ZscoreState.STATS]
+        K, Cc = planes[0].shape
+        if any(p.shape != (K, Cc) for p in planes):
+            raise ValueError("zscore_import: the six planes must share one [K, C] shape")
+        h = C.c_void_p()
+        check(self.lib.sd_zscore_state_import(self.handle, K, Cc, int(exported["window_width"]), *[ptr(p) for p in planes],
+                                              ptr(_lib.as_i32(exported["status"])), C.byref(h)))
+        return ZscoreState(self, h.value, self.lib.sd_zscore_state_destroy)
+
+    def zscore_predict(self, state, Xp, out=None, with_stats=False):
+        """Xp [Tp, C] -> (out [Tp, C], cell status [C], stats): stats = dict(meani, stdi, meanf, stdf) of [Tp, C] fields (on the
+        device for a DeviceArray input) when ``with_stats``, else None"""
+        Cc = state.info()["C"]
+        Xp = self._field2("Xp", Xp, None, Cc)
+        Tp = Xp.shape[0]
+        dev = isinstance(Xp, DeviceArray)
+        out = self._result_buffer(out, (Tp, Cc), dev)
+        stats = {k: (self.empty((Tp, Cc)) if dev else np.empty((Tp, Cc))) for k in ("meani", "stdi", "meanf", "stdf")} if with_stats else None
+        if dev and stats is not None and out.ld != Cc:
+            raise ValueError("zscore_predict: the stats fields share the pitch of `out`, which must be contiguous here")
+        sp = [None] * 4 if stats is None else [s.vptr if dev else ptr(s) for s in stats.values()]
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
+            check(self.lib.sd_zscore_predict_dev(self.handle, state.vptr, Xp.vptr, Xp.ld, Tp, out.vptr, out.ld, *sp, ptr(status)))
+        else:
+            check(self.lib.sd_zscore_predict(self.handle, state.vptr, ptr(Xp), Tp, ptr(out), *sp, ptr(status)))
+        return out, status, stats
 
 
 _default_ctx = None

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Secondary measurements (BASELINE configs 3 and 4): BcsdPrecipitation and PureAnalog on one MI355X.
+"""Secondary measurements (BASELINE configs 3 and 4 and the other estimators) on one MI355X.
 
 Not the headline bench (bench.py); prints one JSON line per workload with the same roofline convention:
 algorithmic bytes per cell / kernel time from HIP events on the engine's stream.
@@ -22,7 +22,7 @@ from skdownscale_amd.engine import Context  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression"], default="analog")
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore"], default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
     ap.add_argument("--steps", type=int, default=2)
@@ -48,6 +48,21 @@ def main():
         step = lambda: ctx.bcsd_fit_predict(_lib.BCSD_PR, f["X_hist"], f["y_obs"], gid, 12, f["X_fut"], gid, True, out=out)  # noqa: E731
         bytes_per_cell = 8 * (T + 2 * T)  # y_obs, X_fut, out (X_hist is only validated: + 8*T actually read)
         name = f"BcsdPrecipitation zero-inflated, {C} cells x {T} steps"
+    elif args.workload == "zscore":
+        from skdownscale_amd.zscore import ZScoreGridModel
+
+        tabs = synth.tas_tables(index)
+        f = {n: field(synth.GAUSS, tabs[n]["stream"], base=tabs[n]["base"], amp=tabs[n]["amp"], cell_scale=tabs[n]["cell_scale"])
+             for n in ("X_hist", "y_obs", "X_fut")}
+        out = ctx.empty((T, C))
+
+        def step():
+            gm = ZScoreGridModel(31, ctx=ctx).fit(f["X_hist"], f["y_obs"], index)
+            r = gm.predict(f["X_fut"], out=out)
+            gm.state.close()
+            return r
+        bytes_per_cell = 8 * (2 * T + 2 * T)  # fit reads X and y, predict reads X_fut and writes out: 32 B per cell-step
+        name = f"ZScoreRegressor w=31 (fit + predict), {C} cells x {T} steps"
     elif args.workload in ("qmr", "ecm"):
         f = {n: field(synth.GAUSS, s0, amp=a) for n, s0, a in (("X", 30, 3.0), ("y", 31, 4.0), ("Xp", 32, 3.5))}
         out = ctx.empty((T, C))
