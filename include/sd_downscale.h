@@ -16,6 +16,10 @@
  *   sd_zscore_predict*      <- ZScoreRegressor.predict (zscore.py:71-112: _get_fut_stats / _expand_params /
  *                              _correct_fut_stats, 241-354)
  *   sd_zscore_state_*       <- the fitted shift_ / scale_ / fit_stats_dict_ (zscore.py:24, 56-67)
+ *   sd_grouped_fit*         <- GroupedRegressor.fit with LinearRegression as estimator (grouping.py:53-80) on the groups of
+ *                              grouping.PaddedDOYGrouper (grouping.py:106-138), or on disjoint groups (window = 0)
+ *   sd_grouped_predict*     <- GroupedRegressor.predict (grouping.py:82-103): the model of each sample's own key
+ *   sd_grouped_state_*      <- the fitted estimators_ (coef_, intercept_ of every group; grouping.py:74)
  *
  * Conventions
  *   - Plain pointers and sizes only.  All fields are float64, time-major with the cell axis
@@ -42,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SD_VERSION 104  /* bump on every change of an exported signature: the Python loader refuses other versions */
+#define SD_VERSION 105  /* bump on every change of an exported signature: the Python loader refuses other versions */
 
 /* return codes */
 #define SD_OK 0
@@ -93,6 +97,7 @@ typedef struct sd_analog_state sd_analog_state;
 typedef struct sd_qm_state sd_qm_state;
 typedef struct sd_linreg_state sd_linreg_state;
 typedef struct sd_zscore_state sd_zscore_state;
+typedef struct sd_grouped_state sd_grouped_state;
 typedef struct sd_comm sd_comm;
 #define SD_COMM_ID_BYTES 128 /* RCCL's ncclUniqueId */
 
@@ -314,6 +319,31 @@ int sd_zscore_state_import(sd_ctx* ctx, int64_t K, int64_t C, int window_width, 
                            const double* y_mean, const double* y_std, const double* shift, const double* scale,
                            const int32_t* cell_status, sd_zscore_state** out);
 int sd_zscore_state_destroy(sd_zscore_state* st);
+
+/* ---- GroupedRegressor (one LinearRegression per group) -------------------------------------------------
+ * fit: X [T, F, C], y [T, C], F in [1, 8].  key: host int32[T], the key of every time step in [0, n), shared by all cells
+ * (day of year - 1 for grouping.PaddedDOYGrouper, n = the largest day of year).  Group g of [0, n) is fitted per cell by
+ * ordinary least squares (sklearn LinearRegression: centred, minimum norm when rank deficient) on the samples whose key
+ * lies in {g - window .. g + window} modulo n, every key once; 0 <= window < n, window = 0 gives disjoint groups.  A group
+ * whose window holds no sample is not fitted.
+ * predict: out [Tq, C], out[t, c] = intercept[key[t], c] + sum_f coef[key[t], f, c] * Xq[t, f, c].  A key outside [0, n) or
+ * without a fitted model is SD_ERR_INVALID; sd_last_error names the smallest such key ("no fitted model for key K").
+ * Cell status as for sd_linreg_*. */
+int sd_grouped_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int F, int64_t C, const int32_t* key, int n, int window,
+                   sd_grouped_state** out);
+int sd_grouped_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int F, int64_t C,
+                       const int32_t* key, int n, int window, sd_grouped_state** out);
+int sd_grouped_predict(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq, int64_t Tq, const int32_t* key, double* out,
+                       int32_t* cell_status);
+int sd_grouped_predict_dev(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, const int32_t* key,
+                           double* out_dev, int64_t ld_out, int32_t* cell_status);
+int sd_grouped_state_info(const sd_grouped_state* st, int* n, int* F, int64_t* C, int* window);
+/* coef [n, F, C], intercept [n, C] (NaN for groups that are not fitted and for cells with a status), fitted int32[n],
+ * cell_status int32[C]; any pointer may be NULL */
+int sd_grouped_state_export(const sd_grouped_state* st, double* coef, double* intercept, int32_t* fitted, int32_t* cell_status);
+int sd_grouped_state_import(sd_ctx* ctx, int n, int F, int64_t C, int window, const double* coef, const double* intercept,
+                            const int32_t* fitted, const int32_t* cell_status, sd_grouped_state** out);
+int sd_grouped_state_destroy(sd_grouped_state* st);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

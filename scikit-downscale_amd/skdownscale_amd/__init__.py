@@ -7,6 +7,7 @@ from .bcsd import BcsdGridModel, BcsdPrecipitation, BcsdTemperature
 from .core import GridArray, GridDataset, PointWiseDownscaler
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
+from .grouping import GroupedGridModel, GroupedRegressor
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -37,5 +38,7 @@ __all__ = [
     "RegressionGridModel",
     "ZScoreRegressor",
     "ZScoreGridModel",
+    "GroupedRegressor",
+    "GroupedGridModel",
 ]
 __version__ = "0.1.0"

@@ -97,6 +97,14 @@ SIGNATURES = {
     "sd_zscore_state_export": [_p, _p, _p, _p, _p, _p, _p, _p],
     "sd_zscore_state_import": [_p, _i64, _i64, _int, _p, _p, _p, _p, _p, _p, _p, C.POINTER(_p)],
     "sd_zscore_state_destroy": [_p],
+    "sd_grouped_fit": [_p, _p, _p, _i64, _int, _i64, _p, _int, _int, C.POINTER(_p)],
+    "sd_grouped_fit_dev": [_p, _p, _p, _i64, _i64, _int, _i64, _p, _int, _int, C.POINTER(_p)],
+    "sd_grouped_predict": [_p, _p, _p, _i64, _p, _p, _p],
+    "sd_grouped_predict_dev": [_p, _p, _p, _i64, _i64, _p, _p, _i64, _p],
+    "sd_grouped_state_info": [_p, C.POINTER(_int), C.POINTER(_int), C.POINTER(_i64), C.POINTER(_int)],
+    "sd_grouped_state_export": [_p, _p, _p, _p, _p],
+    "sd_grouped_state_import": [_p, _int, _int, _i64, _int, _p, _p, _p, _p, C.POINTER(_p)],
+    "sd_grouped_state_destroy": [_p],
     "sd_qm_fit": [_p, _p, _p, _i64, _i64, C.POINTER(_p)],
     "sd_qm_fit_dev": [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_p)],
     "sd_qm_predict": [_p, _p, _int, _int, _int, _p, _i64, _p, _p],
@@ -119,7 +127,7 @@ SIGNATURES = {
 
 _libs = {}
 QT_TAIL_LOWER, QT_TAIL_UPPER = 1, 2  # sd_bcsd_state_set_tails
-ABI_VERSION = 104  # include/sd_downscale.h: SD_VERSION
+ABI_VERSION = 105  # include/sd_downscale.h: SD_VERSION
 
 
 class EngineError(RuntimeError):

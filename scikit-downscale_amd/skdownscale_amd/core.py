@@ -21,6 +21,7 @@ from .bcsd import BcsdBase, check_supported
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .quantile import (CunnaneGridModel, CunnaneTransformer, QmGridModel, QuantileMapper, QuantileMapperGridModel,
                        QuantileMappingReressor, check_extrapolate)
+from .grouping import GroupedGridModel, GroupedRegressor
 from .zscore import ZScoreGridModel, ZScoreRegressor
 
 DEFAULT_FEATURE_DIM = "variable"
@@ -245,7 +246,7 @@ class _BatchedModels:
     """Fitted state of a whole grid held by the engine (replaces the object array of estimators)."""
 
     def __init__(self, kind, grid_model, mask, spatial_dims, spatial_shape, coords):
-        self.kind = kind  # 'bcsd' | 'analog' | 'linreg' | 'qm' | 'cunnane' | 'qmapper' | 'zscore' | 'loop'
+        self.kind = kind  # 'bcsd' | 'analog' | 'linreg' | 'qm' | 'cunnane' | 'qmapper' | 'zscore' | 'grouped' | 'loop'
         self.grid_model = grid_model
         self.mask = mask
         self.spatial_dims = spatial_dims
@@ -409,6 +410,9 @@ class PointWiseDownscaler:
             return "qmapper"
         if isinstance(m, ZScoreRegressor):
             return "zscore"
+        if isinstance(m, GroupedRegressor):
+            m._check_engine()
+            return "grouped"
         return None
 
     # ------------------------------------------------------------------------------------------
@@ -481,6 +485,22 @@ class PointWiseDownscaler:
                 raise TypeError("X.squeeze() must be a pd.Series, got float64")
             gm = ZScoreGridModel(m.window_width).fit(Xv[:, 0, :], yv, index)
             self._raise_for_status(gm.status_, Xv[:, 0, :], yv)
+        elif kind == "grouped":
+            plan = m._fit_plan(index)
+            if plan is None:
+                from .grouping import SUPPORTED
+
+                raise NotImplementedError(f"GroupedRegressor on a grid with overlapping groups from {m.fit_grouper!r}: {SUPPORTED}")
+            per_step, labels, window = plan
+            gm = GroupedGridModel(window).fit_labels(Xv, yv, per_step, labels)
+            if not gm.fitted_.all():
+                from .grouping import NO_SAMPLES_MESSAGE
+
+                raise ValueError(NO_SAMPLES_MESSAGE.format(F=F))
+            bad = mask & (gm.status_ == _lib.CELL_NONFINITE)
+            if bad.any():
+                c = int(np.flatnonzero(bad)[0])
+                self._raise_for_status(np.where(bad, _lib.CELL_NONFINITE, 0), Xv[:, :, c:c + 1].reshape(T, -1), yv[:, c:c + 1], cell=c)
         elif kind == "qm":
             if F != 1:
                 raise ValueError(f"Found array with {F} features (shape=({T}, {F})) while a maximum of 1 is required")
@@ -590,6 +610,12 @@ class PointWiseDownscaler:
                 raise ValueError(f"X must have exactly 1 feature, got {F}")
             out, status, _ = mdl.grid_model.predict(Xv[:, 0, :])
             self._raise_for_status(status, Xv[:, 0, :], Xv[:, 0, :])
+            vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
+            res = GridArray(vals, (self._dim,) + spatial_dims, coords)
+        elif mdl.kind == "grouped":
+            out, status = mdl.grid_model.predict_labels(Xv, self._model._predict_labels(index))
+            if (mdl.mask & (status == _lib.CELL_NONFINITE)).any():
+                raise ValueError("Input X contains NaN.")
             vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
             res = GridArray(vals, (self._dim,) + spatial_dims, coords)
         elif mdl.kind == "qm":
@@ -713,6 +739,11 @@ class PointWiseDownscaler:
             est = copy.deepcopy(m)
             est._adopt(e, c, e["labels"])
             return est
+        if mdl.kind == "grouped":
+            e = cache.setdefault("e", mdl.grid_model.export())
+            est = copy.deepcopy(m)
+            est._adopt(e, c)
+            return est
         if mdl.kind == "analog":
             est = copy.deepcopy(m)
             est.k_ = mdl.grid_model.k_
@@ -752,8 +783,9 @@ class PointWiseDownscaler:
         """Get attribute values specified in ``key`` from each of the pointwise models (core.py:405-425, 174-197): an array
         shaped like the model grid, or like ``template_output`` (whose non-spatial dims receive array-valued attributes).
         Engine-batched grids rebuild the per-cell fitted attributes from the exported state.  Extension: without a template,
-        the BCSD climatologies ``y_climo_`` / ``_x_climo`` come back as [group, *spatial] fields, and the ZScoreRegressor
-        parameters ``shift_`` / ``scale_`` as [day, *spatial] fields."""
+        the BCSD climatologies ``y_climo_`` / ``_x_climo`` come back as [group, *spatial] fields, the ZScoreRegressor
+        parameters ``shift_`` / ``scale_`` as [day, *spatial] fields, and the GroupedRegressor models ``coef_`` / ``intercept_`` as
+        [group, feature, *spatial] / [group, *spatial] fields."""
         mdl = self._models
         if mdl is None:
             raise ValueError("PointWiseDownscaler is not fitted: call fit() first")
@@ -766,6 +798,13 @@ class PointWiseDownscaler:
             coords = dict(mdl.coords)
             coords["group"] = e["keys"]
             return GridArray(a.reshape((a.shape[0],) + tuple(mdl.spatial_shape)), ("group",) + tuple(mdl.spatial_dims), coords)
+        if mdl.kind == "grouped" and key in ("coef_", "intercept_") and template_output is None:
+            e = mdl.grid_model.export()
+            a = np.where(mdl.mask, e[key[:-1]], np.nan).astype(dtype)  # [n, F, C] or [n, C]
+            coords = dict(mdl.coords)
+            coords["group"] = e["labels"]
+            lead = ("group", DEFAULT_FEATURE_DIM) if key == "coef_" else ("group",)
+            return GridArray(a.reshape(a.shape[:len(lead)] + tuple(mdl.spatial_shape)), lead + tuple(mdl.spatial_dims), coords)
         if mdl.kind == "zscore" and key in ("shift_", "scale_") and template_output is None:
             e = mdl.grid_model.export()
             a = np.where(mdl.mask[None, :], e[key[:-1]], np.nan).astype(dtype)  # [K, C]

@@ -184,6 +184,31 @@ class ZscoreState(_State):
         return dict(planes, status=status, window_width=i["window_width"])
 
 
+class GroupedState(_State):
+    def info(self):
+        n, F, Cc, w = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        check(self.ctx.lib.sd_grouped_state_info(self.vptr, C.byref(n), C.byref(F), C.byref(Cc), C.byref(w)))
+        return dict(n=n.value, F=F.value, C=Cc.value, window=w.value)
+
+    def status(self):
+        status = np.empty(self.info()["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_grouped_state_export(self.vptr, None, None, None, ptr(status)))
+        return status
+
+    def fitted(self):
+        fitted = np.empty(self.info()["n"], dtype=np.int32)
+        check(self.ctx.lib.sd_grouped_state_export(self.vptr, None, None, ptr(fitted), None))
+        return fitted.astype(bool)
+
+    def export(self):
+        """coef [n, F, C], intercept [n, C], fitted [n] (bool), status [C], window"""
+        i = self.info()
+        coef, icpt = np.empty((i["n"], i["F"], i["C"])), np.empty((i["n"], i["C"]))
+        fitted, status = np.empty(i["n"], dtype=np.int32), np.empty(i["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_grouped_state_export(self.vptr, ptr(coef), ptr(icpt), ptr(fitted), ptr(status)))
+        return dict(coef=coef, intercept=icpt, fitted=fitted.astype(bool), status=status, window=i["window"])
+
+
 class QmState(_State):
     def info(self):
         T, Cc = C.c_int64(), C.c_int64()
@@ -747,6 +772,61 @@ class Context:
         else:
             check(self.lib.sd_zscore_predict(self.handle, state.vptr, ptr(Xp), Tp, ptr(out), *sp, ptr(status)))
         return out, status, stats
+
+    # ---- GroupedRegressor ----
+    def grouped_fit(self, X, y, key, n, window):
+        """X [T, F, C], y [T, C] (numpy or DeviceArray); key: host [T] in [0, n) (sd_grouped_fit) -> GroupedState"""
+        if not isinstance(X, DeviceArray):
+            X = _lib.as_f64(X)
+        if len(X.shape) != 3:
+            raise ValueError(f"X: expected a [T, F, C] field, got shape {tuple(X.shape)}")
+        T, F, Cc = X.shape
+        y = self._field2("y", y, T, Cc)
+        key = _lib.as_i32(key)
+        if key.shape != (T,):
+            raise ValueError(f"key: expected {T} entries, got shape {key.shape}")
+        h = C.c_void_p()
+        if isinstance(X, DeviceArray):
+            if not isinstance(y, DeviceArray) or X.ld != y.ld:
+                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
+            check(self.lib.sd_grouped_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, F, Cc, ptr(key), int(n), int(window), C.byref(h)))
+        else:
+            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
+            check(self.lib.sd_grouped_fit(self.handle, ptr(X), ptr(y), T, F, Cc, ptr(key), int(n), int(window), C.byref(h)))
+        return GroupedState(self, h.value, self.lib.sd_grouped_state_destroy)
+
+    def grouped_import(self, exported):
+        """device state from ``GroupedState.export()`` (pickling)"""
+        coef, icpt = _lib.as_f64(exported["coef"]), _lib.as_f64(exported["intercept"])
+        n, F, Cc = coef.shape
+        fitted = _lib.as_i32(exported["fitted"])
+        if icpt.shape != (n, Cc) or fitted.shape != (n,):
+            raise ValueError("grouped_import: expected coef [n, F, C], intercept [n, C] and fitted [n]")
+        h = C.c_void_p()
+        check(self.lib.sd_grouped_state_import(self.handle, n, F, Cc, int(exported["window"]), ptr(coef), ptr(icpt), ptr(fitted),
+                                               ptr(_lib.as_i32(exported["status"])), C.byref(h)))
+        return GroupedState(self, h.value, self.lib.sd_grouped_state_destroy)
+
+    def grouped_predict(self, state, Xq, key, out=None):
+        """Xq [Tq, F, C], key: host [Tq] -> (out [Tq, C], cell status [C]); a key without a fitted model is a ValueError"""
+        info = state.info()
+        Cc = info["C"]
+        if not isinstance(Xq, DeviceArray):
+            Xq = _lib.as_f64(Xq)
+        if len(Xq.shape) != 3 or Xq.shape[1] != info["F"] or Xq.shape[2] != Cc:
+            raise ValueError(f"Xq: expected a [Tq, {info['F']}, {Cc}] field, got shape {tuple(Xq.shape)}")
+        Tq = Xq.shape[0]
+        key = _lib.as_i32(key)
+        if key.shape != (Tq,):
+            raise ValueError(f"key: expected {Tq} entries, got shape {key.shape}")
+        dev = isinstance(Xq, DeviceArray)
+        out = self._result_buffer(out, (Tq, Cc), dev)
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
+            check(self.lib.sd_grouped_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, ptr(key), out.vptr, out.ld, ptr(status)))
+        else:
+            check(self.lib.sd_grouped_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(key), ptr(out), ptr(status)))
+        return out, status
 
 
 _default_ctx = None

@@ -22,7 +22,7 @@ from skdownscale_amd.engine import Context  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore"], default="analog")
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped"], default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
     ap.add_argument("--steps", type=int, default=2)
@@ -63,6 +63,25 @@ def main():
             return r
         bytes_per_cell = 8 * (2 * T + 2 * T)  # fit reads X and y, predict reads X_fut and writes out: 32 B per cell-step
         name = f"ZScoreRegressor w=31 (fit + predict), {C} cells x {T} steps"
+    elif args.workload == "grouped":
+        from skdownscale_amd.grouping import GroupedGridModel
+
+        F = args.features
+        tabs = synth.tas_tables(index)
+        y = field(synth.GAUSS, tabs["y_obs"]["stream"], base=tabs["y_obs"]["base"], amp=tabs["y_obs"]["amp"], cell_scale=tabs["y_obs"]["cell_scale"])
+        X3, Xq3 = ctx.empty((T, F, C)), ctx.empty((T, F, C))
+        for n, arr in (("X_hist", X3), ("X_fut", Xq3)):  # [T, F, C]: feature f of time t is row t*F + f
+            ctx.synth_fill(ctx.wrap(arr.ptr, (T * F, C)), synth.GAUSS, 0, tabs[n]["stream"], c_full=C, base=np.repeat(tabs[n]["base"], F),
+                           amp=tabs[n]["amp"])
+        out = ctx.empty((T, C))
+
+        def step():
+            gm = GroupedGridModel(15, ctx=ctx).fit(X3, y, index)
+            r = gm.predict(Xq3, index, out=out)
+            gm.state.close()
+            return r
+        bytes_per_cell = 8 * ((F + 1) * T + (F + 1) * T)  # fit reads X and y, predict reads X_fut and writes out
+        name = f"GroupedRegressor LinearRegression per day of year, window=15, F={F} (fit + predict), {C} cells x {T} steps"
     elif args.workload in ("qmr", "ecm"):
         f = {n: field(synth.GAUSS, s0, amp=a) for n, s0, a in (("X", 30, 3.0), ("y", 31, 4.0), ("Xp", 32, 3.5))}
         out = ctx.empty((T, C))
