@@ -54,62 +54,8 @@ __global__ void __launch_bounds__(256) analog_untranspose_kernel(const double* _
     }
 }
 
-// F == 1: per-cell sort of (x, index) ascending, lexicographic.  One workgroup per cell, keys and
-// 16-bit indices in LDS, truncated standard-form bitonic network (see sd_bcsd.hip).
-__global__ void __launch_bounds__(1024) analog_sort_kernel(const double* __restrict__ Xc, const double* __restrict__ yc,
-                                                           int64_t T, int64_t C, double* __restrict__ xs,
-                                                           int32_t* __restrict__ xi, double* __restrict__ yx) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* key = reinterpret_cast<double*>(smem_raw);
-    uint16_t* idx = reinterpret_cast<uint16_t*>(key + T);
-    const int n = (int)T;
-    int N = 1;
-    while (N < n) N <<= 1;
-    const int half = N >> 1;
-    for (int64_t c = blockIdx.x; c < C; c += gridDim.x) {
-        const double* x = Xc + c * T;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            key[i] = x[i];
-            idx[i] = (uint16_t)i;
-        }
-        __syncthreads();
-        for (int size = 2; size <= N; size <<= 1) {
-            const int hs = size >> 1;
-            for (int stride = hs, first = 1; stride >= 1; stride >>= 1, first = 0) {
-                for (int i = threadIdx.x; i < half; i += blockDim.x) {
-                    int lo, hi;
-                    if (first) {
-                        const int blk = i / hs, off = i - blk * hs;
-                        lo = blk * size + off;
-                        hi = blk * size + size - 1 - off;
-                    } else {
-                        const int blk = i / stride, off = i - blk * stride;
-                        lo = blk * 2 * stride + off;
-                        hi = lo + stride;
-                    }
-                    if (hi < n) {
-                        const double a = key[lo], b = key[hi];
-                        const uint16_t ia = idx[lo], ib = idx[hi];
-                        if (b < a || (b == a && ib < ia)) {
-                            key[lo] = b; key[hi] = a;
-                            idx[lo] = ib; idx[hi] = ia;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        const double* yy = yc + c * T;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            xs[c * T + i] = key[i];
-            xi[c * T + i] = idx[i];
-            if (yx) yx[c * T + i] = yy[idx[i]];
-        }
-        __syncthreads();
-    }
-}
-
-// F == 1, fast form of the same result: two workgroup-level merge sorts of plain float64 keys (sd_sortnet.h).
+// F == 1, the sorted view of a cell ((x, index) ascending, lexicographic): two workgroup-level merge sorts of plain float64 keys
+// (sd_sortnet.h).
 //   1. sort x                       -> xs
 //   2. every training sample finds lb = first position of its value in xs (binary search).  Without equal
 //      values in the cell lb is the sorted position: y and the index are scattered through LDS.  Otherwise the
@@ -119,7 +65,6 @@ __global__ void __launch_bounds__(1024) analog_sort_kernel(const double* __restr
 // keys_only: only xs and xi are produced (feature 0 of an F > 1 training set, or of a query series: x_stride is the
 // distance between the series of consecutive cells); non-finite keys sort as 0 (their cell / query is flagged elsewhere,
 // NaNs must not enter the min/max networks).
-constexpr long long kTagMask = 0x3fff;      // 14 bits: series of up to 16 384 samples
 constexpr unsigned kTagPadHi = 0x7fe00000u;  // upper word of the pad keys (>= 8.98e307: beyond any data the fast path accepts)
 
 // ---- fit, F == 1, tile-shaped first stage ------------------------------------------------------------------------------
@@ -522,7 +467,7 @@ __global__ void __launch_bounds__(1024) analog_sort2_kernel(const double* __rest
         for (int w = 0; w < 16; ++w) tot += red[w];
         const double ybar = tot / (double)n;
         if (tid == 0) ybar_all[c] = ybar;
-        if (pq_all == nullptr) continue;  // the prefix sums are built when a kernel first needs them (ensure_prefix_sums)
+        if (pq_all == nullptr) continue;  // the prefix sums are built when a kernel first needs them (build_prefix_sums)
         double a = 0.0, b = 0.0;
 #pragma unroll
         for (int i = 0; i < K; ++i) {
@@ -577,37 +522,37 @@ struct Sort2Args {
     const double* runs = nullptr;
     int np_runs = 0;
     const int32_t* odd_flags = nullptr;
+    bool tagged = false;  // the plan's choice: index-tag pass before the exact pass
+    bool count = false;   // development library: print how many cells took the exact pass
 };
 
 template <int K>
 int launch_sort2(sd_ctx* ctx, const Sort2Args& a) {
-    int np = (int)((a.T + K - 1) / K * K);
-    if (a.runs != nullptr && a.np_runs > np) np = a.np_runs;
-    const size_t lds = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
+    // index-tag pass first (tagged), then the cells it handed back
+    const AnalogLaunch Lt = analog_launches::sort2(K, a.T, a.C, a.runs != nullptr ? a.np_runs : 0, ctx->cu_count, a.tagged, false);
+    const AnalogLaunch Le = analog_launches::sort2(K, a.T, a.C, a.runs != nullptr ? a.np_runs : 0, ctx->cu_count, a.tagged, true);
+    const size_t lds = Le.lds;
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_sort2_kernel<K, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_sort2_kernel<K, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
-    const int nb = (int)std::min<int64_t>(a.C, (int64_t)ctx->cu_count * 4);
-    // index-tag pass first (series of up to 16 384 samples, no prefix sums asked for), then the cells it handed back
-    const bool tagged = a.T <= kTagMask + 1 && a.pq == nullptr && a.C < ((int64_t)1 << 31) && sd_dev_env("SD_ANALOG_NOTAGS") == nullptr;
     sd_scratch list;
     int32_t* worklist = nullptr;
     int32_t* work_count = nullptr;
-    if (tagged) {
+    if (a.tagged) {
         SD_HIP(list.alloc(ctx, sizeof(int32_t) * (size_t)(a.C + 1)));
         work_count = list.as<int32_t>();
         worklist = work_count + 1;
         SD_HIP(hipMemsetAsync(work_count, 0, sizeof(int32_t), ctx->stream));
-        SD_LAUNCH(ctx, "analog_sort2_kernel", (analog_sort2_kernel<K, true>), dim3(nb), dim3(1024), lds, a.X, a.x_stride, a.keys_only, a.y,
-                  a.T, a.C, a.xs, a.xi, a.yx, a.pq, a.ybar, worklist, work_count, tagged ? a.runs : nullptr, a.np_runs, a.odd_flags);
+        SD_LAUNCH(ctx, "analog_sort2_kernel", (analog_sort2_kernel<K, true>), dim3((unsigned)Lt.gx), dim3(Lt.block), lds, a.X, a.x_stride, a.keys_only, a.y,
+                  a.T, a.C, a.xs, a.xi, a.yx, a.pq, a.ybar, worklist, work_count, a.runs, a.np_runs, a.odd_flags);
     }
-    SD_LAUNCH(ctx, "analog_sort2_exact_kernel", (analog_sort2_kernel<K, false>), dim3(tagged ? std::min(nb, 256) : nb), dim3(1024), lds, a.X,
+    SD_LAUNCH(ctx, "analog_sort2_exact_kernel", (analog_sort2_kernel<K, false>), dim3((unsigned)Le.gx), dim3(Le.block), lds, a.X,
               a.x_stride, a.keys_only, a.y, a.T, a.C, a.xs, a.xi, a.yx, a.pq, a.ybar, worklist, work_count, (const double*)nullptr, 0,
               (const int32_t*)nullptr);
-    if (tagged) SD_HIP(hipStreamSynchronize(ctx->stream));  // the list goes back to the block cache
+    if (a.tagged) SD_HIP(hipStreamSynchronize(ctx->stream));  // the list goes back to the block cache
 #ifdef SD_DEV
-    if (tagged && sd_dev_env("SD_ANALOG_COUNT")) {
+    if (a.tagged && a.count) {
         int32_t h = 0;
         SD_HIP(hipMemcpy(&h, work_count, sizeof(h), hipMemcpyDeviceToHost));
         fprintf(stderr, "analog sort: %d of %lld cells took the exact kernel (presorted runs: %d)\n", h, (long long)a.C, a.runs != nullptr);
@@ -617,28 +562,15 @@ int launch_sort2(sd_ctx* ctx, const Sort2Args& a) {
 }
 
 // The tile-shaped first stage of the F == 1 fit (analog_tile_sort_kernel): writes the cell-major copies Xc / yc, the mask / finite
-// status bits and the sorted runs.  Instantiated for the widths of the 40-year daily series and its neighbours.
-bool tile_sort_applies(int K, int64_t T, int64_t C, size_t lds_max) {
-    if (K != 13 && K != 15 && K != 17) return false;
-    const int64_t chunk = 64 * K, nchunks = (T + chunk - 1) / chunk;
-    if (T > kTagMask + 1 || C >= ((int64_t)1 << 31) || nchunks > 16) return false;
-    if (sizeof(double) * (size_t)(nchunks * chunk + 1) + sizeof(int) * 1025 > lds_max) return false;
-    return sd_dev_env("SD_ANALOG_NOTILE") == nullptr && sd_dev_env("SD_ANALOG_NOTAGS") == nullptr;
-}
-
+// status bits and the sorted runs.
 template <int K>
 int launch_tile_sort_k(sd_ctx* ctx, const double* X, const double* y, int64_t ld, int64_t T, int64_t C, double* Xc, double* yc, double* runs,
                        int64_t runs_stride, int32_t* status, int32_t* odd_flags) {
-    constexpr int CHUNK = 64 * K;
-    constexpr int RS = CHUNK + 2 + ((4 - (CHUNK + 2) % 4) + 2) % 4;
-    const int nchunks = (int)((T + CHUNK - 1) / CHUNK);
-    const size_t lds = sizeof(double) * ((size_t)sdw::kW * RS + sdw::kHeadDoubles);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_tile_sort_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t ntiles = (C + sdw::kW - 1) / sdw::kW, tx = (ntiles + 7) / 8;
-    const int64_t nblocks = 8 * tx * nchunks;
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "analog fit: grid too large");
-    SD_LAUNCH(ctx, "analog_tile_sort_kernel", analog_tile_sort_kernel<K>, dim3((unsigned)nblocks), dim3(sdw::kThreads), lds, X, y, ld, T, C, nchunks,
-              Xc, yc, runs, runs_stride, status, odd_flags);
+    const AnalogLaunch L = analog_launches::tile_sort(K, T, C);
+    static_assert(tile_sort_rs(K) % 4 == 2, "row stride of analog_tile_sort_kernel (its RS)");
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_tile_sort_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, "analog_tile_sort_kernel", analog_tile_sort_kernel<K>, dim3((unsigned)L.gx), dim3(L.block), L.lds, X, y, ld, T, C,
+              (int)tile_sort_chunks(K, T), Xc, yc, runs, runs_stride, status, odd_flags);
     return SD_OK;
 }
 int launch_tile_sort(sd_ctx* ctx, int K, const double* X, const double* y, int64_t ld, int64_t T, int64_t C, double* Xc, double* yc, double* runs,
@@ -661,16 +593,6 @@ int launch_sort2_width(sd_ctx* ctx, int K, const Sort2Args& a) {
         case 19: return launch_sort2<19>(ctx, a);
     }
     return sd_set_error(SD_ERR_INVALID, "analog sort: width %d not instantiated", K);
-}
-
-// widths instantiated for the fast sort: T <= 1024 * K and the keys must fit the LDS
-int sort2_width(int64_t T, size_t lds_max) {
-    const int widths[] = {5, 9, 13, 15, 17, 19};
-    for (int K : widths) {
-        const int64_t np = (T + K - 1) / K * K;
-        if (T <= (int64_t)1024 * K && T <= 65535 && sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025 <= lds_max) return K;
-    }
-    return 0;
 }
 
 // F == 1: exclusive prefix sums of the centred analog values in sorted-x order, pq[c][i] = (sum_{j<i} d_j,

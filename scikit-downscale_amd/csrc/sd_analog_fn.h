@@ -4,8 +4,6 @@
 // ------------------------------------------------------------------------------------------------
 // general F predict: brute force, training rows staged through LDS, per-thread top-k in scratch
 // ------------------------------------------------------------------------------------------------
-constexpr int kBfThreads = 256;
-constexpr int kBfChunk = 1024;
 
 __global__ void __launch_bounds__(kBfThreads) analog_bf_predict_kernel(int mode, const double* __restrict__ Xq, int64_t ld,
                                                                       int64_t Tq, int64_t T, int F, int64_t C,
@@ -466,31 +464,24 @@ __global__ void __launch_bounds__(64) analog_slab_predict_kernel(int mode, const
     if (has_q) finish_query(mode, pa, F, T, c, tq, q, Xc + c * F * T, yc + c * T, sd, si, 64, ok);
 }
 
-// heap [k][64] of (double, IT) + the chunk staging area [F][64] doubles + [64] indices (16-byte aligned pieces)
-size_t bf2_lds_bytes(int k, int F, size_t it_bytes) {
-    const size_t heap = ((size_t)k * 64 * (sizeof(double) + it_bytes) + 15) / 16 * 16;
-    return heap + (size_t)F * 64 * sizeof(double) + 64 * sizeof(int32_t);
-}
-
 template <int F, typename IT>
 int launch_bf2i(sd_ctx* ctx, int mode, const sd_analog_state* st, const double* Xq, int64_t ld, int64_t Tq, int32_t* status_p,
-                const PredictArgs& pa) {
-    const size_t lds = bf2_lds_bytes(pa.k, F, sizeof(IT));
+                const PredictArgs& pa, const AnalogLaunch& L) {
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_bf2_predict_kernel<F, IT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t nbatch = (Tq + 63) / 64, nblocks = st->C * nbatch;
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "sd_analog_predict: too many (cell, query batch) pairs for one launch");
-    SD_LAUNCH(ctx, "analog_bf2_predict_kernel", (analog_bf2_predict_kernel<F, IT>), dim3((unsigned)nblocks), dim3(64), lds, mode,
-              Xq, ld, Tq, st->T, st->C, (int)nbatch, (const double*)st->X, (const double*)st->y, (const int32_t*)st->status,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    SD_LAUNCH(ctx, "analog_bf2_predict_kernel", (analog_bf2_predict_kernel<F, IT>), dim3((unsigned)L.gx), dim3(L.block), L.lds, mode,
+              Xq, ld, Tq, st->T, st->C, (int)((Tq + 63) / 64), (const double*)st->X, (const double*)st->y, (const int32_t*)st->status,
               status_p, pa);
     return SD_OK;
 }
 
+// (16-bit heap indices for T <= 65535: the plan's it_bytes)
 template <int F>
 int launch_bf2(sd_ctx* ctx, int mode, const sd_analog_state* st, const double* Xq, int64_t ld, int64_t Tq, int32_t* status_p,
-               const PredictArgs& pa) {
-    if (st->T <= 65535) return launch_bf2i<F, uint16_t>(ctx, mode, st, Xq, ld, Tq, status_p, pa);
-    return launch_bf2i<F, int32_t>(ctx, mode, st, Xq, ld, Tq, status_p, pa);
+               const PredictArgs& pa, const AnalogPlan& pl) {
+    const AnalogLaunch L = analog_launches::bf2(pl, st->C, Tq);
+    if (pl.it_bytes == 2) return launch_bf2i<F, uint16_t>(ctx, mode, st, Xq, ld, Tq, status_p, pa, L);
+    return launch_bf2i<F, int32_t>(ctx, mode, st, Xq, ld, Tq, status_p, pa, L);
 }
 
 // Query order for the slab search.  A wave stops scanning when the axis distance exceeds the *largest* k-th distance of
@@ -578,20 +569,18 @@ __global__ void __launch_bounds__(256) analog_slab_key_kernel(const double* __re
 // worklist (device, nwork entries): only the listed (cell, query batch) pairs (the hand-backs of analog_slab_topk_kernel)
 template <int F>
 int launch_slab(sd_ctx* ctx, int mode, const sd_analog_state* st, const double* qc, const int32_t* qi, int64_t cb, int64_t cc,
-                int64_t Tq, int32_t* status_p, const PredictArgs& pa, const int32_t* worklist = nullptr, int64_t nwork = 0) {
-    const size_t lds = bf2_lds_bytes(pa.k, F, sizeof(uint16_t));
+                int64_t Tq, int32_t* status_p, const PredictArgs& pa, int ablate, const int32_t* worklist = nullptr, int64_t nwork = 0) {
+    const AnalogLaunch L = analog_launches::slab_heap(pa.k, F, cc, Tq, worklist != nullptr ? nwork : 0);
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_slab_predict_kernel<F>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t nbatch = (Tq + 63) / 64, nblocks = worklist != nullptr ? nwork : cc * nbatch;
-    const char* eab = sd_dev_env("SD_ANALOG_ABLATE");  // timing experiments only (results are wrong): 1 no insertions, 2 no epilogue
-    const int ablate = eab ? atoi(eab) : 0;
-    sd_scratch dbg;  // 4: count scanned chunks and insertion rounds, printed per launch
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    const int64_t nblocks = L.gx;
+    sd_scratch dbg;  // ablate & 4: count scanned chunks and insertion rounds, printed per launch
     if (ablate & 4) {
         SD_HIP(dbg.alloc(ctx, 16));
         SD_HIP(hipMemsetAsync(dbg.p, 0, 16, ctx->stream));
     }
-    SD_LAUNCH(ctx, "analog_slab_predict_kernel", (analog_slab_predict_kernel<F>), dim3((unsigned)nblocks), dim3(64), lds, mode, qc,
-              qi, cb, Tq, st->T, (int)nbatch, (const double*)st->X, (const double*)st->y, (const double*)st->ps,
+    SD_LAUNCH(ctx, "analog_slab_predict_kernel", (analog_slab_predict_kernel<F>), dim3((unsigned)nblocks), dim3(L.block), L.lds, mode, qc,
+              qi, cb, Tq, st->T, (int)((Tq + 63) / 64), (const double*)st->X, (const double*)st->y, (const double*)st->ps,
               (const int32_t*)st->xi, (const int32_t*)st->status, status_p, pa, ablate, dbg.as<unsigned long long>(), worklist);
     if (ablate & 4) {
         unsigned long long h[2];

@@ -26,14 +26,9 @@
 // time-ordered path (tests/test_gpu_analog.py).
 #pragma once
 
-constexpr int kRunK = 16;               // keys per lane of the run sort
-constexpr int kRun = 64 * kRunK;        // queries per run: 1 024 consecutive time steps
-constexpr int kRunRS = kRun + 2;        // LDS row stride in doubles (RS % 4 == 2: rows land 8 or 24 banks apart, like sd_bcsd_rs_row_stride)
-constexpr int kRunRSQ = kRun + 32 + 2;  // the same for rows that hold sorted position p at slot p + p / 32 (see analog_query_runs_kernel)
+// (kRunK, kRun, kRunRS, kRunRSQ and the LDS sizes: sd_analog_plan.h)
 __device__ __forceinline__ int run_slot(int p) { return p + (p >> 5); }
 constexpr unsigned kRunQD = (1u << 21) - 2048u;
-
-inline size_t query_runs_lds_bytes() { return sizeof(double) * ((size_t)sdw::kW * kRunRSQ + sdw::kHeadDoubles); }
 
 __global__ void __launch_bounds__(sdw::kThreads, 4) analog_query_runs_kernel(const double* __restrict__ Xq, int64_t ld, int64_t Tq, int64_t C,
                                                                              int nruns, double* __restrict__ qs /* [C][Tq] */,
@@ -221,27 +216,3 @@ __global__ void __launch_bounds__(sdw::kThreads, 4) analog_untranspose_runs_kern
     }
 }
 
-// the two launches; the staging arrays of a cell chunk start at cell 0 of the chunk
-inline int launch_query_runs(sd_ctx* ctx, const double* Xq, int64_t ld, int64_t Tq, int64_t C, double* qs, unsigned short* qt, int32_t* status) {
-    const int nruns = (int)((Tq + kRun - 1) / kRun);
-    const size_t lds = query_runs_lds_bytes();
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_query_runs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t ntiles = (C + sdw::kW - 1) / sdw::kW, tx = (ntiles + 7) / 8;
-    const int64_t nblocks = 8 * tx * nruns;
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "analog predict: grid too large");
-    SD_LAUNCH(ctx, "analog_query_runs_kernel", analog_query_runs_kernel, dim3((unsigned)nblocks), dim3(sdw::kThreads), lds, Xq, ld, Tq, C, nruns, qs, qt, status);
-    return SD_OK;
-}
-inline int launch_untranspose_runs(sd_ctx* ctx, const double* oc, const unsigned short* qt, int64_t Tq, int64_t C, double* out, int64_t ld, int skip_prob) {
-    const int nruns = (int)((Tq + kRun - 1) / kRun);
-    const size_t lds = sizeof(double) * ((size_t)sdw::kW * kRunRS + sdw::kHeadDoubles);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_untranspose_runs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t ntiles = (C + sdw::kW - 1) / sdw::kW, tx = (ntiles + 7) / 8;
-    const int64_t nblocks = 8 * tx * nruns;
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "analog predict: grid too large");
-    SD_LAUNCH(ctx, "analog_untranspose_runs_kernel", analog_untranspose_runs_kernel, dim3((unsigned)nblocks, skip_prob ? 2u : 3u), dim3(sdw::kThreads), lds, oc, qt,
-              Tq, C, nruns, out, ld, skip_prob);
-    return SD_OK;
-}
-// value-ordered runs pay from a few runs on (the window kernel's value-range passes and every per-cell kernel take them)
-inline bool query_runs_apply(int64_t Tq) { return Tq >= 2 * kRun && sd_dev_env("SD_ANALOG_NORUNS") == nullptr; }

@@ -24,9 +24,7 @@
 // chunk_mask), the pairs are put in exact (rdist, index) order by an insertion sort over the almost sorted list in LDS, and the
 // first k go to the epilogue of the heap kernel (finish_query): same neighbours, same order, same statistics, bit for bit.
 
-constexpr int kTopKeep = 32, kTopNew = 32;
-constexpr int kTopMaxF = 6;                   // (7 and 8 features do not fit 256 registers with the matrix-core tiles: the heap kernel)
-constexpr int kTopMaxK = 30;                  // two spare kept slots tell "every tie of the k-th bucket is here" from "maybe not"
+// (kTopKeep, kTopNew, kTopMaxF, kTopMaxK and topk_lds_bytes: sd_analog_plan.h)
 constexpr unsigned kTopEmpty = 0xffffffc0u;   // keys of empty slots: above the high word of every finite double
 
 __device__ __forceinline__ void topk_prune(unsigned (&kept)[kTopKeep], const unsigned* __restrict__ nk, uint16_t* __restrict__ bi,
@@ -644,39 +642,29 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) an
     }
 }
 
-size_t topk_lds_bytes(int F) {
-    const size_t scan = sizeof(unsigned) * kTopNew * 64 + sizeof(uint16_t) * (kTopKeep + kTopNew) * 64 + sizeof(double) * (size_t)F * 64;
-    const size_t fin = (sizeof(double) + sizeof(uint16_t)) * (size_t)kTopKeep * 64;
-    return scan > fin ? scan : fin;
-}
-
 // the fast kernel over the chunk's cells, then the heap kernel over what it handed back
 template <int F>
-int launch_slab_topk(sd_ctx* ctx, int mode, const sd_analog_state* st, const double* qc, const int32_t* qi, int64_t cb, int64_t cc,
-                     int64_t Tq, int32_t* status_p, const PredictArgs& pa, int32_t* worklist /* [cc * nbatch + 1] */,
-                     double* cen /* [cc][F] */, double* pmax /* [cc] */) {
-    const size_t lds = topk_lds_bytes(F);
+int launch_slab_topk(sd_ctx* ctx, int mode, const sd_analog_state* st, const AnalogCall& call, const AnalogPlan& pl, const double* qc,
+                     const int32_t* qi, int64_t cb, int64_t cc, int32_t* status_p, const PredictArgs& pa,
+                     int32_t* worklist /* [cc * nbatch + 1] */, double* cen /* [cc][F] */, double* pmax /* [cc] */) {
+    const int64_t Tq = call.Tq;
+    const AnalogLaunch Lc = analog_launches::slab_aux(cc, ctx->cu_count), L = analog_launches::slab_topk(pl, cc, Tq);
     SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_slab_topk_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-    const int64_t nbatch = (Tq + 63) / 64, nblocks = cc * nbatch;
-    const char* epa = sd_dev_env("SD_TOPK_PRUNE_AT");
-    int prune_at = epa ? atoi(epa) : 16;
-    prune_at = prune_at < 1 ? 1 : (prune_at > kTopNew ? kTopNew : prune_at);
-    const char* eab = sd_dev_env("SD_ANALOG_ABLATE");  // 4: count chunks, append rounds, prunes
-    const bool count = eab && (atoi(eab) & 4);
+                               (int)L.lds));
+    const int64_t nbatch = (Tq + 63) / 64, nblocks = L.gx;
+    const bool count = (pl.ablate & 4) != 0;  // count chunks, append rounds, prunes
     sd_scratch dbg;
     if (count) {
         SD_HIP(dbg.alloc(ctx, 128));
         SD_HIP(hipMemsetAsync(dbg.p, 0, 128, ctx->stream));
     }
-    SD_LAUNCH(ctx, "analog_slab_center_kernel", analog_slab_center_kernel, dim3((unsigned)std::min<int64_t>(cc, (int64_t)ctx->cu_count * 8)),
-              dim3(256), 0, (const double*)st->ps + cb * F * st->T, st->T, F, cc, cen, pmax);
-    const int use_mfma = sd_dev_env("SD_TOPK_READLANE") == nullptr ? 1 : 0;  // (A/B: the v_readlane form of the pre-filter)
+    SD_LAUNCH(ctx, "analog_slab_center_kernel", analog_slab_center_kernel, dim3((unsigned)Lc.gx), dim3(Lc.block), 0,
+              (const double*)st->ps + cb * F * st->T, st->T, F, cc, cen, pmax);
     int32_t* nwork = worklist + nblocks;
     SD_HIP(hipMemsetAsync(nwork, 0, sizeof(int32_t), ctx->stream));
-    SD_LAUNCH(ctx, "analog_slab_topk_kernel", (analog_slab_topk_kernel<F>), dim3((unsigned)nblocks), dim3(64), lds, mode, qc, qi, cb,
+    SD_LAUNCH(ctx, "analog_slab_topk_kernel", (analog_slab_topk_kernel<F>), dim3((unsigned)nblocks), dim3(L.block), L.lds, mode, qc, qi, cb,
               Tq, st->T, (int)nbatch, (const double*)st->X, (const double*)st->y, (const double*)st->ps, (const int32_t*)st->xi,
-              (const int32_t*)st->status, status_p, pa, prune_at, (const double*)cen, (const double*)pmax, use_mfma, worklist, nwork,
+              (const int32_t*)st->status, status_p, pa, pl.prune_at, (const double*)cen, (const double*)pmax, pl.use_mfma, worklist, nwork,
               count ? dbg.as<unsigned long long>() : nullptr);
     int32_t nw = 0;
     SD_HIP(hipMemcpyAsync(&nw, nwork, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -690,78 +678,69 @@ int launch_slab_topk(sd_ctx* ctx, int mode, const sd_analog_state* st, const dou
                 (double)h[4] / (double)nblocks, (double)h[5] / (double)nblocks, (double)h[6] / (double)nblocks,
                 (double)h[7] / (double)nblocks, (double)h[8] / (double)nblocks);
     }
-    if (nw > 0) SD_TRY((launch_slab<F>(ctx, mode, st, qc, qi, cb, cc, Tq, status_p, pa, worklist, nw)));
+    if (nw > 0) SD_TRY((launch_slab<F>(ctx, mode, st, qc, qi, cb, cc, Tq, status_p, pa, pl.ablate, worklist, nw)));
     return SD_OK;
 }
 
-// F > 1 with the feature-0 sorted copy: queries go cell-major, are sorted by feature 0 per cell, and every wave scans
-// only the slab of training points its 64 neighbouring queries can reach (analog_slab_predict_kernel)
-int predict_slab(sd_ctx* ctx, int mode, const sd_analog_state* st, const double* Xq, int64_t ld, int64_t Tq, int32_t* status_p,
-                 const PredictArgs& pa) {
+// F > 1 with the feature-0 sorted copy (AnalogPath::Slab): queries go cell-major, are sorted by feature 0 inside the classes of
+// analog_slab_s2_kernel per cell, and every wave scans only the slab of training points its 64 neighbouring queries can reach
+int predict_slab(sd_ctx* ctx, int mode, const sd_analog_state* st, const AnalogCall& call, const AnalogPlan& pl, const double* Xq, int64_t ld,
+                 int32_t* status_p, const PredictArgs& pa, bool count) {
     const int F = st->F;
-    const int64_t C = st->C, nbatch = (Tq + 63) / 64;
-    int64_t chunk = 4096;
-    while (chunk > 1 && chunk * nbatch >= ((int64_t)1 << 31)) chunk >>= 1;
+    const int64_t C = st->C, Tq = call.Tq, nbatch = (Tq + 63) / 64, chunk = pl.chunk;
     const int64_t cc_max = C < chunk ? C : chunk;
-    const int Kq = sort2_width(Tq, ctx->lds_max);
-    // classes of the query order (analog_slab_s2_kernel); a short series would only get waves that straddle classes
-    const char* ecl = sd_dev_env("SD_ANALOG_SLAB_CLASSES");
-    int nclass = ecl ? atoi(ecl) : (int)std::min<int64_t>(8, Tq / 512);
-    nclass = nclass < 1 ? 1 : (nclass > 8 ? 8 : nclass);
-    // k <= 30: candidate lists pruned by a register sorting network (analog_slab_topk_kernel); the heap kernel takes larger k
-    // and the batches the fast kernel hands back
-    const bool topk = pa.k <= kTopMaxK && F <= kTopMaxF && sd_dev_env("SD_ANALOG_HEAP") == nullptr;
     sd_scratch qc, qs, qi, key, wl;
     sd_scratch pmax, cen;
-    if (topk) {
+    if (pl.topk) {
         SD_HIP(wl.alloc(ctx, sizeof(int32_t) * (size_t)(cc_max * nbatch + 1)));
         SD_HIP(pmax.alloc(ctx, sizeof(double) * (size_t)cc_max));
         SD_HIP(cen.alloc(ctx, sizeof(double) * (size_t)cc_max * F));
     }
-    if (nclass > 1) SD_HIP(key.alloc(ctx, sizeof(double) * (size_t)Tq * cc_max));
+    if (pl.nclass > 1) SD_HIP(key.alloc(ctx, sizeof(double) * (size_t)Tq * cc_max));
     SD_HIP(qc.alloc(ctx, sizeof(double) * (size_t)Tq * F * cc_max));
     SD_HIP(qs.alloc(ctx, sizeof(double) * (size_t)Tq * cc_max));
     SD_HIP(qi.alloc(ctx, sizeof(int32_t) * (size_t)Tq * cc_max));
     for (int64_t cb = 0; cb < C; cb += chunk) {
         const int64_t cc = C - cb < chunk ? C - cb : chunk;
-        dim3 tgrid((unsigned)((cc + 31) / 32), (unsigned)((Tq + 31) / 32));
+        const AnalogLaunch Lt = analog_launches::transpose(cc, Tq), La = analog_launches::slab_aux(cc, ctx->cu_count);
         for (int f = 0; f < F; ++f)
-            SD_LAUNCH(ctx, "analog_transpose_kernel", analog_transpose_kernel, tgrid, dim3(256), 0, Xq + cb, ld, Tq, F, f, cc,
-                      qc.as<double>(), status_p + cb, 0);
-        const int nbk = (int)std::min<int64_t>(cc, (int64_t)ctx->cu_count * 8);
+            SD_LAUNCH(ctx, "analog_transpose_kernel", analog_transpose_kernel, dim3((unsigned)Lt.gx, (unsigned)Lt.gy), dim3(Lt.block), 0, Xq + cb, ld,
+                      Tq, F, f, cc, qc.as<double>(), status_p + cb, 0);
         Sort2Args a{qc.as<double>(), (int64_t)F * Tq, 1, nullptr, Tq, cc, qs.as<double>(), qi.as<int32_t>(),
                     nullptr, nullptr, nullptr};
-        if (nclass > 1) {
-            SD_LAUNCH(ctx, "analog_slab_s2_kernel", analog_slab_s2_kernel, dim3(nbk), dim3(256), 0, (const double*)qc.p, Tq, F, cc,
+        a.tagged = pl.tagged;
+        a.count = count;
+        if (pl.nclass > 1) {
+            SD_LAUNCH(ctx, "analog_slab_s2_kernel", analog_slab_s2_kernel, dim3((unsigned)La.gx), dim3(La.block), 0, (const double*)qc.p, Tq, F, cc,
                       key.as<double>());
             a.X = key.as<double>();
             a.x_stride = Tq;
-            SD_TRY(launch_sort2_width(ctx, Kq, a));  // qs = sorted s2 (class thresholds)
-            SD_LAUNCH(ctx, "analog_slab_key_kernel", analog_slab_key_kernel, dim3(nbk), dim3(256), 0, (const double*)qc.p,
-                      (const double*)qs.p, Tq, F, cc, nclass, key.as<double>());
+            SD_TRY(launch_sort2_width(ctx, pl.Kq, a));  // qs = sorted s2 (class thresholds)
+            SD_LAUNCH(ctx, "analog_slab_key_kernel", analog_slab_key_kernel, dim3((unsigned)La.gx), dim3(La.block), 0, (const double*)qc.p,
+                      (const double*)qs.p, Tq, F, cc, pl.nclass, key.as<double>());
         }
-        SD_TRY(launch_sort2_width(ctx, Kq, a));  // qi = query order
+        SD_TRY(launch_sort2_width(ctx, pl.Kq, a));  // qi = query order
         const double* q = qc.as<double>();
         const int32_t* qix = qi.as<int32_t>();
-        if (topk) {
+        if (pl.topk) {
             int32_t* w = wl.as<int32_t>();
             switch (F) {
-                case 2: SD_TRY(launch_slab_topk<2>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
-                case 3: SD_TRY(launch_slab_topk<3>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
-                case 4: SD_TRY(launch_slab_topk<4>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
-                case 5: SD_TRY(launch_slab_topk<5>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
-                default: SD_TRY(launch_slab_topk<6>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
+                case 2: SD_TRY(launch_slab_topk<2>(ctx, mode, st, call, pl, q, qix, cb, cc, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
+                case 3: SD_TRY(launch_slab_topk<3>(ctx, mode, st, call, pl, q, qix, cb, cc, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
+                case 4: SD_TRY(launch_slab_topk<4>(ctx, mode, st, call, pl, q, qix, cb, cc, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
+                case 5: SD_TRY(launch_slab_topk<5>(ctx, mode, st, call, pl, q, qix, cb, cc, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
+                default: SD_TRY(launch_slab_topk<6>(ctx, mode, st, call, pl, q, qix, cb, cc, status_p, pa, w, cen.as<double>(), pmax.as<double>())); break;
             }
             continue;
         }
         switch (F) {
-            case 2: SD_TRY(launch_slab<2>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            case 3: SD_TRY(launch_slab<3>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            case 4: SD_TRY(launch_slab<4>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            case 5: SD_TRY(launch_slab<5>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            case 6: SD_TRY(launch_slab<6>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            case 7: SD_TRY(launch_slab<7>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
-            default: SD_TRY(launch_slab<8>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa)); break;
+            case 2: SD_TRY(launch_slab<2>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            case 3: SD_TRY(launch_slab<3>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            case 4: SD_TRY(launch_slab<4>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            case 5: SD_TRY(launch_slab<5>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            case 6: SD_TRY(launch_slab<6>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            case 7: SD_TRY(launch_slab<7>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
+            default: SD_TRY(launch_slab<8>(ctx, mode, st, q, qix, cb, cc, Tq, status_p, pa, pl.ablate)); break;
         }
     }
     SD_HIP(hipStreamSynchronize(ctx->stream));  // the staging buffers go back to the block cache at scope exit

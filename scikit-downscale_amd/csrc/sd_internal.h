@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <unordered_map>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../../include/sd_downscale.h"
+#include "sd_analog_plan.h"
 #include "sd_bcsd_plan.h"
 
 // Internal per-cell status is a bitmask (atomicOr from many workgroups, order independent); it is
@@ -38,6 +40,31 @@ static inline BcsdDevSwitches sd_bcsd_dev_switches() {
     d.no_dma = on("SD_FX_NODMA", "");
     d.no_full = on("SD_FX_NOFULL", "");
     d.no_compact = on("SD_FX_NOCOMPACT", "");
+    return d;
+}
+// the switches and diagnostics of the analog launch plan (sd_analog_plan.h): the only place the analog code reads the environment
+static inline AnalogDevSwitches sd_analog_dev_switches() {
+    const auto on = [](const char* name) { return sd_dev_env(name) != nullptr; };
+    const auto num = [](const char* name, int unset) {
+        const char* e = sd_dev_env(name);
+        return e != nullptr ? atoi(e) : unset;
+    };
+    AnalogDevSwitches d;
+    d.no_slab = on("SD_ANALOG_NOSLAB");
+    d.heap = on("SD_ANALOG_HEAP");
+    d.no_tile = on("SD_ANALOG_NOTILE");
+    d.reg_prefix = on("SD_ANALOG_REG_PREFIX");
+    d.no_runs = on("SD_ANALOG_NORUNS");
+    d.runs_always = on("SD_ANALOG_RUNS_ALWAYS");
+    const int classes = num("SD_ANALOG_SLAB_CLASSES", -1);
+    d.slab_classes = classes < 0 && on("SD_ANALOG_SLAB_CLASSES") ? 0 : classes;
+    d.ablate = num("SD_ANALOG_ABLATE", 0);
+    const int prune = num("SD_TOPK_PRUNE_AT", -1);
+    d.prune_at = prune < 0 && on("SD_TOPK_PRUNE_AT") ? 0 : prune;
+    d.readlane = on("SD_TOPK_READLANE");
+    d.m3_trace = on("SD_M3_TRACE");
+    d.fused_trace = on("SD_FUSED_TRACE");
+    d.count = on("SD_ANALOG_COUNT");
     return d;
 }
 
