@@ -68,7 +68,7 @@ inline int sort2_width(int64_t T, size_t lds_max) {
     const int widths[] = {5, 9, 13, 15, 17, 19};
     for (int K : widths) {
         const int64_t np = (T + K - 1) / K * K;
-        if (T <= (int64_t)1024 * K && T <= 65535 && sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025 <= lds_max) return K;
+        if (T <= (int64_t)1024 * K && T <= 65535 && sdw::block_sort_lds_bytes((int)np) <= lds_max) return K;
     }
     return 0;
 }
@@ -77,13 +77,15 @@ inline int sort2_np(int K, int64_t T, int np_runs) {
     const int np = (int)((T + K - 1) / K * K);
     return np_runs > np ? np_runs : np;
 }
-inline size_t sort2_lds_bytes(int np) { return sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025; }
+inline size_t sort2_lds_bytes(int np) { return sdw::block_sort_lds_bytes(np); }
 
-// analog_tile_sort_kernel<K>: runs of 64 * K keys, row stride, LDS, slots of presorted runs per cell
-constexpr int tile_sort_rs(int K) { return 64 * K + 2 + ((4 - (64 * K + 2) % 4) + 2) % 4; }
-inline size_t tile_sort_lds_bytes(int K) { return sizeof(double) * ((size_t)sdw::kW * tile_sort_rs(K) + sdw::kHeadDoubles); }
-inline int64_t tile_sort_chunks(int K, int64_t T) { return (T + 64 * K - 1) / (64 * (int64_t)K); }
-inline int tile_sort_np(int K, int64_t T) { return (int)(tile_sort_chunks(K, T) * 64 * K); }
+// analog_tile_sort_kernel<K>: row stride, LDS, slots of presorted runs per cell; workgroups of the kernels tiled like the BCSD
+// ones (shared with the quantile-mapping fit: sd_wave_consts.h)
+using sdw::tile_sort_rs;
+using sdw::tile_sort_lds_bytes;
+using sdw::tile_sort_chunks;
+using sdw::tile_sort_np;
+using sdw::tiled_blocks;
 // The tile-shaped first stage of the F == 1 fit: instantiated for the widths of the 40-year daily series and its neighbours.
 inline bool tile_sort_applies(int K, int64_t T, int64_t C, size_t lds_max, bool no_tile) {
     if (K != 13 && K != 15 && K != 17) return false;
@@ -92,12 +94,6 @@ inline bool tile_sort_applies(int K, int64_t T, int64_t C, size_t lds_max, bool 
     if (sort2_lds_bytes(tile_sort_np(K, T)) > lds_max) return false;
     return !no_tile;
 }
-// workgroups of the kernels tiled like the BCSD ones: 8 per 8 tiles of 8 cells and row block
-inline int64_t tiled_blocks(int64_t C, int64_t rows) {
-    const int64_t ntiles = (C + sdw::kW - 1) / sdw::kW, tx = (ntiles + 7) / 8;
-    return 8 * tx * rows;
-}
-
 inline size_t query_runs_lds_bytes() { return sizeof(double) * ((size_t)sdw::kW * kRunRSQ + sdw::kHeadDoubles); }
 inline size_t untranspose_runs_lds_bytes() { return sizeof(double) * ((size_t)sdw::kW * kRunRS + sdw::kHeadDoubles); }
 

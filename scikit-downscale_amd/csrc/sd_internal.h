@@ -16,6 +16,7 @@
 #include "../../include/sd_downscale.h"
 #include "sd_analog_plan.h"
 #include "sd_bcsd_plan.h"
+#include "sd_qm_plan.h"
 
 // Internal per-cell status is a bitmask (atomicOr from many workgroups, order independent); it is
 // folded into the public SD_CELL_* code with the reference's precedence on the way out.
@@ -65,6 +66,15 @@ static inline AnalogDevSwitches sd_analog_dev_switches() {
     d.m3_trace = on("SD_M3_TRACE");
     d.fused_trace = on("SD_FUSED_TRACE");
     d.count = on("SD_ANALOG_COUNT");
+    return d;
+}
+// the switches of the quantile-mapping launch plan (sd_qm_plan.h): the only place the quantile-mapping code reads the environment
+static inline QmDevSwitches sd_qm_dev_switches() {
+    const auto on = [](const char* name) { return sd_dev_env(name) != nullptr; };
+    QmDevSwitches d;
+    d.no_tile = on("SD_QM_NOTILE");
+    d.divide = on("SD_QM_DIVIDE");
+    d.trace = on("SD_QM_TRACE");
     return d;
 }
 

@@ -15,8 +15,10 @@
 // expression (the 1e20 cancels: ~1e4 of absolute rounding noise in the position, ~1e5 in the result -- in the
 // reference's outputs as well).
 // np.interp arithmetic is spelled out: last xp <= x, exact hit -> fp[j], slope * (x - xp[j]) + fp[j] otherwise.
-#include <algorithm>
 #include <cstdlib>
+#include <iterator>
+#include <type_traits>
+#include <utility>
 
 #include "sd_internal.h"
 #include "sd_sortnet.h"
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(sdw::kThreads, 4) qm_tile_runs_kernel(const do
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int CHUNK = kWave * K;
     constexpr int NR = (CHUNK + kRowsPerPass - 1) / kRowsPerPass;
-    constexpr int RS = CHUNK + 2 + ((4 - (CHUNK + 2) % 4) + 2) % 4;  // row stride: >= CHUNK + 1 slots, RS % 4 == 2
+    constexpr int RS = tile_sort_rs(K);  // row stride: >= CHUNK + 1 slots, RS % 4 == 2
     double* const tile = reinterpret_cast<double*>(smem_raw) + kHeadDoubles;
     const int64_t ntiles = (C + kW - 1) / kW;
     int64_t tile_id;
@@ -736,89 +738,131 @@ __global__ void __launch_bounds__(256) qm_status_public_kernel(const int32_t* __
     }
 }
 
-int sort_width(int64_t T, size_t lds_max) {
-    const int widths[] = {1, 3, 5, 9, 13, 15, 17, 19};
-    for (int K : widths) {
-        const int64_t np = (T + K - 1) / K * K;
-        if (T <= (int64_t)1024 * K && sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025 <= lds_max) return K;
-    }
-    return 0;
-}
+// ---- launchers: the plan's widths -> instantiations; every grid, block and LDS size from qm_launches (sd_qm_plan.h) ------------------
+namespace ql = qm_launches;
 
-template <int K>
-int launch_sort(sd_ctx* ctx, double* data, int64_t T, int64_t C) {
-    const int np = (int)((T + K - 1) / K * K);
-    const size_t lds = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_sort_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nb = (int)std::min<int64_t>(C, (int64_t)ctx->cu_count * 4);
-    SD_LAUNCH(ctx, "qm_sort_kernel", qm_sort_kernel<K>, dim3(nb), dim3(1024), lds, data, T, C);
+dim3 grid_of(const QmLaunch& L) { return dim3((unsigned)L.gx, (unsigned)L.gy); }
+
+template <class Kernel>
+int allow_lds(Kernel kernel, const QmLaunch& L) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
     return SD_OK;
 }
 
-template <int K>
-int launch_rank(sd_ctx* ctx, const double* data, int64_t T, int64_t C, int32_t* rank) {
-    const int np = (int)((T + K - 1) / K * K);
-    const size_t lds = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_rank_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nb = (int)std::min<int64_t>(C, (int64_t)ctx->cu_count * 4);
-    SD_LAUNCH(ctx, "qm_rank_kernel", qm_rank_kernel<K>, dim3(nb), dim3(1024), lds, data, T, C, rank);
+// f(std::integral_constant<int, K>) for the K of the list of instantiated widths (sdqm::kSortWidths / kTileWidths); any other K is an error
+template <const auto& Widths, class F, size_t... I>
+int dispatch_width(int K, F& f, std::index_sequence<I...>) {
+    int rc = SD_OK;
+    const bool found = ((K == Widths[I] && ((rc = f(std::integral_constant<int, Widths[I]>{})), true)) || ...);
+    return found ? rc : sd_set_error(SD_ERR_INVALID, "sd_qm: width %d not instantiated", K);
+}
+template <const auto& Widths, class F>
+int dispatch_width(int K, F f) {
+    return dispatch_width<Widths>(K, f, std::make_index_sequence<std::size(Widths)>{});
+}
+
+int launch_transpose(sd_ctx* ctx, const double* src, int64_t ld, int64_t T, int64_t C, double* dst, int32_t* status, int set_mask) {
+    const QmLaunch L = ql::transpose(C, T);
+    SD_LAUNCH(ctx, "qm_transpose_kernel", qm_transpose_kernel, grid_of(L), dim3(L.block), L.lds, src, ld, T, C, dst, status, set_mask);
     return SD_OK;
 }
 
-
-// widths of the tile-shaped fit stage: at most 16 runs of 64 * K samples, merged by a 1 024-thread workgroup
-int tile_runs_width(int64_t T, size_t lds_max) {
-    if (sd_dev_env("SD_QM_NOTILE") != nullptr) return 0;
-    const int widths[] = {13, 15, 17};
-    for (int K : widths) {
-        const int64_t chunk = 64 * K, nchunks = (T + chunk - 1) / chunk;
-        if (nchunks <= 16 && sizeof(double) * (size_t)(nchunks * chunk + 1) + sizeof(int) * 1025 <= lds_max) return K;
-    }
-    return 0;
+int launch_sort(sd_ctx* ctx, int K, double* data, int64_t T, int64_t C) {
+    return dispatch_width<sdqm::kSortWidths>(K, [&](auto k) -> int {
+        const QmLaunch L = ql::sort(k, T, C, ctx->cu_count);
+        SD_TRY(allow_lds(&qm_sort_kernel<k>, L));
+        SD_LAUNCH(ctx, "qm_sort_kernel", qm_sort_kernel<k>, grid_of(L), dim3(L.block), L.lds, data, T, C);
+        return SD_OK;
+    });
 }
 
-// np.sort of every cell's series of one time-major field -> xs [C][T] (plus mask / finite bookkeeping)
-template <int K>
-int launch_tile_sort(sd_ctx* ctx, const double* X_dev, int64_t ld, int64_t T, int64_t C, double* xs, int32_t* status, int set_mask,
-                     double* runs) {
-    constexpr int CHUNK = 64 * K;
-    constexpr int RS = CHUNK + 2 + ((4 - (CHUNK + 2) % 4) + 2) % 4;
-    const int nchunks = (int)((T + CHUNK - 1) / CHUNK);
-    const int np = nchunks * CHUNK;
-    const size_t lds_t = sizeof(double) * ((size_t)sdw::kW * RS + sdw::kHeadDoubles);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_tile_runs_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-    const int64_t ntiles = (C + sdw::kW - 1) / sdw::kW, tx = (ntiles + 7) / 8;
-    const int64_t nblocks = 8 * tx * nchunks;
-    SD_CHECK_ARG(nblocks < ((int64_t)1 << 31), "sd_qm_fit: grid too large");
-    SD_LAUNCH(ctx, "qm_tile_runs_kernel", qm_tile_runs_kernel<K>, dim3((unsigned)nblocks), dim3(sdw::kThreads), lds_t, X_dev, ld, T, C, nchunks,
-              runs, (int64_t)np, status, set_mask);
-    const size_t lds_m = sizeof(double) * (size_t)(np + 1) + sizeof(int) * 1025;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_merge_runs_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
-    const int nb = (int)std::min<int64_t>(C, (int64_t)ctx->cu_count * 4);
-    SD_LAUNCH(ctx, "qm_merge_runs_kernel", qm_merge_runs_kernel<K>, dim3(nb), dim3(1024), lds_m, (const double*)runs, np, T, C, xs);
+int launch_rank(sd_ctx* ctx, int K, const double* data, int64_t T, int64_t C, int32_t* rank) {
+    return dispatch_width<sdqm::kSortWidths>(K, [&](auto k) -> int {
+        const QmLaunch L = ql::rank(k, T, C, ctx->cu_count);
+        SD_TRY(allow_lds(&qm_rank_kernel<k>, L));
+        SD_LAUNCH(ctx, "qm_rank_kernel", qm_rank_kernel<k>, grid_of(L), dim3(L.block), L.lds, data, T, C, rank);
+        return SD_OK;
+    });
+}
+
+// np.sort of every cell's series of one time-major field -> xs [C][T] (plus mask / finite bookkeeping): sorted runs of 64 * Kt
+// samples straight from the field, then the merge rounds
+int launch_tile_sort(sd_ctx* ctx, const QmPlan& pl, const double* X_dev, int64_t ld, int64_t T, int64_t C, double* xs, int32_t* status,
+                     int set_mask, double* runs) {
+    return dispatch_width<sdqm::kTileWidths>(pl.Kt, [&](auto k) -> int {
+        const QmLaunch Lr = ql::tile_runs(pl, C), Lm = ql::merge_runs(pl, C, ctx->cu_count);
+        SD_TRY(allow_lds(&qm_tile_runs_kernel<k>, Lr));
+        SD_LAUNCH(ctx, "qm_tile_runs_kernel", qm_tile_runs_kernel<k>, grid_of(Lr), dim3(Lr.block), Lr.lds, X_dev, ld, T, C, pl.nchunks, runs,
+                  (int64_t)pl.np, status, set_mask);
+        SD_TRY(allow_lds(&qm_merge_runs_kernel<k>, Lm));
+        SD_LAUNCH(ctx, "qm_merge_runs_kernel", qm_merge_runs_kernel<k>, grid_of(Lm), dim3(Lm.block), Lm.lds, (const double*)runs, pl.np, T, C, xs);
+        return SD_OK;
+    });
+}
+
+// One field of a fit: X (set_mask) or y -> its sorted cell-major copy
+int sort_field(sd_ctx* ctx, const QmPlan& pl, const double* field, int64_t ld, int64_t T, int64_t C, double* sorted, int32_t* status,
+               int set_mask, double* runs) {
+    if (pl.tiled) return launch_tile_sort(ctx, pl, field, ld, T, C, sorted, status, set_mask, runs);
+    SD_TRY(launch_transpose(ctx, field, ld, T, C, sorted, status, set_mask));
+    return launch_sort(ctx, pl.K, sorted, T, C);
+}
+
+// Cell-major staging of a predict / Cunnane call.  in: the new series -> qc [C][Tp], their finite bookkeeping -> status_p.
+// out: oc [C][Tp] -> the time-major output (NaN for the cells either status flags), the public status, the stream drained.
+struct qm_staging {
+    sd_scratch qc, oc, status_p;
+};
+int stage_in(sd_ctx* ctx, const double* X_dev, int64_t ld, int64_t Tp, int64_t C, qm_staging* s) {
+    SD_HIP(s->qc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
+    SD_HIP(s->oc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
+    SD_HIP(s->status_p.alloc(ctx, sizeof(int32_t) * C));
+    SD_HIP(hipMemsetAsync(s->status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    return launch_transpose(ctx, X_dev, ld, Tp, C, s->qc.as<double>(), s->status_p.as<int32_t>(), 0);
+}
+int stage_out(sd_ctx* ctx, const sd_qm_state* st, const qm_staging& s, int64_t Tp, double* out_dev, int64_t ld_out, int32_t* cell_status) {
+    const int64_t C = st->C;
+    const QmLaunch Lu = ql::untranspose(C, Tp), Ls = ql::status_public(C);
+    SD_LAUNCH(ctx, "qm_untranspose_kernel", qm_untranspose_kernel, grid_of(Lu), dim3(Lu.block), Lu.lds, (const double*)s.oc.p, Tp, C, out_dev,
+              ld_out, (const int32_t*)st->status, (const int32_t*)s.status_p.p);
+    sd_scratch status_pub;
+    if (cell_status) {
+        SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
+        SD_LAUNCH(ctx, "qm_status_public_kernel", qm_status_public_kernel, grid_of(Ls), dim3(Ls.block), Ls.lds, (const int32_t*)st->status,
+                  (const int32_t*)s.status_p.p, C, status_pub.as<int32_t>());
+        SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SD_HIP(hipStreamSynchronize(ctx->stream));
     return SD_OK;
 }
-int launch_tile_sort_width(sd_ctx* ctx, int K, const double* X_dev, int64_t ld, int64_t T, int64_t C, double* xs, int32_t* status, int set_mask,
-                           double* runs) {
-    switch (K) {
-        case 13: return launch_tile_sort<13>(ctx, X_dev, ld, T, C, xs, status, set_mask, runs);
-        case 15: return launch_tile_sort<15>(ctx, X_dev, ld, T, C, xs, status, set_mask, runs);
-        case 17: return launch_tile_sort<17>(ctx, X_dev, ld, T, C, xs, status, set_mask, runs);
-    }
-    return sd_set_error(SD_ERR_INVALID, "qm tile sort: width %d not instantiated", K);
+
+// The host-buffer form of predict / Cunnane: upload the new series, run the resident call, download the result
+template <class Call>
+int with_device_copies(sd_ctx* ctx, const sd_qm_state* st, const char* op, const double* X, int64_t Tp, double* out, Call call) {
+    SD_CHECK_ARG(ctx && st && X && out, "%s: NULL argument", op);
+    SD_CHECK_ARG(Tp > 0, "%s: bad sizes", op);
+    SD_HIP(hipSetDevice(ctx->device));
+    sd_scratch dX, dout;
+    const size_t bytes = sizeof(double) * (size_t)Tp * st->C;
+    SD_HIP(dX.alloc(ctx, bytes));
+    SD_HIP(dout.alloc(ctx, bytes));
+    SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
+    SD_TRY(call(dX.as<double>(), dout.as<double>()));
+    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
+    SD_HIP(hipStreamSynchronize(ctx->stream));
+    return SD_OK;
 }
 
-#define QM_DISPATCH_K(K, call_prefix, ...)                              \
-    switch (K) {                                                        \
-        case 1: SD_TRY(call_prefix<1>(__VA_ARGS__)); break;             \
-        case 3: SD_TRY(call_prefix<3>(__VA_ARGS__)); break;             \
-        case 5: SD_TRY(call_prefix<5>(__VA_ARGS__)); break;             \
-        case 9: SD_TRY(call_prefix<9>(__VA_ARGS__)); break;             \
-        case 13: SD_TRY(call_prefix<13>(__VA_ARGS__)); break;           \
-        case 15: SD_TRY(call_prefix<15>(__VA_ARGS__)); break;           \
-        case 17: SD_TRY(call_prefix<17>(__VA_ARGS__)); break;           \
-        default: SD_TRY(call_prefix<19>(__VA_ARGS__)); break;           \
-    }
+QmCall qm_call(QmOp op, const sd_ctx* ctx, int64_t T, int64_t Tp, int64_t C, int64_t ld, int64_t ld_out, bool has_y) {
+    QmCall c;
+    c.op = op;
+    c.T = T, c.Tp = Tp, c.C = C, c.ld = ld, c.ld_out = ld_out;
+    c.has_y = has_y;
+    c.lds_max = ctx->lds_max;
+    c.cu_count = ctx->cu_count;
+    c.dev = sd_qm_dev_switches();
+    return c;
+}
 
 }  // namespace
 
@@ -864,11 +908,10 @@ int sd_qm_state_export(const sd_qm_state* st, double* x_sorted, double* y_sorted
 
 int sd_qm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, sd_qm_state** out) {
     SD_CHECK_ARG(ctx && X_dev && out, "sd_qm_fit: NULL argument");  // y may be NULL (CunnaneTransformer: only the X CDF)
-    SD_CHECK_ARG(T >= 2 && C > 0 && ld >= C, "sd_qm_fit: bad sizes");
     *out = nullptr;
+    const QmPlan pl = qm_plan(qm_call(QmOp::Fit, ctx, T, 0, C, ld, 0, y_dev != nullptr));
+    if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
     SD_HIP(hipSetDevice(ctx->device));
-    const int K = sort_width(T, ctx->lds_max);
-    if (K == 0) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_qm_fit: series of %lld samples exceed the workgroup sort (19456)", (long long)T);
     sd_qm_state* st = new sd_qm_state();
     st->ctx = ctx;
     st->T = T;
@@ -878,24 +921,11 @@ int sd_qm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t
         if (y_dev) SD_HIP(sd_pool_malloc(ctx, (void**)&st->ys, sizeof(double) * (size_t)T * C));
         SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * C));
         SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * C, ctx->stream));
-        const int Kt = tile_runs_width(T, ctx->lds_max);
-        if (Kt != 0) {  // tile-shaped first stage: sorted runs straight from the time-major fields, then the merge rounds
-            sd_scratch runs;
-            const int64_t np = (T + 64 * Kt - 1) / (64 * Kt) * (64 * Kt);
-            SD_HIP(runs.alloc(ctx, sizeof(double) * (size_t)np * C));
-            SD_TRY(launch_tile_sort_width(ctx, Kt, X_dev, ld, T, C, st->xs, st->status, 1, runs.as<double>()));
-            if (y_dev) SD_TRY(launch_tile_sort_width(ctx, Kt, y_dev, ld, T, C, st->ys, st->status, 0, runs.as<double>()));
-            SD_HIP(hipStreamSynchronize(ctx->stream));  // (the runs go back to the block cache at scope exit)
-            return SD_OK;
-        }
-        dim3 grid((unsigned)((C + 31) / 32), (unsigned)((T + 31) / 32));
-        SD_LAUNCH(ctx, "qm_transpose_kernel", qm_transpose_kernel, grid, dim3(256), 0, X_dev, ld, T, C, st->xs, st->status, 1);
-        QM_DISPATCH_K(K, launch_sort, ctx, st->xs, T, C);
-        if (y_dev) {
-            SD_LAUNCH(ctx, "qm_transpose_kernel", qm_transpose_kernel, grid, dim3(256), 0, y_dev, ld, T, C, st->ys, st->status, 0);
-            QM_DISPATCH_K(K, launch_sort, ctx, st->ys, T, C);
-        }
-        SD_HIP(hipStreamSynchronize(ctx->stream));
+        sd_scratch runs;
+        if (pl.tiled) SD_HIP(runs.alloc(ctx, pl.runs_bytes));
+        SD_TRY(sort_field(ctx, pl, X_dev, ld, T, C, st->xs, st->status, 1, runs.as<double>()));
+        if (y_dev) SD_TRY(sort_field(ctx, pl, y_dev, ld, T, C, st->ys, st->status, 0, runs.as<double>()));
+        SD_HIP(hipStreamSynchronize(ctx->stream));  // (the runs go back to the block cache at scope exit)
         return SD_OK;
     };
     const int rc = body();
@@ -925,67 +955,53 @@ int sd_qm_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t 
 int sd_qm_predict_dev(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapolate, int n_endpoints, const double* Xp_dev, int64_t ld,
                       int64_t Tp, double* out_dev, int64_t ld_out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xp_dev && out_dev, "sd_qm_predict: NULL argument");
-    SD_CHECK_ARG(extrapolate == SD_EXTRAP_1TO1 || (extrapolate >= SD_EXTRAP_NONE && extrapolate <= SD_EXTRAP_BOTH),
-                 "sd_qm_predict: unknown extrapolate code %d", extrapolate);
-    SD_CHECK_ARG(n_endpoints >= 2, "Invalid number of n_endpoints, must be >= 2");
-    SD_CHECK_ARG(model >= SD_QM_REGRESSOR && model <= SD_QM_EDCDF_RATIO, "sd_qm_predict: unknown model %d", model);
-    SD_CHECK_ARG(st->ys, "sd_qm_predict: the state was fitted without y");
-    SD_CHECK_ARG(Tp > 0 && ld >= st->C && ld_out >= st->C, "sd_qm_predict: bad sizes");
+    QmCall call = qm_call(QmOp::Predict, ctx, st->T, Tp, st->C, ld, ld_out, st->ys != nullptr);
+    call.model = model, call.extrapolate = extrapolate, call.n_endpoints = n_endpoints;
+    const QmPlan pl = qm_plan(call);
+    if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
     SD_HIP(hipSetDevice(ctx->device));
     const int64_t C = st->C, T = st->T;
-    const int K = model == SD_QM_REGRESSOR ? 1 : sort_width(Tp, ctx->lds_max);
-    if (K == 0) return sd_set_error(SD_ERR_UNSUPPORTED, "sd_qm_predict: series of %lld samples exceed the workgroup sort (19456)", (long long)Tp);
-    const size_t lds_map = sizeof(double) * (size_t)T;  // one table of the fit at a time (qm_map_kernel)
-    SD_CHECK_ARG(lds_map <= ctx->lds_max, "sd_qm_predict: fitted series too long for the LDS-resident search");
-    sd_scratch qc, oc, rk, status_p, status_pub;
-    SD_HIP(qc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
-    SD_HIP(oc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
-    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((Tp + 31) / 32));
-    SD_LAUNCH(ctx, "qm_transpose_kernel", qm_transpose_kernel, grid, dim3(256), 0, Xp_dev, ld, Tp, C, qc.as<double>(),
-              status_p.as<int32_t>(), 0);
-    if (model != SD_QM_REGRESSOR) {
+    qm_staging s;
+    sd_scratch rk, ppflag, tails;
+    SD_TRY(stage_in(ctx, Xp_dev, ld, Tp, C, &s));
+    if (pl.rank_K != 0) {
         SD_HIP(rk.alloc(ctx, sizeof(int32_t) * (size_t)Tp * C));
-        QM_DISPATCH_K(K, launch_rank, ctx, qc.as<double>(), Tp, C, rk.as<int32_t>());
+        SD_TRY(launch_rank(ctx, pl.rank_K, s.qc.as<double>(), Tp, C, rk.as<int32_t>()));
     }
     // plotting positions without divisions (ppq): only if the correction step reproduces the division on both grids
     const double dn_h = ((double)T + 1.0 - kAlpha) - kBeta, dm_h = ((double)Tp + 1.0 - kAlpha) - kBeta;  // pp_denom
     const double rdn_h = 1.0 / dn_h, rdm_h = 1.0 / dm_h;
-    sd_scratch ppflag, tails;
     SD_HIP(ppflag.alloc(ctx, sizeof(int32_t)));
     SD_HIP(hipMemsetAsync(ppflag.p, 0, sizeof(int32_t), ctx->stream));
-    SD_LAUNCH(ctx, "qm_ppcheck_kernel", qm_ppcheck_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (int)T, dn_h, rdn_h, ppflag.as<int32_t>());
-    SD_LAUNCH(ctx, "qm_ppcheck_kernel", qm_ppcheck_kernel, dim3((unsigned)((Tp + 255) / 256)), dim3(256), 0, (int)Tp, dm_h, rdm_h, ppflag.as<int32_t>());
+    const QmLaunch Ln = ql::ppcheck(T), Lm = ql::ppcheck(Tp);
+    SD_LAUNCH(ctx, "qm_ppcheck_kernel", qm_ppcheck_kernel, grid_of(Ln), dim3(Ln.block), Ln.lds, (int)T, dn_h, rdn_h, ppflag.as<int32_t>());
+    SD_LAUNCH(ctx, "qm_ppcheck_kernel", qm_ppcheck_kernel, grid_of(Lm), dim3(Lm.block), Lm.lds, (int)Tp, dm_h, rdm_h, ppflag.as<int32_t>());
     int32_t pp_mismatch = 1;
     SD_HIP(hipMemcpyAsync(&pp_mismatch, ppflag.p, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if ((extrapolate & (SD_EXTRAP_MIN | SD_EXTRAP_MAX)) != 0 && extrapolate != SD_EXTRAP_1TO1) {
+    if (pl.tails) {
+        const QmLaunch Lt = ql::tails(C);
         SD_HIP(tails.alloc(ctx, sizeof(double) * 4 * (size_t)C));
-        SD_LAUNCH(ctx, "qm_tails_kernel", qm_tails_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, extrapolate, n_endpoints,
-                  (const double*)st->xs, (const double*)st->ys, T, C, tails.as<double>());
+        SD_LAUNCH(ctx, "qm_tails_kernel", qm_tails_kernel, grid_of(Lt), dim3(Lt.block), Lt.lds, extrapolate, n_endpoints, (const double*)st->xs,
+                  (const double*)st->ys, T, C, tails.as<double>());
     }
     SD_HIP(hipStreamSynchronize(ctx->stream));
-    const bool fastpp = pp_mismatch == 0 && sd_dev_env("SD_QM_DIVIDE") == nullptr;
-    const int nb = (int)std::min<int64_t>(C, (int64_t)ctx->cu_count * (lds_map > ctx->lds_max / 2 ? 1 : 2));
-    SD_CHECK_ARG(Tp < ((int64_t)1 << 31), "sd_qm_predict: series too long");
-#define SD_QM_MAP(QMR, PER, FAST)                                                                                                          \
-    do {                                                                                                                                   \
-        SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_map_kernel<QMR, PER, FAST>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds_map));                                                                                         \
-        SD_LAUNCH(ctx, "qm_map_kernel", (qm_map_kernel<QMR, PER, FAST>), dim3(nb), dim3(1024), lds_map, model, extrapolate, n_endpoints,   \
-                  (const double*)qc.p, (const int32_t*)rk.p, (const double*)st->xs, (const double*)st->ys, T, Tp, C, oc.as<double>(),      \
-                  rdn_h, rdm_h, (const double*)tails.p);                                                                                   \
-    } while (0)
-    if (model == SD_QM_REGRESSOR) {
-        if (fastpp) SD_QM_MAP(true, 16, true);
-        else SD_QM_MAP(true, 16, false);
-    } else {
-        if (fastpp) SD_QM_MAP(false, 8, true);
-        else SD_QM_MAP(false, 8, false);
-    }
-#undef SD_QM_MAP
+    const bool fastpp = pp_mismatch == 0 && !pl.divide;  // the one decision that waits for the device (sd_qm_plan.h)
+    const auto launch_map = [&](auto qmr, auto per, auto fast) -> int {
+        const QmLaunch L = ql::map(pl);
+        SD_TRY(allow_lds(&qm_map_kernel<qmr, per, fast>, L));
+        SD_LAUNCH(ctx, "qm_map_kernel", (qm_map_kernel<qmr, per, fast>), grid_of(L), dim3(L.block), L.lds, model, extrapolate, n_endpoints,
+                  (const double*)s.qc.p, (const int32_t*)rk.p, (const double*)st->xs, (const double*)st->ys, T, Tp, C, s.oc.as<double>(), rdn_h,
+                  rdm_h, (const double*)tails.p);
+        return SD_OK;
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    constexpr std::integral_constant<int, sdqm::kMapPerQmr> per_qmr{};
+    constexpr std::integral_constant<int, sdqm::kMapPerEdcdf> per_edcdf{};
+    if (model == SD_QM_REGRESSOR) SD_TRY(fastpp ? launch_map(yes, per_qmr, yes) : launch_map(yes, per_qmr, no));
+    else SD_TRY(fastpp ? launch_map(no, per_edcdf, yes) : launch_map(no, per_edcdf, no));
 #ifdef SD_DEV
-    if (sd_dev_env("SD_QM_TRACE") != nullptr) {
+    if (pl.trace) {
         long long h[64];
         SD_HIP(hipStreamSynchronize(ctx->stream));
         SD_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(sd_qm_trace), sizeof(h)));
@@ -994,84 +1010,39 @@ int sd_qm_predict_dev(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapo
                     h[r * 8 + 2] - h[r * 8 + 1], h[r * 8 + 3] - h[r * 8 + 2], h[r * 8 + 4] - h[r * 8 + 3], h[r * 8 + 5] - h[r * 8 + 4], h[r * 8 + 6] - h[r * 8 + 5]);
     }
 #endif
-    SD_LAUNCH(ctx, "qm_untranspose_kernel", qm_untranspose_kernel, grid, dim3(256), 0, (const double*)oc.p, Tp, C, out_dev, ld_out,
-              (const int32_t*)st->status, (const int32_t*)status_p.p);
-    if (cell_status) {
-        SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
-        SD_LAUNCH(ctx, "qm_status_public_kernel", qm_status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0,
-                  (const int32_t*)st->status, (const int32_t*)status_p.p, C, status_pub.as<int32_t>());
-        SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return stage_out(ctx, st, s, Tp, out_dev, ld_out, cell_status);
 }
 
 int sd_qm_predict(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapolate, int n_endpoints, const double* Xp, int64_t Tp, double* out,
                   int32_t* cell_status) {
-    SD_CHECK_ARG(ctx && st && Xp && out, "sd_qm_predict: NULL argument");
-    SD_CHECK_ARG(Tp > 0, "sd_qm_predict: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
-    const size_t bytes = sizeof(double) * (size_t)Tp * st->C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xp, bytes));
-    SD_TRY(sd_qm_predict_dev(ctx, st, model, extrapolate, n_endpoints, dX.as<double>(), st->C, Tp, dout.as<double>(), st->C, cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return with_device_copies(ctx, st, "sd_qm_predict", Xp, Tp, out, [&](const double* dX, double* dout) {
+        return sd_qm_predict_dev(ctx, st, model, extrapolate, n_endpoints, dX, st->C, Tp, dout, st->C, cell_status);
+    });
 }
 
 int sd_qm_cunnane_dev(sd_ctx* ctx, const sd_qm_state* st, int direction, int extrapolate, int n_endpoints, const double* X_dev,
                       int64_t ld, int64_t Tp, double* out_dev, int64_t ld_out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && X_dev && out_dev, "sd_qm_cunnane: NULL argument");
-    SD_CHECK_ARG(direction == SD_CUNNANE_FORWARD || direction == SD_CUNNANE_INVERSE, "sd_qm_cunnane: unknown direction %d", direction);
-    SD_CHECK_ARG(extrapolate >= SD_EXTRAP_NONE && extrapolate <= SD_EXTRAP_BOTH, "sd_qm_cunnane: unknown extrapolate code %d", extrapolate);
-    SD_CHECK_ARG(n_endpoints >= 1, "sd_qm_cunnane: n_endpoints must be positive");
-    SD_CHECK_ARG(Tp > 0 && ld >= st->C && ld_out >= st->C, "sd_qm_cunnane: bad sizes");
+    QmCall call = qm_call(QmOp::Cunnane, ctx, st->T, Tp, st->C, ld, ld_out, st->ys != nullptr);
+    call.direction = direction, call.extrapolate = extrapolate, call.n_endpoints = n_endpoints;
+    const QmPlan pl = qm_plan(call);
+    if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
     SD_HIP(hipSetDevice(ctx->device));
     const int64_t C = st->C, T = st->T;
-    const size_t lds = direction == SD_CUNNANE_FORWARD ? sizeof(double) * (size_t)T : 8;
-    SD_CHECK_ARG(lds <= ctx->lds_max, "sd_qm_cunnane: fitted series too long for the LDS-resident search");
-    sd_scratch qc, oc, status_p, status_pub;
-    SD_HIP(qc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
-    SD_HIP(oc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
-    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((Tp + 31) / 32));
-    SD_LAUNCH(ctx, "qm_transpose_kernel", qm_transpose_kernel, grid, dim3(256), 0, X_dev, ld, Tp, C, qc.as<double>(),
-              status_p.as<int32_t>(), 0);
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&qm_cunnane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nb = (int)std::min<int64_t>(C, (int64_t)ctx->cu_count * (lds > ctx->lds_max / 2 ? 1 : 2));
-    SD_LAUNCH(ctx, "qm_cunnane_kernel", qm_cunnane_kernel, dim3(nb), dim3(1024), lds, direction, extrapolate & SD_EXTRAP_MIN,
-              extrapolate & SD_EXTRAP_MAX, n_endpoints, (const double*)qc.p, (const double*)st->xs, T, Tp, C, oc.as<double>());
-    SD_LAUNCH(ctx, "qm_untranspose_kernel", qm_untranspose_kernel, grid, dim3(256), 0, (const double*)oc.p, Tp, C, out_dev, ld_out,
-              (const int32_t*)st->status, (const int32_t*)status_p.p);
-    if (cell_status) {
-        SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
-        SD_LAUNCH(ctx, "qm_status_public_kernel", qm_status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0,
-                  (const int32_t*)st->status, (const int32_t*)status_p.p, C, status_pub.as<int32_t>());
-        SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    qm_staging s;
+    SD_TRY(stage_in(ctx, X_dev, ld, Tp, C, &s));
+    const QmLaunch L = ql::cunnane(pl);
+    SD_TRY(allow_lds(&qm_cunnane_kernel, L));
+    SD_LAUNCH(ctx, "qm_cunnane_kernel", qm_cunnane_kernel, grid_of(L), dim3(L.block), L.lds, direction, extrapolate & SD_EXTRAP_MIN,
+              extrapolate & SD_EXTRAP_MAX, n_endpoints, (const double*)s.qc.p, (const double*)st->xs, T, Tp, C, s.oc.as<double>());
+    return stage_out(ctx, st, s, Tp, out_dev, ld_out, cell_status);
 }
 
 int sd_qm_cunnane(sd_ctx* ctx, const sd_qm_state* st, int direction, int extrapolate, int n_endpoints, const double* X, int64_t Tp,
                   double* out, int32_t* cell_status) {
-    SD_CHECK_ARG(ctx && st && X && out, "sd_qm_cunnane: NULL argument");
-    SD_CHECK_ARG(Tp > 0, "sd_qm_cunnane: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
-    const size_t bytes = sizeof(double) * (size_t)Tp * st->C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    SD_TRY(sd_qm_cunnane_dev(ctx, st, direction, extrapolate, n_endpoints, dX.as<double>(), st->C, Tp, dout.as<double>(), st->C,
-                             cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return with_device_copies(ctx, st, "sd_qm_cunnane", X, Tp, out, [&](const double* dX, double* dout) {
+        return sd_qm_cunnane_dev(ctx, st, direction, extrapolate, n_endpoints, dX, st->C, Tp, dout, st->C, cell_status);
+    });
 }
 
 }  // extern "C"

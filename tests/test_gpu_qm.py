@@ -65,7 +65,8 @@ def test_goldens_from_the_reference(ctx, case, resident):
                 check_against(out, g[f"out{case}_{name}_{ex}_{ne}"], X, Xp, floor, f"{name} case {case} extrapolate={ex} n_endpoints={ne}")
 
 
-@pytest.mark.parametrize("T,Tp,C", [(21, 21, 1), (365, 400, 5), (3000, 2999, 7), (14600, 14600, 4), (14600, 9000, 3), (5000, 19000, 2)])
+@pytest.mark.parametrize("T,Tp,C", [(21, 21, 1), (365, 400, 5), (3000, 2999, 7), (14600, 14600, 4), (14600, 9000, 3), (5000, 19000, 2),
+                                    (17408, 700, 9), (17409, 700, 9)])
 def test_vs_oracle_sizes_and_ties(ctx, T, Tp, C):
     """Every sort width (1 ... 19 samples per thread), ties in fit and predict series (quantized data: the stable
     (value, index) order defines the ranks of EquidistantCdfMatcher), values outside the fitted range, every
@@ -421,7 +422,7 @@ def test_pointwise_transformers_match_the_reference_loop():
     assert_close(np.asarray(climo.values).reshape(12, C), g["y_climo"], what="get_attr('y_climo_')")
 
 
-@pytest.mark.parametrize("T,Tp", [(14600, 14600), (3000, 7001), (19000, 5000)])
+@pytest.mark.parametrize("T,Tp", [(14600, 14600), (3000, 7001), (19000, 5000), (17408, 700), (17409, 700)])
 def test_round6_paths_are_bit_identical_to_the_kernels_they_replace(dev_ctx, monkeypatch, T, Tp):
     """Round 6: the tile-shaped first stage of the fit (qm_tile_runs_kernel + qm_merge_runs_kernel; series of up to 17 408 samples)
     against the staging transpose + workgroup sort (SD_QM_NOTILE), and the plotting positions by the verified correction step
