@@ -20,6 +20,10 @@
  *                              grouping.PaddedDOYGrouper (grouping.py:106-138), or on disjoint groups (window = 0)
  *   sd_grouped_predict*     <- GroupedRegressor.predict (grouping.py:82-103): the model of each sample's own key
  *   sd_grouped_state_*      <- the fitted estimators_ (coef_, intercept_ of every group; grouping.py:74)
+ *   sd_arrm_fit*            <- PiecewiseLinearRegression(fit_option='arrm').fit (arrm.py:144-167): arrm_breakpoints
+ *                              (arrm.py:19-105) and pwlf's fit_with_breaks (degree 1) on them
+ *   sd_arrm_predict*        <- PiecewiseLinearRegression.predict (arrm.py:169-177)
+ *   sd_arrm_state_*         <- fit_breaks_ and the numbers of model_ (beta, ssr)
  *
  * Conventions
  *   - Plain pointers and sizes only.  All fields are float64, time-major with the cell axis
@@ -98,6 +102,7 @@ typedef struct sd_qm_state sd_qm_state;
 typedef struct sd_linreg_state sd_linreg_state;
 typedef struct sd_zscore_state sd_zscore_state;
 typedef struct sd_grouped_state sd_grouped_state;
+typedef struct sd_arrm_state sd_arrm_state;
 typedef struct sd_comm sd_comm;
 #define SD_COMM_ID_BYTES 128 /* RCCL's ncclUniqueId */
 
@@ -344,6 +349,30 @@ int sd_grouped_state_export(const sd_grouped_state* st, double* coef, double* in
 int sd_grouped_state_import(sd_ctx* ctx, int n, int F, int64_t C, int window, const double* coef, const double* intercept,
                             const int32_t* fitted, const int32_t* cell_status, sd_grouped_state** out);
 int sd_grouped_state_destroy(sd_grouped_state* st);
+
+/* ---- PiecewiseLinearRegression(fit_option='arrm') ------------------------------------------------------
+ * fit: X [T, C], y [T, C] (one feature).  Per cell arrm_breakpoints(X, y, 0.05, max_breakpoints) of the reference: B =
+ * 2 * (max_breakpoints / 2) breaks, taken where the correlation of the two independently sorted series over a sliding window is
+ * lowest; then the continuous piecewise-linear least-squares fit on those breaks (pwlf fit_with_breaks, degree 1), minimum norm
+ * where breaks repeat.  Supported: T >= 50 and 2 <= B <= 16, anything else is SD_ERR_INVALID; series beyond the workgroup sort
+ * are SD_ERR_UNSUPPORTED.  r2 (may be NULL): [T, C] diagnostic with rows of C entries (r2_dev too, whatever ld is), r2[t, c] is the squared correlation of the window that the
+ * reference writes last to slot t (both loops, without the masks), NaN for a window of equal values, 2 for a slot no window
+ * writes.
+ * predict: out [Tq, C], out = beta[0] + beta[1] (x - b[0]) + sum_{j=1}^{B-2} beta[j+1] max(x - b[j], 0); the line extends beyond
+ * both ends.  Cell status as for sd_linreg_*. */
+int sd_arrm_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t C, int max_breakpoints, double* r2, sd_arrm_state** out);
+int sd_arrm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, int max_breakpoints,
+                    double* r2_dev, sd_arrm_state** out);
+int sd_arrm_predict(sd_ctx* ctx, const sd_arrm_state* st, const double* Xq, int64_t Tq, double* out, int32_t* cell_status);
+int sd_arrm_predict_dev(sd_ctx* ctx, const sd_arrm_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, double* out_dev, int64_t ld_out,
+                        int32_t* cell_status);
+int sd_arrm_state_info(const sd_arrm_state* st, int* B, int64_t* C, int64_t* T);
+/* breaks [B, C] ascending, break_index int32 [B, C] (positions in the sorted X; -1 for cells with a status), beta [B, C],
+ * ssr [C] (sum of squared residuals), cell_status int32 [C]; any pointer may be NULL */
+int sd_arrm_state_export(const sd_arrm_state* st, double* breaks, int32_t* break_index, double* beta, double* ssr, int32_t* cell_status);
+int sd_arrm_state_import(sd_ctx* ctx, int B, int64_t C, int64_t T, const double* breaks, const int32_t* break_index, const double* beta,
+                         const double* ssr, const int32_t* cell_status, sd_arrm_state** out);
+int sd_arrm_state_destroy(sd_arrm_state* st);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

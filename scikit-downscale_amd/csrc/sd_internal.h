@@ -203,6 +203,15 @@ struct sd_analog_state {
     double* ps = nullptr;   // device [C][F][T]
 };
 
+// (here, not in sd_qm.hip: sd_arrm.hip sorts its two series with sd_qm_fit_dev and reads them in place)
+struct sd_qm_state {
+    sd_ctx* ctx = nullptr;
+    int64_t T = 0, C = 0;
+    double* xs = nullptr;       // device [C][T] sorted X
+    double* ys = nullptr;       // device [C][T] sorted y
+    int32_t* status = nullptr;  // device [C] internal bitmask
+};
+
 int sd_set_error(int code, const char* fmt, ...);
 // Returns a device pointer to at least `bytes` of context-owned scratch (valid until the next call on
 // the context asks for more).  Calls on a context are serialised, so one buffer is enough.

@@ -24,14 +24,6 @@
 #include "sd_sortnet.h"
 #include "sd_wave.h"
 
-struct sd_qm_state {
-    sd_ctx* ctx = nullptr;
-    int64_t T = 0, C = 0;
-    double* xs = nullptr;       // device [C][T] sorted X
-    double* ys = nullptr;       // device [C][T] sorted y
-    int32_t* status = nullptr;  // device [C] internal bitmask
-};
-
 namespace {
 
 __device__ __forceinline__ bool qm_finite(double v) { return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll; }

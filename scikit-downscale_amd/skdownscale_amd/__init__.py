@@ -3,6 +3,7 @@
 Public names mirror ``skdownscale.pointwise_models`` for the hot path only
 (``skdownscale/pointwise_models/__init__.py:17-36`` of the reference).
 """
+from .arrm import ArrmGridModel, PiecewiseLinearRegression, arrm_breakpoints
 from .bcsd import BcsdGridModel, BcsdPrecipitation, BcsdTemperature
 from .core import GridArray, GridDataset, PointWiseDownscaler
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
@@ -40,5 +41,8 @@ __all__ = [
     "ZScoreGridModel",
     "GroupedRegressor",
     "GroupedGridModel",
+    "PiecewiseLinearRegression",
+    "ArrmGridModel",
+    "arrm_breakpoints",
 ]
 __version__ = "0.1.0"

@@ -105,6 +105,14 @@ SIGNATURES = {
     "sd_grouped_state_export": [_p, _p, _p, _p, _p],
     "sd_grouped_state_import": [_p, _int, _int, _i64, _int, _p, _p, _p, _p, C.POINTER(_p)],
     "sd_grouped_state_destroy": [_p],
+    "sd_arrm_fit": [_p, _p, _p, _i64, _i64, _int, _p, C.POINTER(_p)],
+    "sd_arrm_fit_dev": [_p, _p, _p, _i64, _i64, _i64, _int, _p, C.POINTER(_p)],
+    "sd_arrm_predict": [_p, _p, _p, _i64, _p, _p],
+    "sd_arrm_predict_dev": [_p, _p, _p, _i64, _i64, _p, _i64, _p],
+    "sd_arrm_state_info": [_p, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64)],
+    "sd_arrm_state_export": [_p, _p, _p, _p, _p, _p],
+    "sd_arrm_state_import": [_p, _int, _i64, _i64, _p, _p, _p, _p, _p, C.POINTER(_p)],
+    "sd_arrm_state_destroy": [_p],
     "sd_qm_fit": [_p, _p, _p, _i64, _i64, C.POINTER(_p)],
     "sd_qm_fit_dev": [_p, _p, _p, _i64, _i64, _i64, C.POINTER(_p)],
     "sd_qm_predict": [_p, _p, _int, _int, _int, _p, _i64, _p, _p],

@@ -17,6 +17,7 @@ import numpy as np
 import pandas as pd
 
 from . import _lib
+from .arrm import ArrmGridModel, PiecewiseLinearRegression
 from .bcsd import BcsdBase, check_supported
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .quantile import (CunnaneGridModel, CunnaneTransformer, QmGridModel, QuantileMapper, QuantileMapperGridModel,
@@ -246,7 +247,7 @@ class _BatchedModels:
     """Fitted state of a whole grid held by the engine (replaces the object array of estimators)."""
 
     def __init__(self, kind, grid_model, mask, spatial_dims, spatial_shape, coords):
-        self.kind = kind  # 'bcsd' | 'analog' | 'linreg' | 'qm' | 'cunnane' | 'qmapper' | 'zscore' | 'grouped' | 'loop'
+        self.kind = kind  # 'bcsd' | 'analog' | 'linreg' | 'qm' | 'cunnane' | 'qmapper' | 'zscore' | 'grouped' | 'arrm' | 'loop'
         self.grid_model = grid_model
         self.mask = mask
         self.spatial_dims = spatial_dims
@@ -413,6 +414,9 @@ class PointWiseDownscaler:
         if isinstance(m, GroupedRegressor):
             m._check_engine()
             return "grouped"
+        if isinstance(m, PiecewiseLinearRegression):
+            m._check()
+            return "arrm"
         return None
 
     # ------------------------------------------------------------------------------------------
@@ -484,6 +488,14 @@ class PointWiseDownscaler:
             if T == 1:  # zscore.py:51-52: X.squeeze() of one sample is a scalar
                 raise TypeError("X.squeeze() must be a pd.Series, got float64")
             gm = ZScoreGridModel(m.window_width).fit(Xv[:, 0, :], yv, index)
+            self._raise_for_status(gm.status_, Xv[:, 0, :], yv)
+        elif kind == "arrm":
+            if F != 1:
+                raise ValueError(f"Found array with {F} features (shape=({T}, {F})) while a maximum of 1 is required")
+            extra = [k for k in kws if k not in ("along_dim", "feature_dim")]
+            if extra:  # the class raises for them, as pwlf's fit_with_breaks would
+                raise TypeError(f"fit_with_breaks() got an unexpected keyword argument '{extra[0]}'")
+            gm = ArrmGridModel(m.n_segments).fit(Xv[:, 0, :], yv)
             self._raise_for_status(gm.status_, Xv[:, 0, :], yv)
         elif kind == "grouped":
             plan = m._fit_plan(index)
@@ -609,6 +621,13 @@ class PointWiseDownscaler:
             if F != 1:
                 raise ValueError(f"X must have exactly 1 feature, got {F}")
             out, status, _ = mdl.grid_model.predict(Xv[:, 0, :])
+            self._raise_for_status(status, Xv[:, 0, :], Xv[:, 0, :])
+            vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
+            res = GridArray(vals, (self._dim,) + spatial_dims, coords)
+        elif mdl.kind == "arrm":
+            if F != 1:
+                raise ValueError(f"Found array with {F} features (shape=({T}, {F})) while a maximum of 1 is required")
+            out, status = mdl.grid_model.predict(Xv[:, 0, :])
             self._raise_for_status(status, Xv[:, 0, :], Xv[:, 0, :])
             vals = out.reshape((T,) + tuple(spatial_shape)).astype(Xg.dtype, copy=False)
             res = GridArray(vals, (self._dim,) + spatial_dims, coords)
@@ -739,7 +758,7 @@ class PointWiseDownscaler:
             est = copy.deepcopy(m)
             est._adopt(e, c, e["labels"])
             return est
-        if mdl.kind == "grouped":
+        if mdl.kind in ("grouped", "arrm"):
             e = cache.setdefault("e", mdl.grid_model.export())
             est = copy.deepcopy(m)
             est._adopt(e, c)
@@ -785,7 +804,8 @@ class PointWiseDownscaler:
         Engine-batched grids rebuild the per-cell fitted attributes from the exported state.  Extension: without a template,
         the BCSD climatologies ``y_climo_`` / ``_x_climo`` come back as [group, *spatial] fields, the ZScoreRegressor
         parameters ``shift_`` / ``scale_`` as [day, *spatial] fields, and the GroupedRegressor models ``coef_`` / ``intercept_`` as
-        [group, feature, *spatial] / [group, *spatial] fields."""
+        [group, feature, *spatial] / [group, *spatial] fields, and the PiecewiseLinearRegression breaks ``fit_breaks_`` as a
+        [break, *spatial] field."""
         mdl = self._models
         if mdl is None:
             raise ValueError("PointWiseDownscaler is not fitted: call fit() first")
@@ -805,6 +825,11 @@ class PointWiseDownscaler:
             coords["group"] = e["labels"]
             lead = ("group", DEFAULT_FEATURE_DIM) if key == "coef_" else ("group",)
             return GridArray(a.reshape(a.shape[:len(lead)] + tuple(mdl.spatial_shape)), lead + tuple(mdl.spatial_dims), coords)
+        if mdl.kind == "arrm" and key == "fit_breaks_" and template_output is None:
+            a = np.where(mdl.mask[None, :], mdl.grid_model.export()["breaks"], np.nan).astype(dtype)  # [B, C]
+            coords = dict(mdl.coords)
+            coords["break"] = np.arange(a.shape[0])
+            return GridArray(a.reshape((a.shape[0],) + tuple(mdl.spatial_shape)), ("break",) + tuple(mdl.spatial_dims), coords)
         if mdl.kind == "zscore" and key in ("shift_", "scale_") and template_output is None:
             e = mdl.grid_model.export()
             a = np.where(mdl.mask[None, :], e[key[:-1]], np.nan).astype(dtype)  # [K, C]

@@ -209,6 +209,26 @@ class GroupedState(_State):
         return dict(coef=coef, intercept=icpt, fitted=fitted.astype(bool), status=status, window=i["window"])
 
 
+class ArrmState(_State):
+    def info(self):
+        B, Cc, T = C.c_int(), C.c_int64(), C.c_int64()
+        check(self.ctx.lib.sd_arrm_state_info(self.vptr, C.byref(B), C.byref(Cc), C.byref(T)))
+        return dict(B=B.value, C=Cc.value, T=T.value)
+
+    def status(self):
+        status = np.empty(self.info()["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_arrm_state_export(self.vptr, None, None, None, None, ptr(status)))
+        return status
+
+    def export(self):
+        """breaks [B, C], break_index [B, C] (int32), beta [B, C], ssr [C], status [C], T"""
+        i = self.info()
+        breaks, beta = np.empty((i["B"], i["C"])), np.empty((i["B"], i["C"]))
+        index, ssr, status = np.empty((i["B"], i["C"]), dtype=np.int32), np.empty(i["C"]), np.empty(i["C"], dtype=np.int32)
+        check(self.ctx.lib.sd_arrm_state_export(self.vptr, ptr(breaks), ptr(index), ptr(beta), ptr(ssr), ptr(status)))
+        return dict(breaks=breaks, break_index=index, beta=beta, ssr=ssr, status=status, T=i["T"])
+
+
 class QmState(_State):
     def info(self):
         T, Cc = C.c_int64(), C.c_int64()
@@ -826,6 +846,52 @@ class Context:
             check(self.lib.sd_grouped_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, ptr(key), out.vptr, out.ld, ptr(status)))
         else:
             check(self.lib.sd_grouped_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(key), ptr(out), ptr(status)))
+        return out, status
+
+    # ---- PiecewiseLinearRegression(fit_option='arrm') ----
+    def arrm_fit(self, X, y, max_breakpoints, with_r2=False):
+        """X, y [T, C] (numpy or DeviceArray) -> ArrmState, or (ArrmState, r2 [T, C]) with ``with_r2`` (sd_arrm_fit)"""
+        X = self._field2("X", X)
+        y = self._field2("y", y, *X.shape)
+        T, Cc = X.shape
+        h = C.c_void_p()
+        if isinstance(X, DeviceArray):
+            if not isinstance(y, DeviceArray) or X.ld != y.ld:
+                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
+            r2 = self.empty((T, Cc)) if with_r2 else None
+            check(self.lib.sd_arrm_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(max_breakpoints), r2.vptr if with_r2 else None,
+                                           C.byref(h)))
+        else:
+            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
+            r2 = np.empty((T, Cc)) if with_r2 else None
+            check(self.lib.sd_arrm_fit(self.handle, ptr(X), ptr(y), T, Cc, int(max_breakpoints), ptr(r2), C.byref(h)))
+        state = ArrmState(self, h.value, self.lib.sd_arrm_state_destroy)
+        return (state, r2) if with_r2 else state
+
+    def arrm_import(self, exported):
+        """device state from ``ArrmState.export()`` (pickling)"""
+        breaks, beta = _lib.as_f64(exported["breaks"]), _lib.as_f64(exported["beta"])
+        B, Cc = breaks.shape
+        index, ssr = _lib.as_i32(exported["break_index"]), _lib.as_f64(exported["ssr"])
+        if beta.shape != (B, Cc) or index.shape != (B, Cc) or ssr.shape != (Cc,):
+            raise ValueError("arrm_import: expected breaks, break_index and beta [B, C] and ssr [C]")
+        h = C.c_void_p()
+        check(self.lib.sd_arrm_state_import(self.handle, B, Cc, int(exported["T"]), ptr(breaks), ptr(index), ptr(beta), ptr(ssr),
+                                            ptr(_lib.as_i32(exported["status"])), C.byref(h)))
+        return ArrmState(self, h.value, self.lib.sd_arrm_state_destroy)
+
+    def arrm_predict(self, state, Xq, out=None):
+        """Xq [Tq, C] -> (out [Tq, C], cell status [C])"""
+        Cc = state.info()["C"]
+        Xq = self._field2("Xq", Xq, None, Cc)
+        Tq = Xq.shape[0]
+        dev = isinstance(Xq, DeviceArray)
+        out = self._result_buffer(out, (Tq, Cc), dev)
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
+            check(self.lib.sd_arrm_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, out.vptr, out.ld, ptr(status)))
+        else:
+            check(self.lib.sd_arrm_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(out), ptr(status)))
         return out, status
 
 

@@ -22,7 +22,7 @@ from skdownscale_amd.engine import Context  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped"], default="analog")
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm"], default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
     ap.add_argument("--steps", type=int, default=2)
@@ -82,6 +82,19 @@ def main():
             return r
         bytes_per_cell = 8 * ((F + 1) * T + (F + 1) * T)  # fit reads X and y, predict reads X_fut and writes out
         name = f"GroupedRegressor LinearRegression per day of year, window=15, F={F} (fit + predict), {C} cells x {T} steps"
+    elif args.workload == "arrm":
+        from skdownscale_amd.arrm import ArrmGridModel
+
+        f = {n: field(synth.GAUSS, s0, amp=a) for n, s0, a in (("X", 30, 3.0), ("y", 31, 4.0), ("Xp", 32, 3.5))}
+        out = ctx.empty((T, C))
+
+        def step():
+            gm = ArrmGridModel(7, ctx=ctx).fit(f["X"], f["y"])
+            r = gm.predict(f["Xp"], out=out)
+            gm.state.close()
+            return r
+        bytes_per_cell = 8 * (2 * T + 2 * T)  # fit reads X and y, predict reads Xp and writes out
+        name = f"PiecewiseLinearRegression fit_option='arrm', n_segments=7 (fit + predict), {C} cells x {T} steps"
     elif args.workload in ("qmr", "ecm"):
         f = {n: field(synth.GAUSS, s0, amp=a) for n, s0, a in (("X", 30, 3.0), ("y", 31, 4.0), ("Xp", 32, 3.5))}
         out = ctx.empty((T, C))
