@@ -19,6 +19,7 @@
 
 #include "sd_arrm_plan.h"
 #include "sd_internal.h"
+#include "sd_state.h"
 
 struct sd_arrm_state {
     sd_ctx* ctx = nullptr;
@@ -445,34 +446,23 @@ int allow_lds(Kernel kernel, const ArrmLaunch& L) {
     return SD_OK;
 }
 
-int alloc_arrm(sd_ctx* ctx, sd_arrm_state* st) {
-    const size_t n = (size_t)st->B * st->C;
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->breaks, sizeof(double) * n));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->break_index, sizeof(int32_t) * n));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->beta, sizeof(double) * n));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->ssr, sizeof(double) * st->C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * st->C));
-    return SD_OK;
+std::vector<sd_buf> arrm_bufs(const sd_arrm_state* st) {
+    const size_t C = (size_t)st->C, n = (size_t)st->B * C;
+    return {sd_buf_of(st->breaks, n), sd_buf_of(st->break_index, n), sd_buf_of(st->beta, n), sd_buf_of(st->ssr, C),
+            sd_buf_of(st->status, C, true)};
+}
+
+sd_arrm_state* new_arrm(sd_ctx* ctx, int B, int64_t C, int64_t T) {
+    sd_arrm_state* st = new sd_arrm_state();
+    st->ctx = ctx; st->B = B; st->C = C; st->T = T;
+    return st;
 }
 
 }  // namespace
 
 extern "C" {
 
-int sd_arrm_state_destroy(sd_arrm_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    if (st->breaks) sd_pool_release(st->ctx, st->breaks);
-    if (st->break_index) sd_pool_release(st->ctx, st->break_index);
-    if (st->beta) sd_pool_release(st->ctx, st->beta);
-    if (st->ssr) sd_pool_release(st->ctx, st->ssr);
-    if (st->status) sd_pool_release(st->ctx, st->status);
-    delete st;
-    return SD_OK;
-}
+int sd_arrm_state_destroy(sd_arrm_state* st) { return sd_state_destroy(st, arrm_bufs); }
 
 int sd_arrm_state_info(const sd_arrm_state* st, int* B, int64_t* C, int64_t* T) {
     SD_CHECK_ARG(st, "state is NULL");
@@ -486,19 +476,8 @@ int sd_arrm_state_export(const sd_arrm_state* st, double* breaks, int32_t* break
     SD_CHECK_ARG(st, "state is NULL");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    const size_t n = (size_t)st->B * st->C;
-    if (breaks) SD_HIP(hipMemcpyAsync(breaks, st->breaks, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (break_index) SD_HIP(hipMemcpyAsync(break_index, st->break_index, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (beta) SD_HIP(hipMemcpyAsync(beta, st->beta, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (ssr) SD_HIP(hipMemcpyAsync(ssr, st->ssr, sizeof(double) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (cell_status) {
-        std::vector<int32_t> bits(st->C);
-        SD_HIP(hipMemcpyAsync(bits.data(), st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(bits[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    SD_TRY(sd_state_copy(ctx, arrm_bufs(st), {breaks, break_index, beta, ssr}, hipMemcpyDeviceToHost));
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 // fitted numbers -> device state (pickling, checkpoint / resume)
@@ -508,29 +487,14 @@ int sd_arrm_state_import(sd_ctx* ctx, int B, int64_t C, int64_t T, const double*
     SD_CHECK_ARG(C > 0 && B >= 2 && B <= kMaxBreaks && B % 2 == 0 && T >= 0, "sd_arrm_state_import: bad sizes");
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
-    sd_arrm_state* st = new sd_arrm_state();
-    st->ctx = ctx; st->B = B; st->C = C; st->T = T;
-    std::vector<int32_t> bits(C, 0);
-    if (cell_status)
-        for (int64_t c = 0; c < C; ++c) bits[c] = sd_internal_status(cell_status[c]);
-    auto body = [&]() -> int {
-        SD_TRY(alloc_arrm(ctx, st));
-        const size_t n = (size_t)B * C;
-        SD_HIP(hipMemcpyAsync(st->breaks, breaks, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->break_index, break_index, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->beta, beta, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->ssr, ssr, sizeof(double) * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->status, bits.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
+    sd_arrm_state* st = new_arrm(ctx, B, C, T);
+    const std::vector<int32_t> bits = sd_status_bits(cell_status, C);
+    return sd_state_build(st, sd_arrm_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, arrm_bufs(st)));
+        SD_TRY(sd_state_copy(ctx, arrm_bufs(st), {breaks, break_index, beta, ssr, bits.data()}, hipMemcpyHostToDevice));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_arrm_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_arrm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, int max_breakpoints,
@@ -547,10 +511,9 @@ int sd_arrm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64
     SD_HIP(hipSetDevice(ctx->device));
     sd_qm_state* sorted = nullptr;
     SD_TRY(sd_qm_fit_dev(ctx, X_dev, y_dev, ld, T, C, &sorted));  // xs, ys [C][T]; the mask and non-finite bookkeeping
-    sd_arrm_state* st = new sd_arrm_state();
-    st->ctx = ctx; st->B = pl.B; st->C = C; st->T = T;
-    auto body = [&]() -> int {
-        SD_TRY(alloc_arrm(ctx, st));
+    sd_arrm_state* st = new_arrm(ctx, pl.B, C, T);
+    const int rc = sd_state_build(st, sd_arrm_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, arrm_bufs(st)));
         SD_HIP(hipMemcpyAsync(st->status, sorted->status, sizeof(int32_t) * C, hipMemcpyDeviceToDevice, ctx->stream));
         SD_TRY(allow_lds(&arrm_select_kernel, pl.select));
         SD_LAUNCH(ctx, "arrm_select_kernel", arrm_select_kernel, grid_of(pl.select), dim3(pl.select.block), pl.select.lds,
@@ -566,39 +529,25 @@ int sd_arrm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64
                   (const int32_t*)st->status, st->beta, st->ssr);
         SD_HIP(hipStreamSynchronize(ctx->stream));  // (the partial sums go back to the cache on return)
         return SD_OK;
-    };
-    const int rc = body();
+    });
     sd_qm_state_destroy(sorted);
-    if (rc != SD_OK) {
-        sd_arrm_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    return rc;
 }
 
 int sd_arrm_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t C, int max_breakpoints, double* r2, sd_arrm_state** out) {
     SD_CHECK_ARG(ctx && X && y && out, "sd_arrm_fit: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0, "sd_arrm_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy, dr;
+    *out = nullptr;
     const size_t bytes = sizeof(double) * (size_t)T * C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dy.alloc(ctx, bytes));
-    if (r2) SD_HIP(dr.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, bytes));
-    SD_TRY(sd_arrm_fit_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, C, max_breakpoints, r2 ? dr.as<double>() : nullptr, out));
-    if (r2) {
-        const int rc = sd_copy_d2h(ctx, r2, dr.p, bytes);
-        if (rc != SD_OK) {
-            sd_arrm_state_destroy(*out);
-            *out = nullptr;
-            return rc;
-        }
+    const sd_host_field f[] = {sd_in(X, bytes), sd_in(y, bytes), sd_out(r2, bytes)};
+    const int rc = with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_arrm_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, C, max_breakpoints, (double*)d[2], out);
+    });
+    if (rc != SD_OK && *out) {  // the fit succeeded, r2 did not come back: no state without it
+        sd_arrm_state_destroy(*out);
+        *out = nullptr;
     }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return rc;
 }
 
 int sd_arrm_predict_dev(sd_ctx* ctx, const sd_arrm_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, double* out_dev, int64_t ld_out,
@@ -610,34 +559,20 @@ int sd_arrm_predict_dev(sd_ctx* ctx, const sd_arrm_state* st, const double* Xq_d
     SD_CHECK_ARG(L.gy < 65536, "sd_arrm_predict: Tq = %lld samples exceed the grid", (long long)Tq);
     SD_HIP(hipSetDevice(ctx->device));
     sd_scratch status_p;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     SD_LAUNCH(ctx, "arrm_predict_kernel", arrm_predict_kernel, grid_of(L), dim3(L.block), L.lds, Xq_dev, ld, Tq, C, st->B,
               (const double*)st->breaks, (const double*)st->beta, (const int32_t*)st->status, status_p.as<int32_t>(), out_dev, ld_out);
-    if (cell_status) {
-        std::vector<int32_t> a(C), b(C);
-        SD_HIP(hipMemcpyAsync(a.data(), st->status, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipMemcpyAsync(b.data(), status_p.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < C; ++c) cell_status[c] = sd_public_status(a[c] | b[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return sd_status_fold(ctx, st->status, status_p.as<int32_t>(), C, cell_status);
 }
 
 int sd_arrm_predict(sd_ctx* ctx, const sd_arrm_state* st, const double* Xq, int64_t Tq, double* out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xq && out, "sd_arrm_predict: NULL argument");
     SD_CHECK_ARG(Tq > 0, "sd_arrm_predict: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
     const size_t bytes = sizeof(double) * (size_t)Tq * st->C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xq, bytes));
-    SD_TRY(sd_arrm_predict_dev(ctx, st, dX.as<double>(), st->C, Tq, dout.as<double>(), st->C, cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const sd_host_field f[] = {sd_in(Xq, bytes), sd_out(out, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_arrm_predict_dev(ctx, st, (const double*)d[0], st->C, Tq, (double*)d[1], st->C, cell_status);
+    });
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "sd_grouped_plan.h"
 #include "sd_internal.h"
 #include "sd_lsq.h"
+#include "sd_state.h"
 
 struct sd_grouped_state {
     sd_ctx* ctx = nullptr;
@@ -244,31 +245,15 @@ int launch_predict(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq, in
     return SD_OK;
 }
 
-#define GROUPED_DISPATCH_F(F, fn, ...)                     \
-    switch (F) {                                           \
-        case 1: SD_TRY(fn<1>(__VA_ARGS__)); break;         \
-        case 2: SD_TRY(fn<2>(__VA_ARGS__)); break;         \
-        case 3: SD_TRY(fn<3>(__VA_ARGS__)); break;         \
-        case 4: SD_TRY(fn<4>(__VA_ARGS__)); break;         \
-        case 5: SD_TRY(fn<5>(__VA_ARGS__)); break;         \
-        case 6: SD_TRY(fn<6>(__VA_ARGS__)); break;         \
-        case 7: SD_TRY(fn<7>(__VA_ARGS__)); break;         \
-        default: SD_TRY(fn<8>(__VA_ARGS__)); break;        \
-    }
-
-int alloc_grouped(sd_ctx* ctx, sd_grouped_state* st) {
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->coef, sizeof(double) * (size_t)st->n * st->F * st->C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->intercept, sizeof(double) * (size_t)st->n * st->C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * st->C));
-    SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * st->C, ctx->stream));
-    return SD_OK;
+std::vector<sd_buf> grouped_bufs(const sd_grouped_state* st) {
+    const size_t plane = (size_t)st->n * st->C;
+    return {sd_buf_of(st->coef, plane * st->F), sd_buf_of(st->intercept, plane), sd_buf_of(st->status, (size_t)st->C, true)};
 }
 
-template <typename Tv>
-int upload(sd_ctx* ctx, sd_scratch& s, const std::vector<Tv>& v) {
-    SD_HIP(s.alloc(ctx, sizeof(Tv) * std::max<size_t>(v.size(), 1)));
-    SD_HIP(hipMemcpyAsync(s.p, v.data(), sizeof(Tv) * v.size(), hipMemcpyHostToDevice, ctx->stream));
-    return SD_OK;
+sd_grouped_state* new_grouped(sd_ctx* ctx, int n, int F, int64_t C, int window) {
+    sd_grouped_state* st = new sd_grouped_state();
+    st->ctx = ctx; st->n = n; st->F = F; st->C = C; st->window = window;
+    return st;
 }
 
 // the time steps of a predict call ordered by key; refuses a key without a fitted model, the smallest one first
@@ -291,18 +276,7 @@ int predict_table(const sd_grouped_state* st, const int32_t* key, int64_t Tq, Gr
 
 extern "C" {
 
-int sd_grouped_state_destroy(sd_grouped_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    if (st->coef) sd_pool_release(st->ctx, st->coef);
-    if (st->intercept) sd_pool_release(st->ctx, st->intercept);
-    if (st->status) sd_pool_release(st->ctx, st->status);
-    delete st;
-    return SD_OK;
-}
+int sd_grouped_state_destroy(sd_grouped_state* st) { return sd_state_destroy(st, grouped_bufs); }
 
 int sd_grouped_state_info(const sd_grouped_state* st, int* n, int* F, int64_t* C, int* window) {
     SD_CHECK_ARG(st, "state is NULL");
@@ -317,18 +291,9 @@ int sd_grouped_state_export(const sd_grouped_state* st, double* coef, double* in
     SD_CHECK_ARG(st, "state is NULL");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    const size_t plane = (size_t)st->n * st->C;
-    if (coef) SD_HIP(hipMemcpyAsync(coef, st->coef, sizeof(double) * plane * st->F, hipMemcpyDeviceToHost, ctx->stream));
-    if (intercept) SD_HIP(hipMemcpyAsync(intercept, st->intercept, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream));
+    SD_TRY(sd_state_copy(ctx, grouped_bufs(st), {coef, intercept}, hipMemcpyDeviceToHost));
     if (fitted) std::copy(st->fitted.begin(), st->fitted.end(), fitted);
-    if (cell_status) {
-        std::vector<int32_t> bits(st->C);
-        SD_HIP(hipMemcpyAsync(bits.data(), st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(bits[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 // fitted numbers -> device state (pickling, checkpoint / resume)
@@ -338,28 +303,15 @@ int sd_grouped_state_import(sd_ctx* ctx, int n, int F, int64_t C, int window, co
     SD_CHECK_ARG(n > 0 && C > 0 && F >= 1 && F <= kMaxF && window >= 0, "sd_grouped_state_import: bad sizes");
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
-    sd_grouped_state* st = new sd_grouped_state();
-    st->ctx = ctx; st->n = n; st->F = F; st->C = C; st->window = window;
+    sd_grouped_state* st = new_grouped(ctx, n, F, C, window);
     st->fitted.assign(fitted, fitted + n);
-    std::vector<int32_t> bits(C, 0);
-    if (cell_status)
-        for (int64_t c = 0; c < C; ++c) bits[c] = sd_internal_status(cell_status[c]);
-    auto body = [&]() -> int {
-        SD_TRY(alloc_grouped(ctx, st));
-        const size_t plane = (size_t)n * C;
-        SD_HIP(hipMemcpyAsync(st->coef, coef, sizeof(double) * plane * F, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->intercept, intercept, sizeof(double) * plane, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->status, bits.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
+    const std::vector<int32_t> bits = sd_status_bits(cell_status, C);
+    return sd_state_build(st, sd_grouped_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, grouped_bufs(st)));
+        SD_TRY(sd_state_copy(ctx, grouped_bufs(st), {coef, intercept, bits.data()}, hipMemcpyHostToDevice));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_grouped_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_grouped_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int F, int64_t C,
@@ -375,41 +327,31 @@ int sd_grouped_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, in
     const GroupedWindowTile tile = grouped_window_tile(F, n, window, ctx->lds_max);
     SD_CHECK_ARG(tile.cells > 0, "sd_grouped_fit: the statistics of a window=%d, F=%d group do not fit in LDS", window, F);
     SD_HIP(hipSetDevice(ctx->device));
-    sd_grouped_state* st = new sd_grouped_state();
-    st->ctx = ctx; st->n = n; st->F = F; st->C = C; st->window = window;
+    sd_grouped_state* st = new_grouped(ctx, n, F, C, window);
     st->fitted = grouped_fitted(tab.cnt, window);
-    auto body = [&]() -> int {
-        SD_TRY(alloc_grouped(ctx, st));
+    return sd_state_build(st, sd_grouped_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, grouped_bufs(st)));
         sd_scratch d_order, d_off, d_cnt, d_part;
         SD_TRY(upload(ctx, d_order, tab.order));
         SD_TRY(upload(ctx, d_off, tab.off));
         SD_TRY(upload(ctx, d_cnt, tab.cnt));
         SD_HIP(d_part.alloc(ctx, sizeof(double) * (size_t)grouped_nstat(F) * n * C));
-        GROUPED_DISPATCH_F(F, launch_fit, ctx, X_dev, y_dev, ld, st, tile, d_order.as<const int32_t>(), d_off.as<const int64_t>(),
-                           d_cnt.as<const double>(), d_part.as<double>());
+        SD_DISPATCH_F(F, launch_fit, ctx, X_dev, y_dev, ld, st, tile, d_order.as<const int32_t>(), d_off.as<const int64_t>(),
+                      d_cnt.as<const double>(), d_part.as<double>());
         SD_HIP(hipStreamSynchronize(ctx->stream));  // (the scratch tables go back to the cache on return)
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_grouped_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_grouped_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int F, int64_t C, const int32_t* key, int n, int window,
                    sd_grouped_state** out) {
     SD_CHECK_ARG(ctx && X && y && out, "sd_grouped_fit: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0 && F >= 1, "sd_grouped_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    SD_HIP(dX.alloc(ctx, sizeof(double) * (size_t)T * F * C));
-    SD_HIP(dy.alloc(ctx, sizeof(double) * (size_t)T * C));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, sizeof(double) * (size_t)T * F * C));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, sizeof(double) * (size_t)T * C));
-    return sd_grouped_fit_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, F, C, key, n, window, out);
+    const size_t bytes = sizeof(double) * (size_t)T * C;
+    const sd_host_field f[] = {sd_in(X, bytes * F), sd_in(y, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_grouped_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, F, C, key, n, window, out);
+    });
 }
 
 int sd_grouped_predict_dev(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, const int32_t* key,
@@ -419,23 +361,13 @@ int sd_grouped_predict_dev(sd_ctx* ctx, const sd_grouped_state* st, const double
     GroupedKeyTable tab;
     SD_TRY(predict_table(st, key, Tq, &tab));
     SD_HIP(hipSetDevice(ctx->device));
-    const int64_t C = st->C;
     sd_scratch status_p, d_order, d_off;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, st->C));
     SD_TRY(upload(ctx, d_order, tab.order));
     SD_TRY(upload(ctx, d_off, tab.off));
-    GROUPED_DISPATCH_F(st->F, launch_predict, ctx, st, Xq_dev, ld, d_order.as<const int32_t>(), d_off.as<const int64_t>(),
-                       status_p.as<int32_t>(), out_dev, ld_out);
-    if (cell_status) {
-        std::vector<int32_t> a(C), b(C);
-        SD_HIP(hipMemcpyAsync(a.data(), st->status, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipMemcpyAsync(b.data(), status_p.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < C; ++c) cell_status[c] = sd_public_status(a[c] | b[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    SD_DISPATCH_F(st->F, launch_predict, ctx, st, Xq_dev, ld, d_order.as<const int32_t>(), d_off.as<const int64_t>(),
+                  status_p.as<int32_t>(), out_dev, ld_out);
+    return sd_status_fold(ctx, st->status, status_p.as<int32_t>(), st->C, cell_status);
 }
 
 int sd_grouped_predict(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq, int64_t Tq, const int32_t* key, double* out,
@@ -444,16 +376,11 @@ int sd_grouped_predict(sd_ctx* ctx, const sd_grouped_state* st, const double* Xq
     SD_CHECK_ARG(Tq > 0, "sd_grouped_predict: bad sizes");
     GroupedKeyTable tab;
     SD_TRY(predict_table(st, key, Tq, &tab));  // (before the upload: a missing key costs no transfer)
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
-    const size_t in_bytes = sizeof(double) * (size_t)Tq * st->F * st->C, out_bytes = sizeof(double) * (size_t)Tq * st->C;
-    SD_HIP(dX.alloc(ctx, in_bytes));
-    SD_HIP(dout.alloc(ctx, out_bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xq, in_bytes));
-    SD_TRY(sd_grouped_predict_dev(ctx, st, dX.as<double>(), st->C, Tq, key, dout.as<double>(), st->C, cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, out_bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const size_t bytes = sizeof(double) * (size_t)Tq * st->C;
+    const sd_host_field f[] = {sd_in(Xq, bytes * st->F), sd_out(out, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_grouped_predict_dev(ctx, st, (const double*)d[0], st->C, Tq, key, (double*)d[1], st->C, cell_status);
+    });
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "sd_internal.h"
 #include "sd_lsq.h"
+#include "sd_state.h"
 
 struct sd_linreg_state {
     sd_ctx* ctx = nullptr;
@@ -363,15 +364,6 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_predict_kernel(const 
     if (active && bad) atomicOr(&status[c], SDI_NONFINITE);
 }
 
-__global__ void __launch_bounds__(256) linreg_status_public_kernel(const int32_t* __restrict__ a, const int32_t* __restrict__ b, int64_t C,
-                                                                   int32_t* __restrict__ outp) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < C) {
-        const int32_t bits = a[c] | (b ? b[c] : 0);
-        outp[c] = sd_public_status(bits);
-    }
-}
-
 template <int F>
 int launch_fit(sd_ctx* ctx, const double* X, const double* y, int64_t ld, sd_linreg_state* st) {
     const dim3 grid((unsigned)((st->C + kCells - 1) / kCells));
@@ -393,37 +385,30 @@ int launch_predict(sd_ctx* ctx, const sd_linreg_state* st, const double* Xq, int
     return SD_OK;
 }
 
-#define LINREG_DISPATCH_F(F, fn, ...)                      \
-    switch (F) {                                           \
-        case 1: SD_TRY(fn<1>(__VA_ARGS__)); break;         \
-        case 2: SD_TRY(fn<2>(__VA_ARGS__)); break;         \
-        case 3: SD_TRY(fn<3>(__VA_ARGS__)); break;         \
-        case 4: SD_TRY(fn<4>(__VA_ARGS__)); break;         \
-        case 5: SD_TRY(fn<5>(__VA_ARGS__)); break;         \
-        case 6: SD_TRY(fn<6>(__VA_ARGS__)); break;         \
-        case 7: SD_TRY(fn<7>(__VA_ARGS__)); break;         \
-        default: SD_TRY(fn<8>(__VA_ARGS__)); break;        \
+// the device buffers of a state; logit and thresh_off exist with a threshold only
+std::vector<sd_buf> linreg_bufs(const sd_linreg_state* st) {
+    const size_t C = (size_t)st->C, F = (size_t)st->F;
+    std::vector<sd_buf> b = {sd_buf_of(st->coef, F * C), sd_buf_of(st->intercept, C), sd_buf_of(st->rmse, C), sd_buf_of(st->status, C, true)};
+    if (st->has_thresh) {
+        b.push_back(sd_buf_of(st->logit, (F + 1) * C, true));
+        b.push_back(sd_buf_of(st->thresh_off, C, true));
     }
+    return b;
+}
+
+sd_linreg_state* new_linreg(sd_ctx* ctx, int64_t T, int F, int64_t C, int has_thresh, double thresh) {
+    sd_linreg_state* st = new sd_linreg_state();
+    st->ctx = ctx; st->T = T; st->F = F; st->C = C;
+    st->has_thresh = has_thresh;
+    st->thresh = thresh;
+    return st;
+}
 
 }  // namespace
 
 extern "C" {
 
-int sd_linreg_state_destroy(sd_linreg_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    sd_pool_release(st->ctx, st->coef);
-    sd_pool_release(st->ctx, st->intercept);
-    sd_pool_release(st->ctx, st->rmse);
-    sd_pool_release(st->ctx, st->status);
-    if (st->logit) sd_pool_release(st->ctx, st->logit);
-    if (st->thresh_off) sd_pool_release(st->ctx, st->thresh_off);
-    delete st;
-    return SD_OK;
-}
+int sd_linreg_state_destroy(sd_linreg_state* st) { return sd_state_destroy(st, linreg_bufs); }
 
 int sd_linreg_state_info(const sd_linreg_state* st, int64_t* T, int* F, int64_t* C) {
     SD_CHECK_ARG(st, "state is NULL");
@@ -438,38 +423,8 @@ int sd_linreg_state_export(const sd_linreg_state* st, double* coef, double* inte
     SD_CHECK_ARG(st, "state is NULL");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    if (coef) SD_HIP(hipMemcpyAsync(coef, st->coef, sizeof(double) * (size_t)st->F * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (intercept) SD_HIP(hipMemcpyAsync(intercept, st->intercept, sizeof(double) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (fit_error) SD_HIP(hipMemcpyAsync(fit_error, st->rmse, sizeof(double) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (logistic && st->logit)
-        SD_HIP(hipMemcpyAsync(logistic, st->logit, sizeof(double) * (size_t)(st->F + 1) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (thresh_dropped && st->thresh_off)
-        SD_HIP(hipMemcpyAsync(thresh_dropped, st->thresh_off, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (cell_status) {
-        std::vector<int32_t> bits(st->C);
-        SD_HIP(hipMemcpyAsync(bits.data(), st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(bits[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
-}
-
-static int alloc_linreg(sd_ctx* ctx, sd_linreg_state* st) {
-    const int F = st->F;
-    const int64_t C = st->C;
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->coef, sizeof(double) * (size_t)F * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->intercept, sizeof(double) * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->rmse, sizeof(double) * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * C, ctx->stream));
-    if (st->has_thresh) {
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->logit, sizeof(double) * (size_t)(F + 1) * C));
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->thresh_off, sizeof(int32_t) * C));
-        SD_HIP(hipMemsetAsync(st->logit, 0, sizeof(double) * (size_t)(F + 1) * C, ctx->stream));
-        SD_HIP(hipMemsetAsync(st->thresh_off, 0, sizeof(int32_t) * C, ctx->stream));
-    }
-    return SD_OK;
+    SD_TRY(sd_state_copy(ctx, linreg_bufs(st), {coef, intercept, fit_error, nullptr, logistic, thresh_dropped}, hipMemcpyDeviceToHost));
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 // fitted numbers -> device state (pickling, checkpoint / resume): logistic == NULL for a model without a threshold
@@ -480,32 +435,14 @@ int sd_linreg_state_import(sd_ctx* ctx, int64_t T, int F, int64_t C, const doubl
     SD_CHECK_ARG((logistic == nullptr) == (thresh_dropped == nullptr), "sd_linreg_state_import: logistic and thresh_dropped go together");
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
-    sd_linreg_state* st = new sd_linreg_state();
-    st->ctx = ctx; st->T = T; st->F = F; st->C = C;
-    st->has_thresh = logistic != nullptr;
-    std::vector<int32_t> bits(C, 0);
-    if (cell_status)
-        for (int64_t c = 0; c < C; ++c) bits[c] = sd_internal_status(cell_status[c]);
-    auto body = [&]() -> int {
-        SD_TRY(alloc_linreg(ctx, st));
-        SD_HIP(hipMemcpyAsync(st->coef, coef, sizeof(double) * (size_t)F * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->intercept, intercept, sizeof(double) * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->rmse, fit_error, sizeof(double) * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->status, bits.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
-        if (logistic) {
-            SD_HIP(hipMemcpyAsync(st->logit, logistic, sizeof(double) * (size_t)(F + 1) * C, hipMemcpyHostToDevice, ctx->stream));
-            SD_HIP(hipMemcpyAsync(st->thresh_off, thresh_dropped, sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
-        }
+    sd_linreg_state* st = new_linreg(ctx, T, F, C, logistic != nullptr, 0.0);
+    const std::vector<int32_t> bits = sd_status_bits(cell_status, C);
+    return sd_state_build(st, sd_linreg_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, linreg_bufs(st)));
+        SD_TRY(sd_state_copy(ctx, linreg_bufs(st), {coef, intercept, fit_error, bits.data(), logistic, thresh_dropped}, hipMemcpyHostToDevice));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_linreg_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_linreg_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int F, int64_t C,
@@ -515,39 +452,24 @@ int sd_linreg_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
     SD_CHECK_ARG(F >= 1 && F <= kMaxF, "sd_linreg_fit: F=%d outside [1,%d]", F, kMaxF);
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
-    sd_linreg_state* st = new sd_linreg_state();
-    st->ctx = ctx;
-    st->T = T;
-    st->F = F;
-    st->C = C;
-    st->has_thresh = has_thresh ? 1 : 0;
-    st->thresh = thresh;
-    auto body = [&]() -> int {
-        SD_TRY(alloc_linreg(ctx, st));
-        LINREG_DISPATCH_F(F, launch_fit, ctx, X_dev, y_dev, ld, st);
+    sd_linreg_state* st = new_linreg(ctx, T, F, C, has_thresh ? 1 : 0, thresh);
+    return sd_state_build(st, sd_linreg_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, linreg_bufs(st)));
+        SD_DISPATCH_F(F, launch_fit, ctx, X_dev, y_dev, ld, st);
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_linreg_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_linreg_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int F, int64_t C, int has_thresh, double thresh,
                   sd_linreg_state** out) {
     SD_CHECK_ARG(ctx && X && y && out, "sd_linreg_fit: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0 && F >= 1, "sd_linreg_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    SD_HIP(dX.alloc(ctx, sizeof(double) * (size_t)T * F * C));
-    SD_HIP(dy.alloc(ctx, sizeof(double) * (size_t)T * C));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, sizeof(double) * (size_t)T * F * C));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, sizeof(double) * (size_t)T * C));
-    return sd_linreg_fit_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, F, C, has_thresh, thresh, out);
+    const size_t bytes = sizeof(double) * (size_t)T * C;
+    const sd_host_field f[] = {sd_in(X, bytes * F), sd_in(y, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_linreg_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, F, C, has_thresh, thresh, out);
+    });
 }
 
 int sd_linreg_predict_dev(sd_ctx* ctx, const sd_linreg_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, double* out_dev,
@@ -555,34 +477,20 @@ int sd_linreg_predict_dev(sd_ctx* ctx, const sd_linreg_state* st, const double* 
     SD_CHECK_ARG(ctx && st && Xq_dev && out_dev, "sd_linreg_predict: NULL argument");
     SD_CHECK_ARG(Tq > 0 && ld >= st->C && ld_out >= st->C, "sd_linreg_predict: bad sizes");
     SD_HIP(hipSetDevice(ctx->device));
-    const int64_t C = st->C;
-    sd_scratch status_p, status_pub;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
-    LINREG_DISPATCH_F(st->F, launch_predict, ctx, st, Xq_dev, ld, Tq, status_p.as<int32_t>(), out_dev, ld_out);
-    if (cell_status) {
-        SD_HIP(status_pub.alloc(ctx, sizeof(int32_t) * C));
-        SD_LAUNCH(ctx, "linreg_status_public_kernel", linreg_status_public_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0,
-                  (const int32_t*)st->status, (const int32_t*)status_p.p, C, status_pub.as<int32_t>());
-        SD_HIP(hipMemcpyAsync(cell_status, status_pub.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    sd_scratch status_p;
+    SD_TRY(sd_status_scratch(ctx, status_p, st->C));
+    SD_DISPATCH_F(st->F, launch_predict, ctx, st, Xq_dev, ld, Tq, status_p.as<int32_t>(), out_dev, ld_out);
+    return sd_status_fold(ctx, st->status, status_p.as<int32_t>(), st->C, cell_status);
 }
 
 int sd_linreg_predict(sd_ctx* ctx, const sd_linreg_state* st, const double* Xq, int64_t Tq, double* out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xq && out, "sd_linreg_predict: NULL argument");
     SD_CHECK_ARG(Tq > 0, "sd_linreg_predict: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
-    const size_t in_bytes = sizeof(double) * (size_t)Tq * st->F * st->C, out_bytes = sizeof(double) * (size_t)Tq * 3 * st->C;
-    SD_HIP(dX.alloc(ctx, in_bytes));
-    SD_HIP(dout.alloc(ctx, out_bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xq, in_bytes));
-    SD_TRY(sd_linreg_predict_dev(ctx, st, dX.as<double>(), st->C, Tq, dout.as<double>(), st->C, cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, out_bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const size_t bytes = sizeof(double) * (size_t)Tq * st->C;
+    const sd_host_field f[] = {sd_in(Xq, bytes * st->F), sd_out(out, bytes * 3)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_linreg_predict_dev(ctx, st, (const double*)d[0], st->C, Tq, (double*)d[1], st->C, cell_status);
+    });
 }
 
 }  // extern "C"

@@ -7,6 +7,23 @@ namespace sdlsq {
 
 constexpr int kMaxF = 8;
 
+}  // namespace sdlsq
+
+// fn<F>(args) for the feature count of a call, F in [1, kMaxF] (checked by the entry points); returns on failure
+#define SD_DISPATCH_F(F, fn, ...)                          \
+    switch (F) {                                           \
+        case 1: SD_TRY(fn<1>(__VA_ARGS__)); break;         \
+        case 2: SD_TRY(fn<2>(__VA_ARGS__)); break;         \
+        case 3: SD_TRY(fn<3>(__VA_ARGS__)); break;         \
+        case 4: SD_TRY(fn<4>(__VA_ARGS__)); break;         \
+        case 5: SD_TRY(fn<5>(__VA_ARGS__)); break;         \
+        case 6: SD_TRY(fn<6>(__VA_ARGS__)); break;         \
+        case 7: SD_TRY(fn<7>(__VA_ARGS__)); break;         \
+        default: SD_TRY(fn<8>(__VA_ARGS__)); break;        \
+    }
+
+namespace sdlsq {
+
 // A = [ S | b ]: S the symmetric F x F matrix of centred cross products, b = column F.  coef = pinv(S) b like the
 // lstsq inside sklearn's LinearRegression: eigen-decomposition S = V diag(lam) V^T by cyclic Jacobi rotations, coef =
 // sum over the non-null directions of v (v . b) / lam.  Under-determined and collinear designs then give the

@@ -22,6 +22,7 @@
 
 #include "sd_internal.h"
 #include "sd_sortnet.h"
+#include "sd_state.h"
 #include "sd_wave.h"
 
 namespace {
@@ -808,8 +809,7 @@ struct qm_staging {
 int stage_in(sd_ctx* ctx, const double* X_dev, int64_t ld, int64_t Tp, int64_t C, qm_staging* s) {
     SD_HIP(s->qc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
     SD_HIP(s->oc.alloc(ctx, sizeof(double) * (size_t)Tp * C));
-    SD_HIP(s->status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(s->status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, s->status_p, C));
     return launch_transpose(ctx, X_dev, ld, Tp, C, s->qc.as<double>(), s->status_p.as<int32_t>(), 0);
 }
 int stage_out(sd_ctx* ctx, const sd_qm_state* st, const qm_staging& s, int64_t Tp, double* out_dev, int64_t ld_out, int32_t* cell_status) {
@@ -828,22 +828,24 @@ int stage_out(sd_ctx* ctx, const sd_qm_state* st, const qm_staging& s, int64_t T
     return SD_OK;
 }
 
-// The host-buffer form of predict / Cunnane: upload the new series, run the resident call, download the result
+// The host-buffer form of predict / Cunnane: one series up, one of the same size down
 template <class Call>
-int with_device_copies(sd_ctx* ctx, const sd_qm_state* st, const char* op, const double* X, int64_t Tp, double* out, Call call) {
+int qm_with_device_copies(sd_ctx* ctx, const sd_qm_state* st, const char* op, const double* X, int64_t Tp, double* out, Call call) {
     SD_CHECK_ARG(ctx && st && X && out, "%s: NULL argument", op);
     SD_CHECK_ARG(Tp > 0, "%s: bad sizes", op);
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
     const size_t bytes = sizeof(double) * (size_t)Tp * st->C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    SD_TRY(call(dX.as<double>(), dout.as<double>()));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const sd_host_field f[] = {sd_in(X, bytes), sd_out(out, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) { return call((const double*)d[0], (double*)d[1]); });
 }
+
+// the device buffers of a state; ys, last, exists when the fit had a y (with_y: asked at allocation, read off the state afterwards)
+std::vector<sd_buf> qm_bufs(const sd_qm_state* st, bool with_y) {
+    const size_t n = (size_t)st->T * st->C;
+    std::vector<sd_buf> b = {sd_buf_of(st->xs, n), sd_buf_of(st->status, (size_t)st->C, true)};
+    if (with_y) b.push_back(sd_buf_of(st->ys, n));
+    return b;
+}
+std::vector<sd_buf> qm_bufs(const sd_qm_state* st) { return qm_bufs(st, st->ys != nullptr); }
 
 QmCall qm_call(QmOp op, const sd_ctx* ctx, int64_t T, int64_t Tp, int64_t C, int64_t ld, int64_t ld_out, bool has_y) {
     QmCall c;
@@ -861,16 +863,7 @@ QmCall qm_call(QmOp op, const sd_ctx* ctx, int64_t T, int64_t Tp, int64_t C, int
 extern "C" {
 
 int sd_qm_state_destroy(sd_qm_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    sd_pool_release(st->ctx, st->xs);
-    sd_pool_release(st->ctx, st->ys);
-    sd_pool_release(st->ctx, st->status);
-    delete st;
-    return SD_OK;
+    return sd_state_destroy(st, [](const sd_qm_state* s) { return qm_bufs(s); });
 }
 
 int sd_qm_state_info(const sd_qm_state* st, int64_t* T, int64_t* C) {
@@ -882,20 +875,11 @@ int sd_qm_state_info(const sd_qm_state* st, int64_t* T, int64_t* C) {
 
 int sd_qm_state_export(const sd_qm_state* st, double* x_sorted, double* y_sorted, int32_t* cell_status) {
     SD_CHECK_ARG(st, "state is NULL");
+    SD_CHECK_ARG(!y_sorted || st->ys, "sd_qm_state_export: the state was fitted without y");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * (size_t)st->T * st->C;
-    if (x_sorted) SD_HIP(hipMemcpyAsync(x_sorted, st->xs, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SD_CHECK_ARG(!y_sorted || st->ys, "sd_qm_state_export: the state was fitted without y");
-    if (y_sorted) SD_HIP(hipMemcpyAsync(y_sorted, st->ys, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (cell_status) {
-        std::vector<int32_t> bits(st->C);
-        SD_HIP(hipMemcpyAsync(bits.data(), st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(bits[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    SD_TRY(sd_state_copy(ctx, qm_bufs(st), {x_sorted, nullptr, y_sorted}, hipMemcpyDeviceToHost));
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 int sd_qm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, sd_qm_state** out) {
@@ -908,40 +892,25 @@ int sd_qm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t
     st->ctx = ctx;
     st->T = T;
     st->C = C;
-    auto body = [&]() -> int {
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->xs, sizeof(double) * (size_t)T * C));
-        if (y_dev) SD_HIP(sd_pool_malloc(ctx, (void**)&st->ys, sizeof(double) * (size_t)T * C));
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * C));
-        SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * C, ctx->stream));
+    return sd_state_build(st, sd_qm_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, qm_bufs(st, y_dev != nullptr)));
         sd_scratch runs;
         if (pl.tiled) SD_HIP(runs.alloc(ctx, pl.runs_bytes));
         SD_TRY(sort_field(ctx, pl, X_dev, ld, T, C, st->xs, st->status, 1, runs.as<double>()));
         if (y_dev) SD_TRY(sort_field(ctx, pl, y_dev, ld, T, C, st->ys, st->status, 0, runs.as<double>()));
         SD_HIP(hipStreamSynchronize(ctx->stream));  // (the runs go back to the block cache at scope exit)
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_qm_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_qm_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t C, sd_qm_state** out) {
     SD_CHECK_ARG(ctx && X && out, "sd_qm_fit: NULL argument");
     SD_CHECK_ARG(T >= 2 && C > 0, "sd_qm_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
     const size_t bytes = sizeof(double) * (size_t)T * C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    if (y) {
-        SD_HIP(dy.alloc(ctx, bytes));
-        SD_TRY(sd_copy_h2d(ctx, dy.p, y, bytes));
-    }
-    return sd_qm_fit_dev(ctx, dX.as<double>(), y ? dy.as<double>() : nullptr, C, T, C, out);
+    const sd_host_field f[] = {sd_in(X, bytes), sd_in(y, bytes)};  // (y may be NULL)
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_qm_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, C, out);
+    });
 }
 
 int sd_qm_predict_dev(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapolate, int n_endpoints, const double* Xp_dev, int64_t ld,
@@ -1007,7 +976,7 @@ int sd_qm_predict_dev(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapo
 
 int sd_qm_predict(sd_ctx* ctx, const sd_qm_state* st, int model, int extrapolate, int n_endpoints, const double* Xp, int64_t Tp, double* out,
                   int32_t* cell_status) {
-    return with_device_copies(ctx, st, "sd_qm_predict", Xp, Tp, out, [&](const double* dX, double* dout) {
+    return qm_with_device_copies(ctx, st, "sd_qm_predict", Xp, Tp, out, [&](const double* dX, double* dout) {
         return sd_qm_predict_dev(ctx, st, model, extrapolate, n_endpoints, dX, st->C, Tp, dout, st->C, cell_status);
     });
 }
@@ -1032,7 +1001,7 @@ int sd_qm_cunnane_dev(sd_ctx* ctx, const sd_qm_state* st, int direction, int ext
 
 int sd_qm_cunnane(sd_ctx* ctx, const sd_qm_state* st, int direction, int extrapolate, int n_endpoints, const double* X, int64_t Tp,
                   double* out, int32_t* cell_status) {
-    return with_device_copies(ctx, st, "sd_qm_cunnane", X, Tp, out, [&](const double* dX, double* dout) {
+    return qm_with_device_copies(ctx, st, "sd_qm_cunnane", X, Tp, out, [&](const double* dX, double* dout) {
         return sd_qm_cunnane_dev(ctx, st, direction, extrapolate, n_endpoints, dX, st->C, Tp, dout, st->C, cell_status);
     });
 }

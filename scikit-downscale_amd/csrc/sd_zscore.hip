@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "sd_internal.h"
+#include "sd_state.h"
 #include "sd_zscore_plan.h"
 
 struct sd_zscore_state {
@@ -215,35 +216,24 @@ __global__ void __launch_bounds__(kCells * kPredSlices) zscore_predict_kernel(
     if (live && bad) atomicOr(&status[c], SDI_NONFINITE);
 }
 
-int alloc_zscore(sd_ctx* ctx, sd_zscore_state* st) {
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->stats, sizeof(double) * ZS_NSTATS * (size_t)st->K * st->C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * st->C));
-    SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * st->C, ctx->stream));
-    return SD_OK;
+std::vector<sd_buf> zscore_bufs(const sd_zscore_state* st) {
+    return {sd_buf_of(st->stats, ZS_NSTATS * (size_t)st->K * st->C), sd_buf_of(st->status, (size_t)st->C, true)};
 }
 
-template <typename Tv>
-int upload(sd_ctx* ctx, sd_scratch& s, const std::vector<Tv>& v) {
-    SD_HIP(s.alloc(ctx, sizeof(Tv) * std::max<size_t>(v.size(), 1)));
-    SD_HIP(hipMemcpyAsync(s.p, v.data(), sizeof(Tv) * v.size(), hipMemcpyHostToDevice, ctx->stream));
-    return SD_OK;
+sd_zscore_state* new_zscore(sd_ctx* ctx, int64_t K, int64_t C, int window_width) {
+    sd_zscore_state* st = new sd_zscore_state();
+    st->ctx = ctx;
+    st->K = K;
+    st->C = C;
+    st->w = window_width;
+    return st;
 }
 
 }  // namespace
 
 extern "C" {
 
-int sd_zscore_state_destroy(sd_zscore_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    if (st->stats) sd_pool_release(st->ctx, st->stats);
-    if (st->status) sd_pool_release(st->ctx, st->status);
-    delete st;
-    return SD_OK;
-}
+int sd_zscore_state_destroy(sd_zscore_state* st) { return sd_state_destroy(st, zscore_bufs); }
 
 int sd_zscore_state_info(const sd_zscore_state* st, int64_t* K, int64_t* C, int* window_width) {
     SD_CHECK_ARG(st, "state is NULL");
@@ -259,15 +249,10 @@ int sd_zscore_state_export(const sd_zscore_state* st, double* x_mean, double* x_
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
     const size_t plane = (size_t)st->K * st->C;
-    double* dst[ZS_NSTATS] = {x_mean, x_std, y_mean, y_std, shift, scale};
+    double* dst[ZS_NSTATS] = {x_mean, x_std, y_mean, y_std, shift, scale};  // (the one buffer holds six planes)
     for (int q = 0; q < ZS_NSTATS; ++q)
         if (dst[q]) SD_HIP(hipMemcpyAsync(dst[q], st->stats + q * plane, sizeof(double) * plane, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<int32_t> bits(st->C);
-    SD_HIP(hipMemcpyAsync(bits.data(), st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    if (cell_status)
-        for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(bits[c]);
-    return SD_OK;
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 int sd_zscore_state_import(sd_ctx* ctx, int64_t K, int64_t C, int window_width, const double* x_mean, const double* x_std,
@@ -277,31 +262,18 @@ int sd_zscore_state_import(sd_ctx* ctx, int64_t K, int64_t C, int window_width, 
     SD_CHECK_ARG(K > 0 && C > 0 && window_width > 0, "sd_zscore_state_import: bad sizes");
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
-    sd_zscore_state* st = new sd_zscore_state();
-    st->ctx = ctx;
-    st->K = K;
-    st->C = C;
-    st->w = window_width;
-    std::vector<int32_t> bits(C, 0);
-    if (cell_status)
-        for (int64_t c = 0; c < C; ++c) bits[c] = sd_internal_status(cell_status[c]);
-    auto body = [&]() -> int {
-        SD_TRY(alloc_zscore(ctx, st));
+    sd_zscore_state* st = new_zscore(ctx, K, C, window_width);
+    const std::vector<int32_t> bits = sd_status_bits(cell_status, C);
+    return sd_state_build(st, sd_zscore_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, zscore_bufs(st)));
         const size_t plane = (size_t)K * C;
         const double* src[ZS_NSTATS] = {x_mean, x_std, y_mean, y_std, shift, scale};
         for (int q = 0; q < ZS_NSTATS; ++q)
             SD_HIP(hipMemcpyAsync(st->stats + q * plane, src[q], sizeof(double) * plane, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->status, bits.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
+        SD_TRY(sd_state_copy(ctx, zscore_bufs(st), {nullptr, bits.data()}, hipMemcpyHostToDevice));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_zscore_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_zscore_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64_t ld, int64_t T, int64_t C, int window_width,
@@ -313,13 +285,9 @@ int sd_zscore_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
     const ZscorePlan plan = zscore_plan(day_idx, year, T, D, window_width);
     if (plan.err != SD_OK) return sd_set_error(plan.err, "%s", plan.msg.c_str());
     SD_HIP(hipSetDevice(ctx->device));
-    sd_zscore_state* st = new sd_zscore_state();
-    st->ctx = ctx;
-    st->K = plan.K;
-    st->C = C;
-    st->w = window_width;
-    auto body = [&]() -> int {
-        SD_TRY(alloc_zscore(ctx, st));
+    sd_zscore_state* st = new_zscore(ctx, plan.K, C, window_width);
+    return sd_state_build(st, sd_zscore_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, zscore_bufs(st)));
         std::vector<double> cnt(plan.cnt.begin(), plan.cnt.end());
         sd_scratch d_order, d_off, d_win, d_cnt, d_part;
         SD_TRY(upload(ctx, d_order, plan.order));
@@ -335,27 +303,18 @@ int sd_zscore_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
                   (const int32_t*)st->status, st->stats);
         SD_HIP(hipStreamSynchronize(ctx->stream));  // (the scratch tables go back to the cache on return)
         return SD_OK;
-    };
-    const int rc = body();
-    if (rc != SD_OK) {
-        sd_zscore_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_zscore_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int64_t C, int window_width, const int32_t* day_idx,
                   const int32_t* year, int D, sd_zscore_state** out) {
     SD_CHECK_ARG(ctx && X && y && out, "sd_zscore_fit: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0, "sd_zscore_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    SD_HIP(dX.alloc(ctx, sizeof(double) * (size_t)T * C));
-    SD_HIP(dy.alloc(ctx, sizeof(double) * (size_t)T * C));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, sizeof(double) * (size_t)T * C));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, sizeof(double) * (size_t)T * C));
-    return sd_zscore_fit_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, C, window_width, day_idx, year, D, out);
+    const size_t bytes = sizeof(double) * (size_t)T * C;
+    const sd_host_field f[] = {sd_in(X, bytes), sd_in(y, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_zscore_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, C, window_width, day_idx, year, D, out);
+    });
 }
 
 int sd_zscore_predict_dev(sd_ctx* ctx, const sd_zscore_state* st, const double* Xp_dev, int64_t ld, int64_t Tp, double* out_dev,
@@ -366,48 +325,27 @@ int sd_zscore_predict_dev(sd_ctx* ctx, const sd_zscore_state* st, const double* 
     SD_HIP(hipSetDevice(ctx->device));
     const int64_t C = st->C;
     sd_scratch status_p;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     const size_t plane = (size_t)st->K * C;
     const dim3 grid((unsigned)((C + kCells - 1) / kCells), (unsigned)((Tp + kPredSlices * kChunk - 1) / (kPredSlices * kChunk)));
     SD_LAUNCH(ctx, "zscore_predict_kernel", zscore_predict_kernel, grid, dim3(kCells * kPredSlices), 0, Xp_dev, ld, Tp, C, st->w,
               zscore_expand_period(Tp), (const double*)(st->stats + ZS_SHIFT * plane), (const double*)(st->stats + ZS_SCALE * plane),
               (const int32_t*)st->status, status_p.as<int32_t>(), out_dev, ld_out, meani, stdi, meanf, stdf);
-    if (cell_status) {
-        std::vector<int32_t> a(C), b(C);
-        SD_HIP(hipMemcpyAsync(a.data(), st->status, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipMemcpyAsync(b.data(), status_p.p, sizeof(int32_t) * C, hipMemcpyDeviceToHost, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        for (int64_t c = 0; c < C; ++c) cell_status[c] = sd_public_status(a[c] | b[c]);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return sd_status_fold(ctx, st->status, status_p.as<int32_t>(), C, cell_status);
 }
 
 int sd_zscore_predict(sd_ctx* ctx, const sd_zscore_state* st, const double* Xp, int64_t Tp, double* out, double* meani, double* stdi,
                       double* meanf, double* stdf, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xp && out, "sd_zscore_predict: NULL argument");
     SD_CHECK_ARG(Tp > 0, "sd_zscore_predict: bad sizes");
-    if (!zscore_expand_ok(Tp, (int)st->K)) return sd_set_error(SD_ERR_INVALID, "positional indexers are out-of-bounds");
-    SD_HIP(hipSetDevice(ctx->device));
+    if (!zscore_expand_ok(Tp, (int)st->K)) return sd_set_error(SD_ERR_INVALID, "positional indexers are out-of-bounds");  // (before the upload)
     const size_t bytes = sizeof(double) * (size_t)Tp * st->C;
-    double* host[4] = {meani, stdi, meanf, stdf};
-    sd_scratch dX, dout, dstat[4];
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int q = 0; q < 4; ++q)
-        if (host[q]) {
-            SD_HIP(dstat[q].alloc(ctx, bytes));
-            dev[q] = dstat[q].as<double>();
-        }
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xp, bytes));
-    SD_TRY(sd_zscore_predict_dev(ctx, st, dX.as<double>(), st->C, Tp, dout.as<double>(), st->C, dev[0], dev[1], dev[2], dev[3], cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    for (int q = 0; q < 4; ++q)
-        if (host[q]) SD_TRY(sd_copy_d2h(ctx, host[q], dev[q], bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const sd_host_field f[] = {sd_in(Xp, bytes), sd_out(out, bytes), sd_out(meani, bytes), sd_out(stdi, bytes), sd_out(meanf, bytes),
+                               sd_out(stdf, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_zscore_predict_dev(ctx, st, (const double*)d[0], st->C, Tp, (double*)d[1], st->C, (double*)d[2], (double*)d[3],
+                                     (double*)d[4], (double*)d[5], cell_status);
+    });
 }
 
 }  // extern "C"
