@@ -92,6 +92,10 @@ extern "C" {
 #define SD_EXTRAP_1TO1 4     /* regressors only: samples beyond the fitted X range keep their offset to it (quantile.py:277-310) */
 
 /* synthetic field kinds (sd_synth_fill) */
+/* sd_regrid_create: interpolation method */
+#define SD_REGRID_LINEAR 0  /* interp_like(method='linear'): bilinear on a rectilinear grid, one dimension after the other */
+#define SD_REGRID_NEAREST 1 /* method='nearest': a midpoint goes to the lower neighbour */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -103,6 +107,7 @@ typedef struct sd_linreg_state sd_linreg_state;
 typedef struct sd_zscore_state sd_zscore_state;
 typedef struct sd_grouped_state sd_grouped_state;
 typedef struct sd_arrm_state sd_arrm_state;
+typedef struct sd_regrid sd_regrid;
 typedef struct sd_comm sd_comm;
 #define SD_COMM_ID_BYTES 128 /* RCCL's ncclUniqueId */
 
@@ -373,6 +378,26 @@ int sd_arrm_state_export(const sd_arrm_state* st, double* breaks, int32_t* break
 int sd_arrm_state_import(sd_ctx* ctx, int B, int64_t C, int64_t T, const double* breaks, const int32_t* break_index, const double* beta,
                          const double* ssr, const int32_t* cell_status, sd_arrm_state** out);
 int sd_arrm_state_destroy(sd_arrm_state* st);
+
+/* ---- regridding: GridArray.interp_like (xarray's interp_like with 1-D coordinates) -------------------------
+ * A [T, ny, nx] field on the rectilinear grid (src_y [ny], src_x [nx]) is interpolated onto the grid (dst_y [Ny], dst_x [Nx]); the
+ * result is a [T, C] field, C = Ny * Nx, cells fastest, rows ld_out >= C elements apart: what the fit / predict entry points take.
+ * Per dimension the rule of scipy.interpolate.interp1d(bounds_error=False, fill_value=nan, assume_sorted=False), the first spatial
+ * dimension (y) before the second: bracket hi = clip(searchsorted(x ascending, xn, 'left'), 1, n - 1), lo = hi - 1, value
+ * (v[hi] - v[lo]) / (x[hi] - x[lo]) * (xn - x[lo]) + v[lo]; a target on node k >= 1 uses the interval below it; NaN outside the
+ * source range; a NaN node of the bracket gives NaN also at weight 0.  SD_REGRID_NEAREST: the nearest node, a midpoint to the lower
+ * one, NaN outside the range.  Source coordinates ascend or descend strictly, target coordinates come in any order; a coordinate
+ * that is NaN, a source coordinate that is not strictly monotonic and a source dimension of length 1 are SD_ERR_INVALID.
+ * sd_regrid_create builds the two separable tables (Ny + Nx entries) and uploads them; a sd_regrid serves any number of calls.
+ * src: float64, or float32 with src_is_f32 != 0 (widened in the kernel: the values are those of the widened source). */
+int sd_regrid_create(sd_ctx* ctx, int method, int64_t ny, int64_t nx, const double* src_y, const double* src_x, int64_t Ny, int64_t Nx,
+                     const double* dst_y, const double* dst_x, sd_regrid** out);
+int sd_regrid_destroy(sd_regrid* rg);
+int sd_regrid_info(const sd_regrid* rg, int* method, int64_t* ny, int64_t* nx, int64_t* Ny, int64_t* Nx);
+int sd_regrid_apply_dev(sd_ctx* ctx, const sd_regrid* rg, const void* src_dev, int src_is_f32, int64_t T, double* out_dev,
+                        int64_t ld_out);
+/* host buffers: src [T, ny, nx], out [T, Ny * Nx] */
+int sd_regrid_apply(sd_ctx* ctx, const sd_regrid* rg, const void* src_host, int src_is_f32, int64_t T, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

@@ -9,6 +9,7 @@ from .core import GridArray, GridDataset, PointWiseDownscaler
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
 from .grouping import GroupedGridModel, GroupedRegressor
+from .regrid import InterpolatedGridArray, Regridder
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -44,5 +45,7 @@ __all__ = [
     "PiecewiseLinearRegression",
     "ArrmGridModel",
     "arrm_breakpoints",
+    "Regridder",
+    "InterpolatedGridArray",
 ]
 __version__ = "0.1.0"

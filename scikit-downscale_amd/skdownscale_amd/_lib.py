@@ -23,6 +23,7 @@ QM_REGRESSOR, QM_EDCDF_DIFFERENCE, QM_EDCDF_RATIO = 0, 1, 2
 CUNNANE_FORWARD, CUNNANE_INVERSE = 0, 1
 EXTRAP_CODES = {None: 0, "1to1": 0, "min": 1, "max": 2, "both": 3}  # SD_EXTRAP_* (CunnaneTransformer: '1to1' clamps like None)
 QM_EXTRAP_CODES = {None: 0, "min": 1, "max": 2, "both": 3, "1to1": 4}  # regressors (sd_qm_predict)
+REGRID_METHODS = {"linear": 0, "nearest": 1}  # SD_REGRID_*
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -122,6 +123,11 @@ SIGNATURES = {
     "sd_qm_state_info": [_p, C.POINTER(_i64), C.POINTER(_i64)],
     "sd_qm_state_export": [_p, _p, _p, _p],
     "sd_qm_state_destroy": [_p],
+    "sd_regrid_create": [_p, _int, _i64, _i64, _p, _p, _i64, _i64, _p, _p, C.POINTER(_p)],
+    "sd_regrid_destroy": [_p],
+    "sd_regrid_info": [_p, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "sd_regrid_apply_dev": [_p, _p, _p, _int, _i64, _p, _i64],
+    "sd_regrid_apply": [_p, _p, _p, _int, _i64, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

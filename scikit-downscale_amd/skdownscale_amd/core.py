@@ -89,6 +89,29 @@ class GridArray:
         perm = [self.dims.index(d) for d in dims]
         return GridArray(self.values.transpose(perm), dims, self.coords, self.name)
 
+    def interp_like(self, other, method="linear"):
+        """Interpolate onto the grid of ``other`` over exactly the two spatial dims both arrays name (``xarray``'s
+        ``interp_like`` for 1-D coordinates); ``time`` and ``variable`` pass through, and an ``other`` with a time dim contributes
+        only its spatial coordinates.  -> ``InterpolatedGridArray``: the coarse data, interpolated on the GPU when needed."""
+        from .regrid import interp_dims
+
+        dims = interp_dims(self, other.dims)
+        missing = [d for d in dims if d not in other.coords]
+        if missing:
+            raise ValueError(f"`other` has no coordinate for dim {missing[0]!r}")
+        return self.interp({d: other.coords[d] for d in dims}, method=method)
+
+    def interp(self, coords=None, method="linear", **coords_kw):
+        """Interpolate onto new 1-D coordinates of exactly two spatial dims (``da.interp(lat=..., lon=...)``)"""
+        from .regrid import InterpolatedGridArray, interp_dims
+
+        target = dict(coords or {}, **coords_kw)
+        unknown = [d for d in target if d not in self.dims]
+        if unknown:
+            raise ValueError(f"dim {unknown[0]!r} is not a dim of this array {self.dims}")
+        interp_dims(self, target)
+        return InterpolatedGridArray(self, target, method)
+
     def __repr__(self):
         return f"<GridArray {self.sizes}>"
 
@@ -224,6 +247,8 @@ def _unchunked(obj):
     """a block handed to a child model: plain (loaded) data without chunk structure"""
     if isinstance(obj, GridDataset):
         return GridDataset({k: _unchunked(v) for k, v in obj.items()})
+    if hasattr(obj, "unchunked"):  # InterpolatedGridArray: the block stays coarse data + target coordinates
+        return obj.unchunked()
     if isinstance(obj, GridArray):
         return GridArray(obj.values, obj.dims, obj.coords, obj.name)
     if _is_xarray(obj):
@@ -436,17 +461,11 @@ class PointWiseDownscaler:
                 fitted.append((sel, child))
             self._models = _BlockedModels(dims, [sizes[d] for d in dims], chunksizes, fitted)
             return
+        if self._resident_input(X) and args:
+            return self._fit_resident(X, args[0], feature_dim)
         Xg, _ = self._to_feature_x(X, feature_dim)
-        yg = None
         spatial_dims, spatial_shape = Xg.dims[2:], Xg.shape[2:]
-        if args:
-            # the reference selects y[index] by dimension *name* for every cell of X (core.py:86-93): align y to X's cell order
-            yg, _ = _to_grid(args[0], feature_dim)
-            if set(yg.dims) != {self._dim, *spatial_dims}:
-                raise ValueError(f"y has dims {yg.dims}; expected {(self._dim,) + tuple(spatial_dims)} (the spatial dims of X, no feature dim)")
-            yg = yg.transpose(self._dim, *spatial_dims)
-            if tuple(yg.shape[1:]) != tuple(spatial_shape) or yg.shape[0] != Xg.shape[0]:
-                raise ValueError(f"y has sizes {yg.sizes}, X has {Xg.sizes}")
+        yg = self._aligned_y(args[0], Xg.sizes, spatial_dims, feature_dim) if args else None
         T, F = Xg.shape[:2]
         C = int(np.prod(spatial_shape, dtype=np.int64)) if spatial_shape else 1
         Xv = np.ascontiguousarray(Xg.values, dtype=np.float64).reshape(T, F, C)
@@ -542,6 +561,47 @@ class PointWiseDownscaler:
                 self._raise_for_status(np.where(bad, _lib.CELL_NONFINITE, 0), Xv[:, :, c:c + 1].reshape(T, -1), yv[:, c:c + 1], cell=c)
         self._models = _BatchedModels(kind, gm, mask, spatial_dims, spatial_shape, coords)
 
+    def _aligned_y(self, y, x_sizes, spatial_dims, feature_dim):
+        """the reference selects y[index] by dimension *name* for every cell of X (core.py:86-93): align y to X's cell order"""
+        yg, _ = _to_grid(y, feature_dim)
+        if set(yg.dims) != {self._dim, *spatial_dims}:
+            raise ValueError(f"y has dims {yg.dims}; expected {(self._dim,) + tuple(spatial_dims)} (the spatial dims of X, no feature dim)")
+        yg = yg.transpose(self._dim, *spatial_dims)
+        if any(yg.sizes[d] != x_sizes[d] for d in yg.dims):
+            raise ValueError(f"y has sizes {yg.sizes}, X has {x_sizes}")
+        return yg
+
+    # ---- single-feature BCSD on an interpolated coarse field: the fine X is produced in HBM and never crosses PCIe ----
+    def _resident_input(self, X):
+        from .regrid import InterpolatedGridArray
+
+        return (isinstance(X, InterpolatedGridArray) and isinstance(self._model, BcsdBase) and len(X.dims) == 3 and X.dims[0] == self._dim)
+
+    def _fit_resident(self, X, y, feature_dim):
+        spatial_dims, spatial_shape = tuple(X.dims[1:]), tuple(X.shape[1:])
+        yg = self._aligned_y(y, X.sizes, spatial_dims, feature_dim)
+        T, C = X.shape[0], int(np.prod(spatial_shape, dtype=np.int64))
+        self._batched()
+        gm = self._bcsd_proto._new_grid()
+        Xd = X.device_field(gm.ctx)
+        mask = ~np.isnan(Xd.rows(0, 1).to_host()[0])  # core.py:35-37 on the regridded first time step: one row comes back
+        yv = np.ascontiguousarray(yg.values, dtype=np.float64).reshape(T, C)
+        gm.fit(Xd, gm.ctx.to_device(yv), _time_index(X, self._dim))
+        if np.isin(gm.status_, (_lib.CELL_NONFINITE, _lib.CELL_BAD_CLIMO)).any():  # (the message names X or y: needs the values)
+            self._raise_for_status(gm.status_, np.asarray(X.values, dtype=np.float64).reshape(T, C), yv)
+        coords = {k: v for k, v in X.coords.items() if k in spatial_dims}
+        self._models = _BatchedModels("bcsd", gm, mask, spatial_dims, spatial_shape, coords)
+
+    def _predict_resident(self, X):
+        mdl = self._models
+        T, C = X.shape[0], int(np.prod(mdl.spatial_shape, dtype=np.int64))
+        out, status = mdl.grid_model.predict(X.device_field(mdl.grid_model.ctx), _time_index(X, self._dim))
+        if np.isin(status, (_lib.CELL_NONFINITE, _lib.CELL_BAD_CLIMO)).any():
+            Xv = np.asarray(X.values, dtype=np.float64).reshape(T, C)
+            self._raise_for_status(status, Xv, Xv)
+        vals = out.to_host().reshape((T,) + tuple(mdl.spatial_shape))
+        return GridArray(vals, X.dims, dict(X.coords))
+
     @staticmethod
     def _raise_for_status(status, Xv, yv, cell=None):
         """Raise like the reference would for the first offending cell (base.py:18-20, bcsd.py:140-141)."""
@@ -598,6 +658,9 @@ class PointWiseDownscaler:
             return self._apply_blocks("predict", X, kwargs)
         kws = {"along_dim": self._dim, "feature_dim": DEFAULT_FEATURE_DIM} | kwargs
         feature_dim = kws["feature_dim"]
+        mdl = self._models
+        if mdl.kind == "bcsd" and self._resident_input(X) and (tuple(X.dims[1:]), tuple(X.shape[1:])) == (tuple(mdl.spatial_dims), tuple(mdl.spatial_shape)):
+            return self._predict_resident(X)
         Xg, was_x = self._to_feature_x(X, feature_dim)
         Xg = self._align_to_fitted(Xg, feature_dim)
         T, F = Xg.shape[:2]

@@ -55,6 +55,12 @@ class DeviceArray:
         return DeviceArray(self.ctx, self.shape[:-1] + (c1 - c0,), self.dtype, dptr=self.ptr + c0 * self.dtype.itemsize,
                            owner=False, ld=self.ld, base=self)
 
+    def rows(self, r0, r1):
+        """View of the rows [r0, r1) of a [T, C] field"""
+        assert len(self.shape) == 2 and 0 <= r0 < r1 <= self.shape[0]
+        return DeviceArray(self.ctx, (r1 - r0, self.shape[1]), self.dtype, dptr=self.ptr + r0 * self.ld * self.dtype.itemsize, owner=False,
+                           ld=self.ld, base=self)
+
     def to_host(self):
         if self.ld != self.shape[-1]:  # strided view: copy the parent's rows and slice on the host
             rows = int(np.prod(self.shape[:-1], dtype=np.int64))
@@ -242,6 +248,49 @@ class QmState(_State):
         status = np.empty(i["C"], dtype=np.int32)
         check(self.ctx.lib.sd_qm_state_export(self.vptr, ptr(xs), None if ys is None else ptr(ys), ptr(status)))
         return dict(x_sorted=xs, y_sorted=ys, status=status)
+
+
+class RegridState(_State):
+    """Separable interpolation tables of one (source grid, target grid, method) on the device (sd_regrid_create)."""
+
+    def info(self):
+        method = C.c_int()
+        ny, nx, Ny, Nx = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(self.ctx.lib.sd_regrid_info(self.vptr, C.byref(method), C.byref(ny), C.byref(nx), C.byref(Ny), C.byref(Nx)))
+        return dict(method=method.value, ny=ny.value, nx=nx.value, Ny=Ny.value, Nx=Nx.value)
+
+    def apply(self, src, out=None):
+        """src [T, ny, nx]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray -> [T, Ny * Nx]
+        float64 DeviceArray, cells fastest (``out``: a [T, C] DeviceArray, possibly a cells() view of a wider one).  float32 goes to
+        the device as float32 and is widened in the kernel."""
+        i = self.info()
+        src, f32 = self._source(src, i)
+        T = src.shape[0]
+        if not isinstance(src, DeviceArray):
+            src = self.ctx.to_device(src, src.dtype)
+        out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
+        check(self.ctx.lib.sd_regrid_apply_dev(self.ctx.handle, self.vptr, src.vptr, f32, T, out.vptr, out.ld))
+        return out
+
+    def apply_host(self, src):
+        """host [T, ny, nx] -> host [T, Ny * Nx] through sd_regrid_apply (upload, run, download in one call)"""
+        i = self.info()
+        src, f32 = self._source(src, i)
+        if isinstance(src, DeviceArray):
+            raise ValueError("apply_host: expected a host array")
+        out = np.empty((src.shape[0], i["Ny"] * i["Nx"]))
+        check(self.ctx.lib.sd_regrid_apply(self.ctx.handle, self.vptr, ptr(src), f32, src.shape[0], ptr(out)))
+        return out
+
+    @staticmethod
+    def _source(src, i):
+        if not isinstance(src, DeviceArray):
+            src = np.ascontiguousarray(src, dtype=np.float32 if getattr(src, "dtype", None) == np.float32 else np.float64)
+        if len(src.shape) != 3 or tuple(src.shape[1:]) != (i["ny"], i["nx"]) or src.shape[0] < 1:
+            raise ValueError(f"src: expected a [T, {i['ny']}, {i['nx']}] field, got shape {tuple(src.shape)}")
+        if isinstance(src, DeviceArray) and (src.dtype not in (np.float32, np.float64) or src.ld != src.shape[-1]):
+            raise ValueError("src: expected a contiguous float32 or float64 DeviceArray")
+        return src, int(src.dtype == np.float32)
 
 
 class Context:
@@ -893,6 +942,18 @@ class Context:
         else:
             check(self.lib.sd_arrm_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(out), ptr(status)))
         return out, status
+
+
+    # ---- regridding (GridArray.interp_like) ----
+    def regrid_create(self, src_y, src_x, dst_y, dst_x, method="linear"):
+        """Tables that take a [T, len(src_y), len(src_x)] field onto the (dst_y, dst_x) grid -> RegridState"""
+        if method not in _lib.REGRID_METHODS:
+            raise NotImplementedError(f"regrid method {method!r}: expected 'linear' or 'nearest'")
+        sy, sx, dy, dx = (_lib.as_f64(np.ravel(a)) for a in (src_y, src_x, dst_y, dst_x))
+        h = C.c_void_p()
+        check(self.lib.sd_regrid_create(self.handle, _lib.REGRID_METHODS[method], len(sy), len(sx), ptr(sy), ptr(sx), len(dy), len(dx),
+                                        ptr(dy), ptr(dx), C.byref(h)))
+        return RegridState(self, h.value, self.lib.sd_regrid_destroy)
 
 
 _default_ctx = None

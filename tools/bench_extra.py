@@ -20,9 +20,119 @@ from skdownscale_amd import _lib, synth  # noqa: E402
 from skdownscale_amd.engine import Context  # noqa: E402
 
 
+def regrid_case(T, Ny, Nx, ny=16, nx=25):
+    """a coarse [T, ny, nx] temperature field (descending latitude, like gridMET) and a fine grid inside its hull"""
+    rng = np.random.default_rng(24)
+    sy, sx = np.linspace(50.0, 30.0, ny), np.linspace(-125.0, -100.0, nx)
+    dy, dx = np.linspace(49.9, 30.1, Ny), np.linspace(-124.9, -100.1, Nx)
+    season = 10.0 * np.sin(2.0 * np.pi * np.arange(T) / 365.25)
+    return 285.0 + season[:, None, None] + 3.0 * rng.normal(size=(T, ny, nx)), sy, sx, dy, dx
+
+
+def device_fill_ms(nbytes, dptr, repeats):
+    """median HIP-event time of hipMemsetAsync over nbytes of device memory: the rate a plain fill of the output buffer reaches"""
+    import ctypes
+
+    hip = ctypes.CDLL("libamdhip64.so")
+    e0, e1 = ctypes.c_void_p(), ctypes.c_void_p()
+    ms, times = ctypes.c_float(), []
+    assert hip.hipEventCreate(ctypes.byref(e0)) == 0 and hip.hipEventCreate(ctypes.byref(e1)) == 0
+    for _ in range(repeats + 1):  # (the first one warms up)
+        assert hip.hipEventRecord(e0, None) == 0
+        assert hip.hipMemsetAsync(ctypes.c_void_p(dptr), 0, ctypes.c_size_t(nbytes), None) == 0
+        assert hip.hipEventRecord(e1, None) == 0 and hip.hipEventSynchronize(e1) == 0
+        assert hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1) == 0
+        times.append(ms.value)
+    hip.hipEventDestroy(e0), hip.hipEventDestroy(e1)
+    return float(np.median(times[1:]))
+
+
+def bench_regrid(ctx, args):
+    """regrid_kernel: a 16 x 25 coarse field onto 250 x 400 cells, float64 and float32 sources; GB/s by algorithmic bytes
+    (8 * T * C written + the source read once), beside a plain device fill of the same output buffer, parity against the oracle on the
+    first 256 cells"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _regrid_oracle as ro
+
+    T, Ny, Nx = args.times, 250, 400
+    C = Ny * Nx
+    src, sy, sx, dy, dx = regrid_case(T, Ny, Nx)
+    state = ctx.regrid_create(sy, sx, dy, dx)
+    out = ctx.empty((T, C))
+    repeats = max(args.steps, 5)
+    res = {"workload": f"regrid 16x25 -> {Ny}x{Nx} ({C} cells) x {T} steps, bilinear", "repeats": repeats}
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        host = src.astype(dtype)
+        d = ctx.to_device(host, dtype)
+        state.apply(d, out=out)
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            state.apply(d, out=out)
+            times.append(ctx.prof()["regrid_kernel"]["ms"])
+        ctx.prof_enable(False)
+        ms = float(np.median(times))
+        nbytes = 8 * T * C + host.nbytes
+        want = ro.regrid(host, sy, sx, dy[:1], dx[:256]).reshape(T, 256)
+        got = out.cells(0, 256).to_host()
+        err = float(np.abs(got - want).max() / np.abs(host).max())
+        res[name] = {"kernel_ms": ms, "kernel_ms_min_max": [min(times), max(times)], "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                     "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "max_err_over_max_src_first_256_cells": err,
+                     "bit_identical_to_oracle": bool(np.array_equal(got, want))}
+        d.free()
+    fill_ms = device_fill_ms(8 * T * C, out.ptr, repeats)
+    res["device_fill"] = {"ms": fill_ms, "bytes": 8 * T * C, "GBps": 8 * T * C / fill_ms / 1e6}
+    res["kernel_over_fill"] = {k: res[k]["kernel_ms"] / fill_ms for k in ("f64", "f32")}
+    return res
+
+
+def bench_regrid_e2e(ctx, args):
+    """PointWiseDownscaler(BcsdTemperature()) fit + predict from host data, twice in this process: X_hist / X_fut as materialised fine
+    host grids, and as coarse.interp_like(obs) (the fine X is produced in HBM); cells/s of both legs, outputs compared bit for bit"""
+    import pandas as pd
+
+    from skdownscale_amd import BcsdTemperature, GridArray, PointWiseDownscaler
+
+    T, Nx = args.times, 400
+    Ny = max(1, args.cells // Nx)
+    C = Ny * Nx
+    hist, sy, sx, dy, dx = regrid_case(T, Ny, Nx)
+    time_index = pd.date_range("1980-01-01", periods=T, freq="D")
+    rng = np.random.default_rng(25)
+    coords = dict(time=time_index, lat=sy, lon=sx)
+    fine = dict(time=time_index, lat=dy, lon=dx)
+    coarse = {"hist": GridArray(hist, ("time", "lat", "lon"), coords), "fut": GridArray(hist + 1.5 + rng.normal(size=hist.shape), ("time", "lat", "lon"), coords)}
+    obs = GridArray(hist.mean(axis=(1, 2))[:, None, None] - 2.0 + 2.0 * rng.normal(size=(T, Ny, Nx)), ("time", "lat", "lon"), fine)
+    legs = {"interpolated": {k: v.interp_like(obs) for k, v in coarse.items()},
+            "materialised": {k: GridArray(v.interp_like(obs).values, ("time", "lat", "lon"), fine) for k, v in coarse.items()}}
+
+    def run(X):
+        model = PointWiseDownscaler(BcsdTemperature())
+        model.fit(X["hist"], obs)
+        return np.asarray(model.predict(X["fut"]).values)
+
+    run(legs["materialised"])  # warm-up: code objects, pinned rings, the block cache
+    res = {"workload": f"PointWiseDownscaler(BcsdTemperature) fit + predict from host data, 16x25 -> {Ny}x{Nx} ({C} cells) x {T} steps", "repeats": args.steps}
+    outs = {}
+    for _ in range(args.steps):  # the two legs alternate
+        for name, X in legs.items():
+            t0 = time.perf_counter()
+            outs[name] = run(X)
+            res.setdefault(name, []).append(time.perf_counter() - t0)
+    for name in legs:
+        s = float(np.median(res[name]))
+        res[name] = {"seconds": s, "cells_per_s": C / s}
+    res["speedup"] = res["materialised"]["seconds"] / res["interpolated"]["seconds"]
+    res["bit_identical"] = bool(np.array_equal(outs["interpolated"], outs["materialised"], equal_nan=True))
+    res["fine_X_reached_the_host"] = any(v.computed for v in legs["interpolated"].values())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm"], default="analog")
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e"],
+                    default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
     ap.add_argument("--steps", type=int, default=2)
@@ -32,6 +142,13 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
+    if args.workload in ("regrid", "regrid_e2e"):
+        line = json.dumps((bench_regrid if args.workload == "regrid" else bench_regrid_e2e)(ctx, args))
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+        return
     T, C = args.times, args.cells
     index = synth.daily_calendar(T)
     gid = (np.asarray(index.month) - 1).astype(np.int32)
