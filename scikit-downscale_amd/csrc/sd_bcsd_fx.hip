@@ -832,11 +832,13 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fx_kernel(const Params) {
 //             K l .. K l + K - 1), and without the skew the lane stride K x 64 B would put every lane on the same bank.
 //   u side    the shifted series is not written back as float64: the key generation (one v_add_f64 with 2^21: q and 31
 //             further bits of the fixed-point quotient come out of the mantissa) leaves a 32-bit SECOND-LEVEL key u2 per
-//             sample, stored cell-major in the first 39 KB of the tile once every wave has read its windows; the fix-up of
-//             equal-q neighbours compares u2 (equal u2 = equal or indistinguishable values: work list).  The rest of the
-//             tile is free during the sort of u: that is where the early half of the y tile lands.
-//   y side    the late half of y is requested behind the vote barrier (the u2 area is dead then); column reads, keys, sort,
-//             fix-up on the float64 observations by tag, gather, scatter to the tags of u, shift restored in place.
+//             sample, stored cell-major in the first 40 chunks of the tile (five whole chunks per cell) once every wave has
+//             read its windows; the fix-up of equal-q neighbours compares u2 (equal u2 = equal or indistinguishable values:
+//             work list).  The rest of the tile is free during the sort of u: that is where the early half of the y tile lands.
+//   y side    the late half of y: each wave requests the five chunks under ITS OWN cell's u2 region as soon as its own fix-up
+//             of u is done (the region is dead then, and no other wave reads or writes it), waits for its requests and meets
+//             the others at one barrier, behind which the vote on the fix-ups is read; column reads, keys, sort, fix-up on
+//             the float64 observations by tag, gather, scatter to the tags of u, shift restored in place.
 //   output    the tile is already time-major: ds_read_b128 of a chunk, lane-linear, and 64-byte row fragments to memory.
 //
 // Row indices of the requests: loaded once per order table into registers (element 16 k + i of a wave's chunk list in register
@@ -877,17 +879,22 @@ template <int NREG>
 struct RowIdx {
     int v[NREG];
 };
-// rows of the chunks q0 + wave + 8 k, k = 0 .. 4 NREG - 1
+// rows of the chunks qb + qs k, k = 0 .. 4 NREG - 1 (a chunk past the tile names the segment's last row: row_of_slot)
 template <int NREG>
-__device__ __forceinline__ RowIdx<NREG> rows_of_wave(const int32_t* __restrict__ ord, int n, int q0, int wave, int lane) {
+__device__ __forceinline__ RowIdx<NREG> rows_of_chunks(const int32_t* __restrict__ ord, int n, int qb, int qs, int lane) {
     RowIdx<NREG> t;
     const int nl = lanes_of(n);
 #pragma unroll
     for (int j = 0; j < NREG; ++j) {
         const int e = 64 * j + lane;
-        t.v[j] = ord[row_of_slot(q0 + wave + kW * (e >> 4), e & 15, nl, n)];
+        t.v[j] = ord[row_of_slot(qb + qs * (e >> 4), e & 15, nl, n)];
     }
     return t;
+}
+// rows of the chunks q0 + wave + 8 k: the tile dealt round the waves
+template <int NREG>
+__device__ __forceinline__ RowIdx<NREG> rows_of_wave(const int32_t* __restrict__ ord, int n, int q0, int wave, int lane) {
+    return rows_of_chunks<NREG>(ord, n, q0 + wave, kW, lane);
 }
 // The indices are "used" here, so the compiler's wait for their loads sits here -- ahead of the requests -- and not between
 // them, where it would count only its own loads and drain the DMA queue with them.
@@ -900,16 +907,17 @@ template <int NREG>
 __device__ __forceinline__ int row_of_request(const RowIdx<NREG>& rows, int k, int lane) {
     return __builtin_amdgcn_ds_bpermute(4 * (16 * (k & 3) + (lane >> 2)), rows.v[k >> 2]);
 }
-// requests for the chunks q = q0 + wave + 8 k < q1 of a tile (NK = requests per wave at most)
-template <int NK, int NREG>
-__device__ __forceinline__ void dma_chunks(const double* __restrict__ src, int64_t ld, const RowIdx<NREG>& rows, int q0, int q1,
-                                           int64_t c0, unsigned tile_b, int wave, int lane) {
+// requests for the chunks q = qb + qs k < q1 of a tile (NK = requests per wave at most; rows: rows_of_chunks of the same qb, qs);
+// ALL: every one of the NK chunks lies inside the tile (q1 is not read, no bound is tested: the requests are straight-line code)
+template <int NK, int NREG, bool ALL = false>
+__device__ __forceinline__ void dma_chunk_list(const double* __restrict__ src, int64_t ld, const RowIdx<NREG>& rows, int qb, int qs, int q1,
+                                               int64_t c0, unsigned tile_b, int lane) {
     static_assert(NK <= 4 * NREG, "row registers");
     const char* colp = reinterpret_cast<const char*>(src + c0) + 16 * (lane & 3);
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int q = q0 + wave + kW * k;
-        if (q < q1) {  // (wave-uniform)
+        const int q = qb + qs * k;
+        if (ALL || q < q1) {  // (wave-uniform)
             const int ti = row_of_request(rows, k, lane);
             const char* g = colp + (uint64_t)(uint32_t)ti * (uint64_t)(uint32_t)((uint32_t)ld * 8u);
             const int dst = __builtin_amdgcn_readfirstlane((int)(tile_b + (unsigned)q * (unsigned)kChunkStride));
@@ -920,6 +928,12 @@ __device__ __forceinline__ void dma_chunks(const double* __restrict__ src, int64
                          : "memory");
         }
     }
+}
+// requests for the chunks q = q0 + wave + 8 k < q1 (rows: rows_of_wave of the same q0)
+template <int NK, int NREG>
+__device__ __forceinline__ void dma_chunks(const double* __restrict__ src, int64_t ld, const RowIdx<NREG>& rows, int q0, int q1,
+                                           int64_t c0, unsigned tile_b, int wave, int lane) {
+    dma_chunk_list<NK, NREG>(src, ld, rows, q0 + wave, kW, q1, c0, tile_b, lane);
 }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -1066,13 +1080,34 @@ __device__ __forceinline__ int fix_equal_q_by(unsigned (&k)[K], int lane, const 
 
 // (LDS of a workgroup, fd_u2_stride, fd_late_chunks, fd_lds_bytes: sd_bcsd_plan.h)
 // Half of the y tile is requested ahead of the sort of u (the second-level keys are compacted into the other half behind a
-// workgroup barrier); the other half behind the vote.
+// workgroup barrier); the other half by each wave behind its own fix-up of u, ahead of the one barrier that also carries the vote.
+// The u2 area INSIDE the kernel is not packed at the plan's fd_u2_stride (4 RSU = 64 chunks_of(m) bytes per cell: one 1 032-byte
+// chunk would straddle the regions of two cells, and no wave could overwrite its region before every wave was done with u2):
+// cell `col` owns the whole chunks 5 col .. 5 col + 4 (kU2CellBytes), the area is the chunks 0 .. 39 (kU2Chunks), the early half
+// of y the chunks 40 .. nch - 1.  Params::RS and the plan's fd_u2_stride / fd_late_chunks still describe the packed area: it is
+// what the plan's `fits` sizes (late <= 40, nch - late <= 40, nch <= 80) and what the plan tests pin; the launcher checks that
+// those bounds cover the kernel's geometry (fd_geometry_ok).
 // RAG: segments of any length the launcher admits (February and December of a daily series: 1 130 / 1 230 samples, m % 20 = 10).
 // The last data lane holds r = m % 20 samples in the slots of a whole lane (r = 17 .. 19 reach its tail slots); the slots past the
 // segment hold copies of its last row (row_of_slot), so the finite checks and the extremes of the observations need no mask.
 // Per-sample predicates where a position past m would change a result: the rolling window and its count (the last two lanes),
 // the extremes of u, the pad keys, the y climatology sum, the scatter and the stores; the other lanes compute the same values
 // as the whole-lane instantiation.  The x_hist rows are predicated like the general kernel's (segments below full_min_len).
+constexpr int kU2CellChunks = 5;                                 // whole chunks per cell of the u2 area
+constexpr int kU2CellBytes = kU2CellChunks * tmj::kChunkStride;  // 5 160 B
+constexpr int kU2Chunks = kW * kU2CellChunks;                    // 40: the u2 area = the late half of y
+constexpr int kFdMaxChunks = 80;                                 // chunks of a tile at most (64 lanes of data)
+static_assert(4 * fd_u2_stride(64 * tmj::kBlock) <= kU2CellBytes && tmj::chunks_of(64 * tmj::kBlock) == kFdMaxChunks,
+              "the second-level keys of a cell (one word per slot of the tile) fit its five chunks");
+static_assert(kU2CellChunks <= 5 && kFdMaxChunks - kU2Chunks <= 5 * kW, "five requests per wave for either half of y (dma_chunks<5, 2>)");
+static_assert(tmj::chunks_of(641) > kU2Chunks, "every admitted segment (more than 640 samples: the plan's `fits`) has chunks past the u2 area");
+// what the kernel relies on, on the launch record's numbers (rs = fd_u2_stride, lds = fd_lds_bytes of the longest segment; every
+// segment of the launch has more than 32 lanes of data -- the plan's `fits` --, i.e. at least 49 chunks: the area lies inside
+// every tile and the early half is never empty)
+inline bool fd_geometry_ok(int rs, size_t lds) {
+    const int nch = rs / 16;
+    return rs % 16 == 0 && nch >= kU2Chunks && nch <= kFdMaxChunks && lds >= kHeadDoubles * sizeof(double) + (size_t)nch * tmj::kChunkStride;
+}
 template <int K, bool RAG>
 __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1115,8 +1150,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     if (m == 0) return;
     const int nl = RAG ? tmj::lanes_of(m) : m / K;  // lanes with data
     const int nch = tmj::chunks_of(m);
-    const int RSU = p->RS;                    // 32-bit words per cell of the u2 area
-    const int nlate = fd_late_chunks(RSU) < nch ? fd_late_chunks(RSU) : nch;  // chunks under the u2 area: the late half of y
+    constexpr int nlate = kU2Chunks;  // chunks under the u2 area: the late half of y (nch > nlate: fd_geometry_ok)
     const bool cell_live = cell_ok && p->status_fit[cell_ok ? c : 0] == 0;
     // a tile whose last cells lie past the grid (C is even: pairs of cells are whole) fetches its last whole pair instead
     const int64_t cfetch = c0 + kW <= p->C ? c0 : p->C - kW;  // (C >= 8: the launcher's condition)
@@ -1240,8 +1274,9 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
             }
         }
         SDT(3);  // rolling mean
-        // the rows of the y requests (the loads return under the key generation)
-        ry_late = tmj::rows_of_wave<2>(p->ord_f + begf, m, 0, wave, lane);
+        // the rows of the y requests (the loads return under the key generation): the late chunks are those under the u2 region
+        // of the wave's column -- col, not wave: a tile shifted back over its predecessor rotates the columns
+        ry_late = tmj::rows_of_chunks<2>(p->ord_f + begf, m, kU2CellChunks * col, 1, lane);
         ry_early = tmj::rows_of_wave<2>(p->ord_f + begf, m, nlate, wave, lane);
         SDPH("u_keys");
         unsigned u2[K];
@@ -1256,7 +1291,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         tmj::rows_ready(ry_early);
         __syncthreads();
         if (!(abl & 32)) tmj::dma_chunks<5, 2>(p->y, p->ld, ry_early, nlate, nch, cfetch, tile_b, wave, lane);
-        const unsigned ub = tile_b + 4u * (unsigned)(col * RSU);
+        const unsigned ub = tile_b + (unsigned)(col * kU2CellBytes);
         if (has) {  // by tag: the lane's chunk is 16 consecutive words, its tail four words 16 bytes apart
             const tmj::Tags tg = tmj::tags_of(lane, nl);
             typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
@@ -1281,35 +1316,40 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         const bool tie = (abl & 8) ? false : tmj::fix_equal_q_by<K>(ku, lane, cmp_u2) != 0;
         redo = tie && cell_live && bad_cell[wave] == 0 && (abl & 0x7ff) == 0;  // wave-uniform
         SDT(6);  // fix-up of u
+        // ---- y: the late half of the tile.  No barrier here: the wave has compared its last second-level keys, nobody else
+        // reads or writes its column's u2 region, and its five late chunks cover exactly that region (kU2CellBytes).  The wave's
+        // vote (bit 0 of its flag) rides on the barrier behind which the tile is complete.
+        SDPH("y_tile");
+        redo_flag[wave] = redo ? 1 : 0;
+        // (phase clocks: slot 7, which tools/dev/trace_fx.py still prints as "vote barrier", now holds the flag write alone --
+        // next to nothing --, and slot 9, "y landed + barrier", the whole wait for the late half and for the other waves)
+        SDT(7);
+        if (!(abl & 32)) tmj::dma_chunk_list<kU2CellChunks, 2, true>(p->y, p->ld, ry_late, kU2CellChunks * col, 1, nlate, cfetch, tile_b, lane);  // (all below nlate < nch)
+        SDT(8);  // late half requested
+        tmj::dma_wait_all();
     }
-    SDPH("vote");
-    redo_flag[wave] = redo ? 1 : 0;
     __syncthreads();
+    SDT(9);  // y tile landed
     int any_redo = 0;
 #pragma unroll
-    for (int w = 0; w < kW; ++w) any_redo |= redo_flag[w];
+    for (int w = 0; w < kW; ++w) any_redo |= redo_flag[w] & 1;  // (bit 0: a wave far ahead may already have written its second vote)
     if (any_redo) {
-        tmj::dma_wait_all();  // (no request of this workgroup may land in the LDS of its successor)
+        // A handed-back item has fetched its late y for nothing (a few items per million).  Invariant of this return: every wave
+        // has waited for ALL of its own requests (dma_wait_all above, early half included) before the barrier, so no request of
+        // this workgroup can land in the LDS of its successor.
         if (threadIdx.x == 0) {
             const int slot = atomicAdd(p->work_count, 1);
             if (slot < p->work_cap) p->worklist[slot] = tile_id * p->G + g;
         }
         return;
     }
-    SDT(7);  // vote
 
-    // ---- y: the late half of the tile, climatology, sorted observations ---------------------------------------------------
-    SDPH("y_tile");
+    // ---- y: climatology, sorted observations --------------------------------------------------------------------------------
     double yc = 0.0;
     double t[K];
     bool redo_y = false;
     {
         SD_LANE();
-        if (!(abl & 32)) tmj::dma_chunks<5, 2>(p->y, p->ld, ry_late, 0, nlate, cfetch, tile_b, wave, lane);
-        SDT(8);  // late half requested
-        tmj::dma_wait_all();
-        __syncthreads();
-        SDT(9);  // y tile landed
         SDPH("y_keys");
         const bool has = K * lane < m;
         const int bl = has ? lane : 0;
@@ -1374,7 +1414,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     }
     SDPH("store");
     SDT(13);  // scatter, shift restored
-    redo_flag[wave] = redo_y ? 1 : 0;
+    redo_flag[wave] = redo_y ? 2 : 0;  // (bit 1: no barrier lies between the readers of the first vote and this write; bit 0 stays 0)
     tmj::RowIdx<3> ro = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, tid_now() % kWave);  // (named ahead of the last barrier)
     __syncthreads();
     tmj::rows_ready(ro);
@@ -2001,10 +2041,12 @@ int run_k(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
             if constexpr (compact_width(K) != 0) return launch_rec(ctx, L, p, &bcsd_fxc_kernel<K, compact_width(K), false>);
             break;
         case BcsdKernel::FdWhole:
-            if constexpr (K == tmj::kBlock) return launch_rec(ctx, L, p, &bcsd_fd_kernel<K, false>);
-            break;
         case BcsdKernel::FdRagged:
-            if constexpr (K == tmj::kBlock) return launch_rec(ctx, L, p, &bcsd_fd_kernel<K, true>);
+            if constexpr (K == tmj::kBlock) {
+                if (!fd_geometry_ok(L.rs, L.lds))
+                    return sd_set_error(SD_ERR_INVALID, "bcsd_fd_kernel: rs = %d, %zu bytes of LDS do not hold its u2 area", L.rs, (size_t)L.lds);
+                return launch_rec(ctx, L, p, L.kernel == BcsdKernel::FdWhole ? &bcsd_fd_kernel<K, false> : &bcsd_fd_kernel<K, true>);
+            }
             break;
         default: break;
     }
