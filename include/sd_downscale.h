@@ -96,6 +96,10 @@ extern "C" {
 #define SD_REGRID_LINEAR 0  /* interp_like(method='linear'): bilinear on a rectilinear grid, one dimension after the other */
 #define SD_REGRID_NEAREST 1 /* method='nearest': a midpoint goes to the lower neighbour */
 
+/* sd_resample: reduction over the rows of a bin */
+#define SD_RESAMPLE_MEAN 0  /* NaN samples skipped; NaN for a bin without a sample */
+#define SD_RESAMPLE_SUM 1   /* NaN samples skipped; 0 for a bin without a sample (pandas' min_count=0) */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -398,6 +402,21 @@ int sd_regrid_apply_dev(sd_ctx* ctx, const sd_regrid* rg, const void* src_dev, i
                         int64_t ld_out);
 /* host buffers: src [T, ny, nx], out [T, Ny * Nx] */
 int sd_regrid_apply(sd_ctx* ctx, const sd_regrid* rg, const void* src_host, int src_is_f32, int64_t T, double* out_host);
+
+/* ---- resampling of the time axis: GridArray.resample(time=rule).mean() / .sum() -----------------------------
+ * A [T, C] field (cells fastest, rows ld >= C elements apart) is reduced over runs of consecutive rows into an [M, C] float64 field
+ * (rows ld_out >= C apart): bin m is the rows offsets[m] .. offsets[m + 1] - 1.  The table is a host array of M + 1 entries that
+ * starts at 0, never decreases and ends at T (pandas' resampler makes it: counts = series.resample(rule).size(), offsets = [0,
+ * cumsum(counts)]); an empty bin has two equal entries.  Both reductions skip NaN samples; a bin without a non-NaN sample -- empty or
+ * all NaN -- gives NaN for SD_RESAMPLE_MEAN and 0 for SD_RESAMPLE_SUM, as pandas' DataFrame.resample(rule).mean() / .sum() do.  The
+ * samples of a bin are added in time order, so the result of a bin does not depend on what else the call holds.  inf follows IEEE
+ * arithmetic.  src: float64, or float32 with src_is_f32 != 0 (widened per sample in the kernel).  An unknown op, sizes <= 0, ld < C,
+ * ld_out < C and a table that breaks the rules above are SD_ERR_INVALID. */
+int sd_resample_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C, const int64_t* offsets,
+                    int64_t M, double* out_dev, int64_t ld_out);
+/* host buffers: src [T, C], out [M, C]; upload, run, download */
+int sd_resample(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int64_t* offsets, int64_t M,
+                double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

@@ -10,6 +10,7 @@ from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression,
 from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
 from .grouping import GroupedGridModel, GroupedRegressor
 from .regrid import InterpolatedGridArray, Regridder
+from .resample import GridResample, ResampledGridArray, time_bins
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -47,5 +48,8 @@ __all__ = [
     "arrm_breakpoints",
     "Regridder",
     "InterpolatedGridArray",
+    "ResampledGridArray",
+    "GridResample",
+    "time_bins",
 ]
 __version__ = "0.1.0"

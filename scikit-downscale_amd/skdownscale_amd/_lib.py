@@ -24,6 +24,7 @@ CUNNANE_FORWARD, CUNNANE_INVERSE = 0, 1
 EXTRAP_CODES = {None: 0, "1to1": 0, "min": 1, "max": 2, "both": 3}  # SD_EXTRAP_* (CunnaneTransformer: '1to1' clamps like None)
 QM_EXTRAP_CODES = {None: 0, "min": 1, "max": 2, "both": 3, "1to1": 4}  # regressors (sd_qm_predict)
 REGRID_METHODS = {"linear": 0, "nearest": 1}  # SD_REGRID_*
+RESAMPLE_OPS = {"mean": 0, "sum": 1}  # SD_RESAMPLE_*
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -128,6 +129,8 @@ SIGNATURES = {
     "sd_regrid_info": [_p, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "sd_regrid_apply_dev": [_p, _p, _p, _int, _i64, _p, _i64],
     "sd_regrid_apply": [_p, _p, _p, _int, _i64, _p],
+    "sd_resample_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64],
+    "sd_resample": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

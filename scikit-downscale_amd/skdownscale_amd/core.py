@@ -112,6 +112,21 @@ class GridArray:
         interp_dims(self, target)
         return InterpolatedGridArray(self, target, method)
 
+    def resample(self, indexer=None, scratch_bytes=None, **kwargs):
+        """``resample(time='MS').mean()`` / ``.sum()``: pandas' ``DataFrame.resample(rule, **kw)`` bins of the dim's coordinate, reduced
+        per cell on the GPU (``xarray``'s ``da.resample(time=rule)`` for these two reductions).  Exactly one dim is named, as a keyword
+        or in ``indexer``; every other keyword (``closed``, ``label``, ``offset``, ``origin``) goes to pandas.  NaN samples are skipped;
+        a bin without a non-NaN sample gives NaN for ``mean`` and 0.0 for ``sum`` (pandas' rule; xarray's ``sum`` may differ on empty
+        bins).  ``scratch_bytes``: device scratch of one block of whole bins (default 1 GiB; a block is at least one bin).
+        -> ``GridResample``, whose ``mean()`` / ``sum()`` give a lazy ``ResampledGridArray`` (float64)."""
+        from .resample import DEFAULT_SCRATCH_BYTES, GridResample
+
+        named = dict(indexer or {}, **{k: kwargs.pop(k) for k in list(kwargs) if k in self.dims})
+        if len(named) != 1:
+            raise ValueError(f"resample needs exactly one dim=rule, got {sorted(named)} (dims of this array: {self.dims})")
+        (dim, rule), = named.items()
+        return GridResample(self, dim, rule, kwargs, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def __repr__(self):
         return f"<GridArray {self.sizes}>"
 
@@ -566,7 +581,8 @@ class PointWiseDownscaler:
         yg, _ = _to_grid(y, feature_dim)
         if set(yg.dims) != {self._dim, *spatial_dims}:
             raise ValueError(f"y has dims {yg.dims}; expected {(self._dim,) + tuple(spatial_dims)} (the spatial dims of X, no feature dim)")
-        yg = yg.transpose(self._dim, *spatial_dims)
+        if tuple(yg.dims) != (self._dim,) + tuple(spatial_dims):  # (a lazy y already in X's order stays lazy)
+            yg = yg.transpose(self._dim, *spatial_dims)
         if any(yg.sizes[d] != x_sizes[d] for d in yg.dims):
             raise ValueError(f"y has sizes {yg.sizes}, X has {x_sizes}")
         return yg
@@ -574,10 +590,14 @@ class PointWiseDownscaler:
     # ---- single-feature BCSD on an interpolated coarse field: the fine X is produced in HBM and never crosses PCIe ----
     def _resident_input(self, X):
         from .regrid import InterpolatedGridArray
+        from .resample import ResampledGridArray
 
-        return (isinstance(X, InterpolatedGridArray) and isinstance(self._model, BcsdBase) and len(X.dims) == 3 and X.dims[0] == self._dim)
+        return (isinstance(X, (InterpolatedGridArray, ResampledGridArray)) and isinstance(self._model, BcsdBase) and len(X.dims) == 3
+                and X.dims[0] == self._dim)
 
     def _fit_resident(self, X, y, feature_dim):
+        from .resample import ResampledGridArray
+
         spatial_dims, spatial_shape = tuple(X.dims[1:]), tuple(X.shape[1:])
         yg = self._aligned_y(y, X.sizes, spatial_dims, feature_dim)
         T, C = X.shape[0], int(np.prod(spatial_shape, dtype=np.int64))
@@ -585,10 +605,14 @@ class PointWiseDownscaler:
         gm = self._bcsd_proto._new_grid()
         Xd = X.device_field(gm.ctx)
         mask = ~np.isnan(Xd.rows(0, 1).to_host()[0])  # core.py:35-37 on the regridded first time step: one row comes back
-        yv = np.ascontiguousarray(yg.values, dtype=np.float64).reshape(T, C)
-        gm.fit(Xd, gm.ctx.to_device(yv), _time_index(X, self._dim))
+        def y_host():
+            return np.ascontiguousarray(yg.values, dtype=np.float64).reshape(T, C)
+
+        # (a resampled y is reduced in HBM as well; _aligned_y has brought any other y to X's order on the host)
+        yd = yg.device_field(gm.ctx) if isinstance(yg, ResampledGridArray) else gm.ctx.to_device(y_host())
+        gm.fit(Xd, yd, _time_index(X, self._dim))
         if np.isin(gm.status_, (_lib.CELL_NONFINITE, _lib.CELL_BAD_CLIMO)).any():  # (the message names X or y: needs the values)
-            self._raise_for_status(gm.status_, np.asarray(X.values, dtype=np.float64).reshape(T, C), yv)
+            self._raise_for_status(gm.status_, np.asarray(X.values, dtype=np.float64).reshape(T, C), y_host())
         coords = {k: v for k, v in X.coords.items() if k in spatial_dims}
         self._models = _BatchedModels("bcsd", gm, mask, spatial_dims, spatial_shape, coords)
 

@@ -955,6 +955,49 @@ class Context:
                                         ptr(dy), ptr(dx), C.byref(h)))
         return RegridState(self, h.value, self.lib.sd_regrid_destroy)
 
+    # ---- resampling of the time axis (GridArray.resample) ----
+    @staticmethod
+    def _resample_args(field, offsets, op):
+        if op not in _lib.RESAMPLE_OPS:
+            raise NotImplementedError(f"resample reduction {op!r}: only 'mean' and 'sum' are implemented")
+        if not isinstance(field, DeviceArray):
+            field = np.ascontiguousarray(field, dtype=np.float32 if getattr(field, "dtype", None) == np.float32 else np.float64)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
+        return field, offsets, _lib.RESAMPLE_OPS[op], int(field.dtype == np.float32)
+
+    def resample(self, field, offsets, op="mean", out=None):
+        """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart);
+        offsets: host int64 [M + 1], bin m = rows offsets[m] .. offsets[m + 1] - 1 -> [M, C] float64 DeviceArray (``out``: a [M, C]
+        DeviceArray, possibly a view of a wider or longer one).  op 'mean' | 'sum', NaN samples skipped (sd_resample_dev)."""
+        field, offsets, code, f32 = self._resample_args(field, offsets, op)
+        if not isinstance(field, DeviceArray):
+            field = self.to_device(field, field.dtype)
+        T, Cc = field.shape
+        M = len(offsets) - 1
+        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_resample: bad sizes (T={T}, C={Cc}, M={M})")
+        out = self._result_buffer(out, (M, Cc), True)
+        for name, a in (("field", field), ("out", out)):
+            if a.ctx is not self:
+                raise ValueError(f"sd_downscale: sd_resample: `{name}` belongs to another context")
+        check(self.lib.sd_resample_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(offsets), M, out.vptr, out.ld))
+        return out
+
+    def resample_host(self, field, offsets, op="mean"):
+        """host [T, C] -> host [M, C] through sd_resample (upload, run, download in one call)"""
+        field, offsets, code, f32 = self._resample_args(field, offsets, op)
+        if isinstance(field, DeviceArray):
+            raise ValueError("resample_host: expected a host array")
+        T, Cc = field.shape
+        M = len(offsets) - 1
+        out = np.empty((max(M, 0), Cc))
+        check(self.lib.sd_resample(self.handle, code, ptr(field), f32, T, Cc, ptr(offsets), M, ptr(out)))
+        return out
+
 
 _default_ctx = None
 

@@ -7,6 +7,7 @@ algorithmic bytes per cell / kernel time from HIP events on the e
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -129,9 +130,73 @@ def bench_regrid_e2e(ctx, args):
     return res
 
 
+def device_copy_ms(ctx, dst, src, nbytes, repeats):
+    """median HIP-event time of sd_memcpy_d2d over nbytes on the engine's stream: the rate a plain device copy of the source reaches"""
+    times = []
+    for _ in range(repeats + 1):  # (the first one warms up)
+        ctx.timer_start()
+        _lib.check(ctx.lib.sd_memcpy_d2d(ctx.handle, dst.vptr, src.vptr, nbytes))
+        times.append(ctx.timer_stop())
+    return float(np.median(times[1:])), [min(times[1:]), max(times[1:])]
+
+
+def bench_resample(ctx, args):
+    """resample_kernel: daily steps to 'MS' bins (14 600 -> 480) on 100 000 cells, float64 and float32 sources, mean; GB/s by algorithmic
+    bytes (the source read once + 8 * M * C written), beside sd_memcpy_d2d of the same source bytes in the same run, parity against the
+    oracle on the first 256 cells"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _resample_oracle as so
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    labels, offsets = time_bins(index, "MS")
+    M = len(labels)
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    d64, first = fill(C), fill(256).to_host()
+    out, spare = ctx.empty((M, C)), ctx.empty((T, C))
+    repeats = max(args.steps, 5)
+    res = {"workload": f"resample {T} daily steps -> {M} 'MS' bins x {C} cells, mean", "repeats": repeats}
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        if dtype == np.float32:
+            d = ctx.empty((T, C), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, d64.vptr, T * C, d.vptr))
+            ctx.synchronize()
+        else:
+            d = d64
+        host = first.astype(dtype)
+        ctx.resample(d, offsets, "mean", out=out)
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            ctx.resample(d, offsets, "mean", out=out)
+            times.append(ctx.prof()["resample_kernel"]["ms"])
+        ctx.prof_enable(False)
+        ms = float(np.median(times))
+        src_bytes = T * C * np.dtype(dtype).itemsize
+        nbytes = src_bytes + 8 * M * C
+        got, want = out.cells(0, 256).to_host(), so.resample(host, offsets, "mean")
+        with contextlib.redirect_stdout(sys.stderr):  # (the check prints its figure; stdout carries the JSON line alone)
+            ratio = so.check(got, want, host, offsets, "mean", f"bench {name}")
+        copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+        res[name] = {"kernel_ms": ms, "kernel_ms_min_max": [min(times), max(times)], "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                     "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "max_err_over_bound_first_256_cells": ratio, "parity": bool(ratio <= 1.0),
+                     "bit_identical_to_oracle": bool(np.array_equal(got, want, equal_nan=True)),
+                     "device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6},
+                     "kernel_over_copy_ms": ms / copy_ms, "GBps_over_copy_GBps": (nbytes / ms) / (src_bytes / copy_ms)}
+        if d is not d64:
+            d.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -142,8 +207,8 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload in ("regrid", "regrid_e2e"):
-        line = json.dumps((bench_regrid if args.workload == "regrid" else bench_regrid_e2e)(ctx, args))
+    if args.workload in ("regrid", "regrid_e2e", "resample"):
+        line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
