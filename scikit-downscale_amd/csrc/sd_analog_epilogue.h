@@ -89,36 +89,45 @@ __device__ void pure_analog_stats(const PredictArgs& pa, int k, int kind, int sa
 }
 
 // AnalogRegression for one query (gard.py:194-224): centred normal equations over the analogs selected by `use`
-// (all of them without a threshold; those above it otherwise, gard.py:215: ne of them, ne >= 1).
+// (all of them without a threshold; those above it otherwise, gard.py:215: ne of them, ne >= 1).  The analogs are shifted by
+// the first selected one before they are centred: a feature that has the same value in every selected analog (quantised data)
+// then gets an exactly zero row -- centred on the rounded mean it would keep a row at rounding level, which the equilibration
+// of minnorm_solve would blow up to a feature of its own.
 template <typename XV, typename YV, typename USE>
 __device__ void analog_regression(int k, int F, XV xv /* (i,f) */, YV yv /* (i) */, USE use /* (i) */, int ne, const double* q,
                                   double* pred, double* err) {
-    double xm[kMaxF], A[kMaxF][kMaxF + 1], coef[kMaxF];
+    double x0[kMaxF], xm[kMaxF], A[kMaxF][kMaxF + 1], coef[kMaxF];
+    int first = 0;
+    while (first < k - 1 && !use(first)) ++first;
+    const double y0 = yv(first);
     double ym = 0.0;
-    for (int f = 0; f < F; ++f) xm[f] = 0.0;
+    for (int f = 0; f < F; ++f) {
+        x0[f] = xv(first, f);
+        xm[f] = 0.0;
+    }
     for (int i = 0; i < k; ++i) {
         if (!use(i)) continue;
-        ym += yv(i);
-        for (int f = 0; f < F; ++f) xm[f] += xv(i, f);
+        ym += yv(i) - y0;
+        for (int f = 0; f < F; ++f) xm[f] += xv(i, f) - x0[f];
     }
-    ym /= (double)ne;
+    ym /= (double)ne;  // means of the shifted data
     for (int f = 0; f < F; ++f) xm[f] /= (double)ne;
     for (int f = 0; f < F; ++f)
         for (int g = 0; g <= F; ++g) A[f][g] = 0.0;
     for (int i = 0; i < k; ++i) {
         if (!use(i)) continue;
-        const double dy = yv(i) - ym;
+        const double dy = (yv(i) - y0) - ym;
         for (int f = 0; f < F; ++f) {
-            const double df = xv(i, f) - xm[f];
-            for (int g = f; g < F; ++g) A[f][g] += df * (xv(i, g) - xm[g]);
+            const double df = (xv(i, f) - x0[f]) - xm[f];
+            for (int g = f; g < F; ++g) A[f][g] += df * ((xv(i, g) - x0[g]) - xm[g]);
             A[f][F] += df * dy;
         }
     }
     for (int f = 0; f < F; ++f)
         for (int g = 0; g < f; ++g) A[f][g] = A[g][f];
     sdlsq::minnorm_solve(F, A, coef);  // like LinearRegression's lstsq (gard.py:215-217)
-    double icpt = ym;
-    for (int f = 0; f < F; ++f) icpt -= xm[f] * coef[f];
+    double icpt = y0 + ym;
+    for (int f = 0; f < F; ++f) icpt -= (x0[f] + xm[f]) * coef[f];
     double p = icpt;
     for (int f = 0; f < F; ++f) p += q[f] * coef[f];
     double ss = 0.0;

@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(kGroupedThreads) grouped_window_kernel(const d
         double coef[kMaxF], icpt = nan;
         const bool fit = ok && cn > 0.0;
         if (fit) {
-            double dm[F], A[kMaxF][kMaxF + 1];
+            double dm[F], raw[F], A[kMaxF][kMaxF + 1];
             const double em = acc[S::kSy] / cn;
 #pragma unroll
             for (int f = 0; f < F; ++f) dm[f] = acc[S::kSx + f] / cn;
@@ -155,11 +155,13 @@ __global__ void __launch_bounds__(kGroupedThreads) grouped_window_kernel(const d
                 A[f][F] = acc[S::kSxy + f] - cn * dm[f] * em;  // centred: sum d e - n mean(d) mean(e)
 #pragma unroll
                 for (int h = f; h < F; ++h) {
+                    if (h == f) raw[f] = acc[q];
                     const double v = acc[q++] - cn * dm[f] * dm[h];
                     A[f][h] = v;
                     A[h][f] = v;
                 }
             }
+            sdlsq::clear_unresolved(F, A, raw, cn);  // a feature that is constant over the window's samples
             sdlsq::minnorm_solve(F, A, coef);
             icpt = y0 + em;
 #pragma unroll

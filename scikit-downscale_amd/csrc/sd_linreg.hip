@@ -129,19 +129,22 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
     }
     const double em = slice_sum(sy, part, cx, ty) / n, ym = y0 + em;
     const double Syy = slice_sum(syy, part, cx, ty) - n * em * em;  // centred: sum e^2 - n mean(e)^2
-    double A[kMaxF][kMaxF + 1];
+    double A[kMaxF][kMaxF + 1], raw[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         A[f][F] = slice_sum(b[f], part, cx, ty) - n * dm[f] * em;  // centred: sum d e - n mean(d) mean(e)
 #pragma unroll
         for (int g = f; g < F; ++g) {
-            const double v = slice_sum(S[f][g], part, cx, ty) - n * dm[f] * dm[g];
+            const double s = slice_sum(S[f][g], part, cx, ty);
+            if (g == f) raw[f] = s;
+            const double v = s - n * dm[f] * dm[g];
             A[f][g] = v;
             A[g][f] = v;
         }
     }
     if (ty == 0) {
         double coef[kMaxF], sxy[F];
+        sdlsq::clear_unresolved(F, A, raw, n);  // a feature that is constant over the samples of the linear model
 #pragma unroll
         for (int f = 0; f < F; ++f) sxy[f] = A[f][F];  // (the solver works in place)
         sdlsq::minnorm_solve(F, A, coef);

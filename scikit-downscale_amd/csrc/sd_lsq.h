@@ -1,7 +1,14 @@
 // Minimum-norm least squares on centred normal equations (device code shared by the analog regression epilogue and
-// the batched linear regression).
+// the batched linear regression).  The header also compiles with a plain host compiler (tests/lsq_check.cpp runs the same text
+// on the CPU against an exact reference): the device qualifier is attached under hipcc only.
 #pragma once
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define SD_LSQ_FN __device__ inline
+#else
+#include <math.h>
+#define SD_LSQ_FN inline
+#endif
 
 namespace sdlsq {
 
@@ -33,7 +40,13 @@ namespace sdlsq {
 // equilibrated matrix is <= 1e-12 of the largest (correlation beyond 1 - 1e-12: the normal equations cannot resolve
 // more), a constant feature gets coefficient 0; among the solutions of a rank-deficient system the one of minimum norm in
 // the original coordinates is returned, like lstsq does.  S is overwritten.
-__device__ inline void minnorm_solve(int F, double (&A)[kMaxF][kMaxF + 1], double* coef) {
+// Stated limit (not asserted by the tests): "minimum norm in the original coordinates" is itself ill-conditioned when the null
+// space is not axis-aligned and the feature scales differ by many orders of magnitude.  With scales 2^-17..2^17 and designs of
+// rank 1..F-1 (correlation condition <= 1e4) the prediction at a query off the row space is off by up to a few 1e-4 of
+// max|y - mean(y)|, for this solver and for numpy's lstsq on the data matrix alike (315 designs: 2.2e-4 and 1.7e-4; another
+// sample of such designs: about 5e-5 and 5e-4).  Full rank, constant columns and scales within 2^-3..2^3 stay within
+// ~500 eps kappa (tests/test_lsq_host.py, profiles/lsq/README.md).
+SD_LSQ_FN void minnorm_solve(int F, double (&A)[kMaxF][kMaxF + 1], double* coef) {
     double V[kMaxF][kMaxF], bvec[kMaxF], sc[kMaxF];
     for (int f = 0; f < F; ++f) sc[f] = A[f][f] > 0.0 ? 1.0 / sqrt(A[f][f]) : 0.0;
     for (int f = 0; f < F; ++f) {
@@ -117,8 +130,26 @@ __device__ inline void minnorm_solve(int F, double (&A)[kMaxF][kMaxF + 1], doubl
     }
 }
 
+// For callers that centre one-pass sums, S_ff = sum d_f^2 - n mean(d_f)^2 (linreg_fit_kernel, grouped_window_kernel): a feature
+// with the same value in every sample leaves S_ff at the rounding level of the two terms, of either sign -- |S_ff| <= 3 (n + 1) u
+// sum d_f^2 for u = 2^-53 (n additions and one product per term, the division and the square of the mean).  The equilibration of
+// minnorm_solve would blow such a row up to a feature of its own, so it is cleared here, with its right-hand side: the feature is
+// constant and gets coefficient 0.  raw[f] = sum d_f^2 before centring.  A feature that really varies by less than this against
+// its distance from the shift is not resolved by the sums either.
+SD_LSQ_FN void clear_unresolved(int F, double (&A)[kMaxF][kMaxF + 1], const double* raw, double n) {
+    const double lim = 2.0 * (n + 1.0) * 2.220446049250313e-16;
+    for (int f = 0; f < F; ++f) {
+        if (!(A[f][f] <= lim * raw[f])) continue;  // (a NaN row stays: the cell is flagged by its caller)
+        for (int g = 0; g < F; ++g) {
+            A[f][g] = 0.0;
+            A[g][f] = 0.0;
+        }
+        A[f][F] = 0.0;
+    }
+}
+
 // Cholesky solve of the symmetric positive definite n x n system H d = r (n <= kMaxF + 1); false if a pivot is not positive
-__device__ inline bool chol_solve(int n, double (&H)[kMaxF + 1][kMaxF + 1], const double* r, double* d) {
+SD_LSQ_FN bool chol_solve(int n, double (&H)[kMaxF + 1][kMaxF + 1], const double* r, double* d) {
     for (int j = 0; j < n; ++j) {
         double s = H[j][j];
         for (int p = 0; p < j; ++p) s -= H[j][p] * H[j][p];
@@ -145,7 +176,7 @@ __device__ inline bool chol_solve(int n, double (&H)[kMaxF + 1][kMaxF + 1], cons
 }
 
 // log(1 + exp(z)) and the logistic function without overflow
-__device__ inline double softplus(double z) { return z > 0.0 ? z + log1p(exp(-z)) : log1p(exp(z)); }
-__device__ inline double sigmoid(double z) { return 0.5 * (1.0 + tanh(0.5 * z)); }
+SD_LSQ_FN double softplus(double z) { return z > 0.0 ? z + log1p(exp(-z)) : log1p(exp(z)); }
+SD_LSQ_FN double sigmoid(double z) { return 0.5 * (1.0 + tanh(0.5 * z)); }
 
 }  // namespace sdlsq

@@ -75,7 +75,9 @@ def main(n_cases=40, seed=0):
             Xq = Xq[sel[:200]]
             out, _ = ctx.analogreg_predict(st, Xq, k)
             # k <= F + 1 is under-determined: the reference's lstsq cut-off (eps * max(k, F)) sits at the rounding level of
-            # the centred analogs, its answer flips between the minimum-norm solution and noise -- unpinned
+            # the centred analogs, its answer flips between the minimum-norm solution and noise -- not compared here; pinned
+            # against the exact rational pseudo-inverse, quantised data included, by tests/test_gpu_lsq.py
+            # (test_analog_regression_few_analogs)
             if k >= F + 2 and not quant:
                 exp = ao.pointwise_analog(X, y, Xq, k, 3, regression=True)
                 assert_close(out, exp, what=f"case {it} analogreg F={F} T={T} k={k}")
