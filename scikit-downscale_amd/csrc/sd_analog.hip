@@ -42,6 +42,7 @@
 #include "sd_analog_plan.h"
 #include "sd_lsq.h"
 #include "sd_sortnet.h"
+#include "sd_state.h"
 #include "sd_wave.h"
 #include "sd_wsort.h"
 
@@ -87,28 +88,57 @@ __global__ void __launch_bounds__(256) analog_status_public_kernel(const int32_t
 
 dim3 grid_of(const AnalogLaunch& L) { return dim3((unsigned)L.gx, (unsigned)L.gy, (unsigned)L.gz); }
 
+// The device buffers of a state, each under its name.  Every state has kX, kY and kStatus; which of the others a fit or a first
+// predict allocates is the plan's decision (sd_analog_fit_dev, build_prefix_sums), and sd_state_destroy skips the ones that never
+// were.  A new buffer gets a name before kAnalogBufs and a line here; one without a line is caught below.
+enum AnalogBuf { kX, kY, kStatus, kXs, kXi, kYx, kYbar, kPq, kRx, kXbar, kPs, kAnalogBufs };
+std::vector<sd_buf> analog_bufs(const sd_analog_state* st) {
+    const size_t T = (size_t)st->T, C = (size_t)st->C, F = (size_t)st->F;
+    std::vector<sd_buf> b(kAnalogBufs, sd_buf{nullptr, 0, false});
+    b[kX] = sd_buf_of(st->X, T * F * C);
+    b[kY] = sd_buf_of(st->y, T * C);
+    b[kStatus] = sd_buf_of(st->status, C, true);
+    b[kXs] = sd_buf_of(st->xs, T * C);
+    b[kXi] = sd_buf_of(st->xi, T * C);
+    b[kYx] = sd_buf_of(st->yx, T * C);
+    b[kYbar] = sd_buf_of(st->ybar, C);
+    b[kPq] = sd_buf_of(st->pq, 2 * (T + 1) * C);
+    b[kRx] = sd_buf_of(st->rx, (T + 1) * C);
+    b[kXbar] = sd_buf_of(st->xbar, C);
+    b[kPs] = sd_buf_of(st->ps, T * F * C);
+    for (const sd_buf& x : b)
+        if (!x.slot) abort();  // (a name without a line above)
+    return b;
+}
+// Allocates the named buffers.  The state may be const (build_prefix_sums gets it from a predict call): sd_buf_of keeps the address
+// of the pointer field as a plain void**, which is the const_cast of a late allocation; every state is created non-const by fit.
+int analog_alloc(sd_ctx* ctx, const sd_analog_state* st, std::initializer_list<AnalogBuf> which) {
+    const std::vector<sd_buf> all = analog_bufs(st);
+    std::vector<sd_buf> some;
+    for (AnalogBuf name : which) some.push_back(all[name]);
+    return sd_state_alloc(ctx, some);
+}
+
 // exclusive prefix sums of the centred analog values (analog_prefix_kernel) and the cross term of the one-feature regression
 // (analog_rx_kernel), built when a kernel that reads them from memory first runs on a state (calls on a context are serialised)
 int build_prefix_sums(sd_ctx* ctx, const sd_analog_state* st, const AnalogPlan& pl) {
-    sd_analog_state* ms = const_cast<sd_analog_state*>(st);
     const int64_t T = st->T, C = st->C;
     if (pl.need_pq) {
         const AnalogLaunch L = analog_launches::prefix_sums(T, C, ctx->cu_count, ctx->lds_max);
-        SD_HIP(sd_pool_malloc(ctx, (void**)&ms->pq, sizeof(double) * 2 * (size_t)(T + 1) * C));
+        SD_TRY(analog_alloc(ctx, st, {kPq}));
         if (L.lds != 0) {
             SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_prefix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-            SD_LAUNCH(ctx, "analog_prefix_kernel", analog_prefix_kernel, grid_of(L), dim3(L.block), L.lds, (const double*)st->yx, T, C, ms->pq, ms->ybar, 1);
+            SD_LAUNCH(ctx, "analog_prefix_kernel", analog_prefix_kernel, grid_of(L), dim3(L.block), L.lds, (const double*)st->yx, T, C, st->pq, st->ybar, 1);
         } else {
-            SD_LAUNCH(ctx, "analog_prefix_kernel", analog_prefix_direct_kernel, grid_of(L), dim3(L.block), 0, (const double*)st->yx, T, C, ms->pq, ms->ybar, 1);
+            SD_LAUNCH(ctx, "analog_prefix_kernel", analog_prefix_direct_kernel, grid_of(L), dim3(L.block), 0, (const double*)st->yx, T, C, st->pq, st->ybar, 1);
         }
     }
     if (pl.need_rx) {
         const AnalogLaunch L = analog_launches::rx(T, C, ctx->cu_count);
-        SD_HIP(sd_pool_malloc(ctx, (void**)&ms->rx, sizeof(double) * (size_t)(T + 1) * C));
-        SD_HIP(sd_pool_malloc(ctx, (void**)&ms->xbar, sizeof(double) * C));
+        SD_TRY(analog_alloc(ctx, st, {kRx, kXbar}));
         SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&analog_rx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
         SD_LAUNCH(ctx, "analog_rx_kernel", analog_rx_kernel, grid_of(L), dim3(L.block), L.lds, (const double*)st->xs, (const double*)st->yx,
-                  (const double*)st->ybar, T, C, ms->rx, ms->xbar);
+                  (const double*)st->ybar, T, C, st->rx, st->xbar);
     }
     return SD_OK;
 }
@@ -269,8 +299,7 @@ int predict_common(int mode, sd_ctx* ctx, const sd_analog_state* st, const doubl
     const int64_t C = st->C, T = st->T;
     const int F = st->F;
     sd_scratch status_p, sc_d, sc_i, status_pub;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     SD_HIP(sc_d.alloc(ctx, sizeof(double) * (size_t)pl.nb * k * pl.nthr));
     SD_HIP(sc_i.alloc(ctx, sizeof(int32_t) * (size_t)pl.nb * k * pl.nthr));
     int32_t* sp = status_p.as<int32_t>();
@@ -318,26 +347,14 @@ int predict_host(int mode, sd_ctx* ctx, const sd_analog_state* st, const double*
                  int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xq && out, "sd_analog_predict: NULL argument");
     SD_CHECK_ARG(Tq > 0 && k >= 1, "sd_analog_predict: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
     const int64_t C = st->C;
-    sd_scratch dq, dout, dinds, ddist, dsamp;
-    const size_t qb = sizeof(double) * (size_t)Tq * st->F * C, ob = sizeof(double) * (size_t)Tq * 3 * C;
-    SD_HIP(dq.alloc(ctx, qb));
-    SD_HIP(dout.alloc(ctx, ob));
-    SD_TRY(sd_copy_h2d(ctx, dq.p, Xq, qb));
-    if (inds) SD_HIP(dinds.alloc(ctx, sizeof(int64_t) * (size_t)Tq * k * C));
-    if (dist) SD_HIP(ddist.alloc(ctx, sizeof(double) * (size_t)Tq * k * C));
-    if (sample) {
-        SD_HIP(dsamp.alloc(ctx, sizeof(int32_t) * (size_t)Tq * C));
-        SD_TRY(sd_copy_h2d(ctx, dsamp.p, sample, sizeof(int32_t) * (size_t)Tq * C));
-    }
-    SD_TRY(predict_common(mode, ctx, st, dq.as<double>(), C, Tq, k, kind, has_thresh, thresh, dsamp.as<int32_t>(), C,
-                          dout.as<double>(), C, dinds.as<int64_t>(), ddist.as<double>(), cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, ob));
-    if (inds) SD_HIP(hipMemcpyAsync(inds, dinds.p, sizeof(int64_t) * (size_t)Tq * k * C, hipMemcpyDeviceToHost, ctx->stream));
-    if (dist) SD_HIP(hipMemcpyAsync(dist, ddist.p, sizeof(double) * (size_t)Tq * k * C, hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const size_t cells = (size_t)Tq * C;
+    const sd_host_field f[] = {sd_in(Xq, sizeof(double) * cells * st->F), sd_in(sample, sizeof(int32_t) * cells), sd_out(out, sizeof(double) * cells * 3),
+                               sd_out(inds, sizeof(int64_t) * cells * k), sd_out(dist, sizeof(double) * cells * k)};  // (sample, inds, dist may be NULL)
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return predict_common(mode, ctx, st, (const double*)d[0], C, Tq, k, kind, has_thresh, thresh, (const int32_t*)d[1], C, (double*)d[2], C,
+                              (int64_t*)d[3], (double*)d[4], cell_status);
+    });
 }
 
 // columns `list[0 .. nw)` of a [R, ld] field <-> a packed [R, nw] field (cells the fused kernel handed back)
@@ -489,26 +506,7 @@ int fit_predict_dev(sd_ctx* ctx, const double* X, const double* y, int64_t ld, i
 
 extern "C" {
 
-int sd_analog_state_destroy(sd_analog_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    sd_pool_release(st->ctx, st->X);
-    sd_pool_release(st->ctx, st->y);
-    sd_pool_release(st->ctx, st->status);
-    sd_pool_release(st->ctx, st->xs);
-    sd_pool_release(st->ctx, st->xi);
-    sd_pool_release(st->ctx, st->yx);
-    sd_pool_release(st->ctx, st->pq);
-    sd_pool_release(st->ctx, st->ybar);
-    sd_pool_release(st->ctx, st->rx);
-    sd_pool_release(st->ctx, st->xbar);
-    sd_pool_release(st->ctx, st->ps);
-    delete st;
-    return SD_OK;
-}
+int sd_analog_state_destroy(sd_analog_state* st) { return sd_state_destroy(st, analog_bufs); }
 
 int sd_analog_state_info(const sd_analog_state* st, int64_t* T, int* F, int64_t* C) {
     SD_CHECK_ARG(st, "state is NULL");
@@ -534,11 +532,8 @@ int sd_analog_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
     st->T = T;
     st->F = F;
     st->C = C;
-    auto body = [&]() -> int {
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->X, sizeof(double) * (size_t)T * F * C));
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->y, sizeof(double) * (size_t)T * C));
-        SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * C));
-        SD_HIP(hipMemsetAsync(st->status, 0, sizeof(int32_t) * C, ctx->stream));
+    return sd_state_build(st, sd_analog_state_destroy, out, [&]() -> int {
+        SD_TRY(analog_alloc(ctx, st, {kX, kY, kStatus}));
         sd_scratch runs_buf, odd_buf;
         if (pl.tiled && runs_buf.alloc(ctx, sizeof(double) * (size_t)pl.np_runs * (size_t)C) != hipSuccess) {
             (void)hipGetLastError();  // no room for the presorted runs: the plan with the two transposes
@@ -564,10 +559,7 @@ int sd_analog_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
             // sorted view for the 1-D fast path: values, original indices, and y in the same order
             // (no prefix sums yet: the BASELINE path -- analog_f1_mean3_kernel -- builds its own on chip; the kernels
             // that read them from memory get them from build_prefix_sums on their first call)
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->xs, sizeof(double) * (size_t)T * C));
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->xi, sizeof(int32_t) * (size_t)T * C));
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->yx, sizeof(double) * (size_t)T * C));
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->ybar, sizeof(double) * C));
+            SD_TRY(analog_alloc(ctx, st, {kXs, kXi, kYx, kYbar}));
             Sort2Args a{st->X, T, 0, st->y, T, C, st->xs, st->xi, st->yx, nullptr, st->ybar};
             if (pl.tiled) {
                 a.runs = runs_buf.as<double>();
@@ -584,8 +576,7 @@ int sd_analog_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
             const AnalogLaunch L = analog_launches::gather_sorted(C, ctx->cu_count);
             sd_scratch keys;
             SD_HIP(keys.alloc(ctx, sizeof(double) * (size_t)T * C));
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->xi, sizeof(int32_t) * (size_t)T * C));
-            SD_HIP(sd_pool_malloc(ctx, (void**)&st->ps, sizeof(double) * (size_t)T * F * C));
+            SD_TRY(analog_alloc(ctx, st, {kXi, kPs}));
             Sort2Args a{st->X, (int64_t)F * T, 1, nullptr, T, C, keys.as<double>(), st->xi, nullptr, nullptr, nullptr};
             a.tagged = pl.tagged;
             a.count = dev.count;
@@ -596,26 +587,14 @@ int sd_analog_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int
         }
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    int rc = body();
-    if (rc != SD_OK) {
-        sd_analog_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 int sd_analog_fit(sd_ctx* ctx, const double* X, const double* y, int64_t T, int F, int64_t C, sd_analog_state** out) {
     SD_CHECK_ARG(ctx && X && y && out, "sd_analog_fit: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0 && F >= 1, "sd_analog_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    SD_HIP(dX.alloc(ctx, sizeof(double) * (size_t)T * F * C));
-    SD_HIP(dy.alloc(ctx, sizeof(double) * (size_t)T * C));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, sizeof(double) * (size_t)T * F * C));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, sizeof(double) * (size_t)T * C));
-    return sd_analog_fit_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, F, C, out);
+    const sd_host_field f[] = {sd_in(X, sizeof(double) * (size_t)T * F * C), sd_in(y, sizeof(double) * (size_t)T * C)};
+    return with_device_copies(ctx, f, [&](void* const* d) { return sd_analog_fit_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, F, C, out); });
 }
 
 int sd_analog_predict_dev(sd_ctx* ctx, const sd_analog_state* st, const double* Xq_dev, int64_t ld, int64_t Tq, int k,
@@ -641,20 +620,12 @@ int sd_analog_fit_predict(sd_ctx* ctx, const double* X, const double* y, int64_t
                           int kind, int has_thresh, double thresh, double* out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && X && y && Xq && out, "sd_analog_fit_predict: NULL argument");
     SD_CHECK_ARG(T > 0 && C > 0 && Tq > 0 && F >= 1, "sd_analog_fit_predict: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy, dq, dout;
-    const size_t xb = sizeof(double) * (size_t)T * F * C, yb = sizeof(double) * (size_t)T * C, qb = sizeof(double) * (size_t)Tq * F * C,
-                 ob = sizeof(double) * (size_t)Tq * 3 * C;
-    SD_HIP(dX.alloc(ctx, xb));
-    SD_HIP(dy.alloc(ctx, yb));
-    SD_HIP(dq.alloc(ctx, qb));
-    SD_HIP(dout.alloc(ctx, ob));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, X, xb));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, yb));
-    SD_TRY(sd_copy_h2d(ctx, dq.p, Xq, qb));
-    SD_TRY(fit_predict_dev(ctx, dX.as<double>(), dy.as<double>(), C, T, F, C, dq.as<double>(), C, Tq, k, kind, has_thresh, thresh, dout.as<double>(), C,
-                           cell_status));
-    return sd_copy_d2h(ctx, out, dout.p, ob);
+    const sd_host_field f[] = {sd_in(X, sizeof(double) * (size_t)T * F * C), sd_in(y, sizeof(double) * (size_t)T * C),
+                               sd_in(Xq, sizeof(double) * (size_t)Tq * F * C), sd_out(out, sizeof(double) * (size_t)Tq * 3 * C)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return fit_predict_dev(ctx, (const double*)d[0], (const double*)d[1], C, T, F, C, (const double*)d[2], C, Tq, k, kind, has_thresh, thresh,
+                               (double*)d[3], C, cell_status);
+    });
 }
 
 int sd_analogreg_predict_dev(sd_ctx* ctx, const sd_analog_state* st, const double* Xq_dev, int64_t ld, int64_t Tq,

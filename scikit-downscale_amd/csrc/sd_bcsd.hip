@@ -21,6 +21,7 @@
 #include "sd_bcsd_rs.h"
 #include "sd_internal.h"
 #include "sd_sortnet.h"
+#include "sd_state.h"
 
 namespace {
 
@@ -811,11 +812,18 @@ int launch_long_predict(sd_ctx* ctx, const BcsdLaunch& L, const sdrs::Params& p,
         default: SD_TRY(fn<1>(__VA_ARGS__)); break;        \
     }
 
+// the device buffers of a state; the climatologies and the trend lines start cleared (a fit writes the groups it has, and the lines
+// only with detrend)
+std::vector<sd_buf> bcsd_bufs(const sd_bcsd_state* st) {
+    const size_t C = (size_t)st->C, G = (size_t)st->G;
+    return {sd_buf_of(st->ys, (size_t)st->T * C), sd_buf_of(st->x_climo, G * C, true), sd_buf_of(st->y_climo, G * C, true),
+            sd_buf_of(st->y_trend, 2 * G * C, true), sd_buf_of(st->status, C), sd_buf_of(st->goff_dev, G + 1)};
+}
+
+// a state with its sizes and options, no buffer yet (sd_state_alloc on bcsd_bufs, inside the caller's sd_state_build)
 // options = SD_BCSD_RETURN_ANOMS | SD_BCSD_QM_DETREND bits (the public `return_anoms` argument of the fit entry points)
-int alloc_state(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int options, sd_bcsd_state** out) {
-    *out = nullptr;
+int new_state(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int options, sd_bcsd_state** out) {
     SD_CHECK_ARG(options >= 0 && options <= 3, "options %d: expected a combination of SD_BCSD_RETURN_ANOMS and SD_BCSD_QM_DETREND", options);
-    const int return_anoms = options & SD_BCSD_RETURN_ANOMS;
     sd_bcsd_state* st = new sd_bcsd_state();
     st->detrend = (options & SD_BCSD_QM_DETREND) ? 1 : 0;
     st->ctx = ctx;
@@ -823,18 +831,29 @@ int alloc_state(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int options,
     st->G = G;
     st->T = T;
     st->C = C;
-    st->return_anoms = return_anoms;
+    st->return_anoms = options & SD_BCSD_RETURN_ANOMS;
     *out = st;
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->ys, sizeof(double) * T * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->x_climo, sizeof(double) * G * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->y_climo, sizeof(double) * G * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->y_trend, sizeof(double) * 2 * G * C));
-    SD_HIP(hipMemsetAsync(st->y_trend, 0, sizeof(double) * 2 * G * C, ctx->stream));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->status, sizeof(int32_t) * C));
-    SD_HIP(sd_pool_malloc(ctx, (void**)&st->goff_dev, sizeof(int32_t) * (G + 1)));
-    SD_HIP(hipMemsetAsync(st->x_climo, 0, sizeof(double) * G * C, ctx->stream));
-    SD_HIP(hipMemsetAsync(st->y_climo, 0, sizeof(double) * G * C, ctx->stream));
     return SD_OK;
+}
+
+// the checks the two resident fits share; op: the entry point's name in the messages, pointers: its own pointer arguments all there
+int check_fit_args(const char* op, bool pointers, int kind, const double* X_dev, int G, int64_t T, int64_t C, int64_t ld) {
+    SD_CHECK_ARG(pointers, "%s: NULL argument", op);
+    SD_CHECK_ARG(kind == SD_BCSD_TAS || kind == SD_BCSD_PR, "%s: unknown kind %d", op, kind);
+    SD_CHECK_ARG(kind == SD_BCSD_PR || X_dev, "%s: BcsdTemperature needs X", op);
+    SD_CHECK_ARG(T > 0 && C > 0 && G > 0 && ld >= C, "%s: bad sizes T=%lld C=%lld G=%d ld=%lld", op, (long long)T, (long long)C, G,
+                 (long long)ld);
+    return SD_OK;
+}
+
+// The host-buffer form of the two fits: X (absent for a precipitation fit) and y go up, `call` is the resident form on them
+template <class Call>
+int fit_with_device_copies(sd_ctx* ctx, const char* op, bool pointers, const double* X, const double* y, int64_t T, int64_t C, Call call) {
+    SD_CHECK_ARG(pointers, "%s: NULL argument", op);
+    SD_CHECK_ARG(T > 0 && C > 0, "%s: bad sizes", op);
+    const size_t bytes = sizeof(double) * (size_t)T * (size_t)C;
+    const sd_host_field f[] = {sd_in(X, bytes), sd_in(y, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) { return call((const double*)d[0], (const double*)d[1]); });
 }
 
 // samples of every group (host offsets [G+1])
@@ -932,29 +951,11 @@ static int finish_predict(sd_ctx* ctx, int64_t C, const int32_t* status_f, const
 
 extern "C" {
 
-int sd_bcsd_state_destroy(sd_bcsd_state* st) {
-    if (!st) return SD_OK;
-    if (st->ctx) {
-        (void)hipSetDevice(st->ctx->device);
-        (void)hipStreamSynchronize(st->ctx->stream);
-    }
-    sd_pool_release(st->ctx, st->ys);
-    sd_pool_release(st->ctx, st->x_climo);
-    sd_pool_release(st->ctx, st->y_climo);
-    sd_pool_release(st->ctx, st->y_trend);
-    sd_pool_release(st->ctx, st->status);
-    sd_pool_release(st->ctx, st->goff_dev);
-    delete st;
-    return SD_OK;
-}
+int sd_bcsd_state_destroy(sd_bcsd_state* st) { return sd_state_destroy(st, bcsd_bufs); }
 
 int sd_bcsd_fit_dev(sd_ctx* ctx, int kind, const double* X_dev, const double* y_dev, int64_t ld,
                     const int32_t* group_id, int G, int64_t T, int64_t C, int return_anoms, sd_bcsd_state** out) {
-    SD_CHECK_ARG(ctx && y_dev && group_id && out, "sd_bcsd_fit: NULL argument");
-    SD_CHECK_ARG(kind == SD_BCSD_TAS || kind == SD_BCSD_PR, "sd_bcsd_fit: unknown kind %d", kind);
-    SD_CHECK_ARG(kind == SD_BCSD_PR || X_dev, "sd_bcsd_fit: BcsdTemperature needs X");
-    SD_CHECK_ARG(T > 0 && C > 0 && G > 0 && ld >= C, "sd_bcsd_fit: bad sizes T=%lld C=%lld G=%d ld=%lld", (long long)T,
-                 (long long)C, G, (long long)ld);
+    SD_TRY(check_fit_args("sd_bcsd_fit", ctx && y_dev && group_id && out, kind, X_dev, G, T, C, ld));
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
     DevGroupTable gt;
@@ -989,7 +990,10 @@ static int predict_with_table(sd_ctx* ctx, const sd_bcsd_state* st, const double
     return SD_OK;
 }
 
-// cells that are masked / failed in fit (status_f) or non-finite in predict (status_p) -> NaN columns; public status codes to the host
+// cells that are masked / failed in fit (status_f) or non-finite in predict (status_p) -> NaN columns; public status codes to the host.
+// The fold stays status_public_kernel and is not sd_status_fold: that one reports the or of the two bit sets, this one the fit's
+// code and, only for a cell the fit left clean, the call's.  A cell with a bad climatology and a NaN in the predict input is
+// SD_CELL_BAD_CLIMO here; or'ed bits would make it SD_CELL_NONFINITE.
 static int finish_predict(sd_ctx* ctx, int64_t C, const int32_t* status_f, const int32_t* status_p, int64_t Tp, double* out_dev,
                           int64_t ld_out, int32_t* cell_status) {
     sd_scratch status_pub;
@@ -1018,14 +1022,11 @@ static int fit_with_table(sd_ctx* ctx, int kind, const double* X_dev, const doub
         plan = &own;
     }
     sd_bcsd_state* st = nullptr;
-    int rc = alloc_state(ctx, kind, G, T, C, options, &st);
-    if (rc != SD_OK) {
-        sd_bcsd_state_destroy(st);
-        return rc;
-    }
+    SD_TRY(new_state(ctx, kind, G, T, C, options, &st));
     st->goff = gt.host_off;
     st->nmax = gt.nmax;
-    auto body = [&]() -> int {
+    return sd_state_build(st, sd_bcsd_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, bcsd_bufs(st)));
         SD_HIP(hipMemcpyAsync(st->goff_dev, gt.off.p, sizeof(int32_t) * (G + 1), hipMemcpyDeviceToDevice, ctx->stream));
         const double* first = X_dev ? X_dev : y_dev;
         SD_LAUNCH(ctx, "bcsd_mask_kernel", bcsd_mask_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, first, C,
@@ -1037,14 +1038,7 @@ static int fit_with_table(sd_ctx* ctx, int kind, const double* X_dev, const doub
         SD_TRY(run_launches(ctx, *plan, true, p, st));
         SD_HIP(hipStreamSynchronize(ctx->stream));
         return SD_OK;
-    };
-    rc = body();
-    if (rc != SD_OK) {
-        sd_bcsd_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 extern "C" {
@@ -1058,8 +1052,7 @@ int sd_bcsd_predict_dev(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp_d
     DevGroupTable gt;
     SD_TRY(upload_group_table(ctx, group_id_p, Tp, st->G, &gt));
     sd_scratch status_p;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     SD_TRY(predict_with_table(ctx, st, Xp_dev, ld, gt, out_dev, ld_out, status_p.as<int32_t>()));
     return finish_predict(ctx, C, st->status, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
 }
@@ -1077,8 +1070,7 @@ int sd_bcsd_predict_trend_dev(sd_ctx* ctx, const sd_bcsd_state* st, const double
     SD_TRY(upload_group_table(ctx, group_id_p, Tp, st->G, &gq));
     SD_TRY(upload_group_table(ctx, trend_group_id, Tp, G_trend, &gr));
     sd_scratch status_p, u, shift, gidq;
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     SD_HIP(u.alloc(ctx, sizeof(double) * (size_t)Tp * (size_t)C));
     SD_HIP(shift.alloc(ctx, sizeof(double) * (size_t)Tp * (size_t)C));
     SD_HIP(gidq.alloc(ctx, sizeof(int32_t) * (size_t)Tp));
@@ -1123,8 +1115,7 @@ int sd_bcsd_fit_predict_dev(sd_ctx* ctx, int kind, const double* X_dev, const do
         SD_TRY(fit_with_table(ctx, kind, X_dev, y_dev, ld, gf, G, C, return_anoms, &st, &plan));
         const auto predict = [&]() -> int {
             sd_scratch status_p;
-            SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-            SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+            SD_TRY(sd_status_scratch(ctx, status_p, C));
             SD_TRY(predict_with_table(ctx, st, Xp_dev, ld_p, gp, out_dev, ld_out, status_p.as<int32_t>(), &plan));
             return finish_predict(ctx, C, st->status, status_p.as<int32_t>(), Tp, out_dev, ld_out, cell_status);
         };
@@ -1137,8 +1128,7 @@ int sd_bcsd_fit_predict_dev(sd_ctx* ctx, int kind, const double* X_dev, const do
     // restores the shift.
     sd_scratch status_f, status_p;
     SD_HIP(status_f.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(status_p.alloc(ctx, sizeof(int32_t) * C));
-    SD_HIP(hipMemsetAsync(status_p.p, 0, sizeof(int32_t) * C, ctx->stream));
+    SD_TRY(sd_status_scratch(ctx, status_p, C));
     QTables qt;
     if (!plan.identity) SD_TRY(build_q_tables(ctx, gf.host_off, gp.host_off, G, &qt));
     const double* first = X_dev ? X_dev : y_dev;
@@ -1154,18 +1144,9 @@ int sd_bcsd_fit_predict_dev(sd_ctx* ctx, int kind, const double* X_dev, const do
 
 int sd_bcsd_fit(sd_ctx* ctx, int kind, const double* X, const double* y, const int32_t* group_id, int G, int64_t T,
                 int64_t C, int return_anoms, sd_bcsd_state** out) {
-    SD_CHECK_ARG(ctx && y && group_id && out, "sd_bcsd_fit: NULL argument");
-    SD_CHECK_ARG(T > 0 && C > 0, "sd_bcsd_fit: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    const size_t bytes = sizeof(double) * (size_t)T * (size_t)C;
-    if (X) {
-        SD_HIP(dX.alloc(ctx, bytes));
-        SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    }
-    SD_HIP(dy.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, bytes));
-    return sd_bcsd_fit_dev(ctx, kind, dX.as<double>(), dy.as<double>(), C, group_id, G, T, C, return_anoms, out);
+    return fit_with_device_copies(ctx, "sd_bcsd_fit", ctx && y && group_id && out, X, y, T, C, [&](const double* dX, const double* dy) {
+        return sd_bcsd_fit_dev(ctx, kind, dX, dy, C, group_id, G, T, C, return_anoms, out);
+    });
 }
 
 // Host-buffer predict.  Large grids go through in blocks of cells, pipelined over the two directions of the PCIe link: while the
@@ -1181,14 +1162,10 @@ int sd_bcsd_predict(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, cons
     const size_t bytes = sizeof(double) * (size_t)Tp * (size_t)C;
     const int nblk = (bytes >= ((size_t)256 << 20) && C >= 1024) ? 4 : 1;
     if (nblk == 1) {
-        sd_scratch dX, dout;
-        SD_HIP(dX.alloc(ctx, bytes));
-        SD_HIP(dout.alloc(ctx, bytes));
-        SD_TRY(sd_copy_h2d(ctx, dX.p, Xp, bytes));
-        SD_TRY(sd_bcsd_predict_dev(ctx, st, dX.as<double>(), C, group_id_p, Tp, dout.as<double>(), C, cell_status));
-        SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
-        return SD_OK;
+        const sd_host_field f[] = {sd_in(Xp, bytes), sd_out(out, bytes)};
+        return with_device_copies(ctx, f, [&](void* const* d) {
+            return sd_bcsd_predict_dev(ctx, st, (const double*)d[0], C, group_id_p, Tp, (double*)d[1], C, cell_status);
+        });
     }
     sd_advise_result_buffer(out, bytes);
     const size_t pitch = sizeof(double) * (size_t)C;
@@ -1246,11 +1223,7 @@ int sd_bcsd_predict(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, cons
 
 int sd_bcsd_fit_groups_dev(sd_ctx* ctx, int kind, const double* X_dev, const double* y_dev, int64_t ld, const int32_t* group_order,
                            const int64_t* group_offsets, int G, int64_t T, int64_t C, int return_anoms, sd_bcsd_state** out) {
-    SD_CHECK_ARG(ctx && y_dev && group_order && group_offsets && out, "sd_bcsd_fit_groups: NULL argument");
-    SD_CHECK_ARG(kind == SD_BCSD_TAS || kind == SD_BCSD_PR, "sd_bcsd_fit_groups: unknown kind %d", kind);
-    SD_CHECK_ARG(kind == SD_BCSD_PR || X_dev, "sd_bcsd_fit_groups: BcsdTemperature needs X");
-    SD_CHECK_ARG(T > 0 && C > 0 && G > 0 && ld >= C, "sd_bcsd_fit_groups: bad sizes T=%lld C=%lld G=%d ld=%lld", (long long)T,
-                 (long long)C, G, (long long)ld);
+    SD_TRY(check_fit_args("sd_bcsd_fit_groups", ctx && y_dev && group_order && group_offsets && out, kind, X_dev, G, T, C, ld));
     *out = nullptr;
     SD_HIP(hipSetDevice(ctx->device));
     DevGroupTable gt;
@@ -1260,35 +1233,22 @@ int sd_bcsd_fit_groups_dev(sd_ctx* ctx, int kind, const double* X_dev, const dou
 
 int sd_bcsd_fit_groups(sd_ctx* ctx, int kind, const double* X, const double* y, const int32_t* group_order,
                        const int64_t* group_offsets, int G, int64_t T, int64_t C, int return_anoms, sd_bcsd_state** out) {
-    SD_CHECK_ARG(ctx && y && group_order && group_offsets && out, "sd_bcsd_fit_groups: NULL argument");
-    SD_CHECK_ARG(T > 0 && C > 0, "sd_bcsd_fit_groups: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dy;
-    const size_t bytes = sizeof(double) * (size_t)T * (size_t)C;
-    if (X) {
-        SD_HIP(dX.alloc(ctx, bytes));
-        SD_TRY(sd_copy_h2d(ctx, dX.p, X, bytes));
-    }
-    SD_HIP(dy.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dy.p, y, bytes));
-    return sd_bcsd_fit_groups_dev(ctx, kind, dX.as<double>(), dy.as<double>(), C, group_order, group_offsets, G, T, C, return_anoms, out);
+    return fit_with_device_copies(ctx, "sd_bcsd_fit_groups", ctx && y && group_order && group_offsets && out, X, y, T, C,
+                                  [&](const double* dX, const double* dy) {
+                                      return sd_bcsd_fit_groups_dev(ctx, kind, dX, dy, C, group_order, group_offsets, G, T, C, return_anoms, out);
+                                  });
 }
 
 int sd_bcsd_predict_trend(sd_ctx* ctx, const sd_bcsd_state* st, const double* Xp, const int32_t* group_id_p,
                           const int32_t* trend_group_id, int G_trend, int64_t Tp, double* out, int32_t* cell_status) {
     SD_CHECK_ARG(ctx && st && Xp && group_id_p && trend_group_id && out, "sd_bcsd_predict_trend: NULL argument");
     SD_CHECK_ARG(Tp > 0, "sd_bcsd_predict_trend: bad sizes");
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch dX, dout;
     const size_t bytes = sizeof(double) * (size_t)Tp * (size_t)st->C;
-    SD_HIP(dX.alloc(ctx, bytes));
-    SD_HIP(dout.alloc(ctx, bytes));
-    SD_TRY(sd_copy_h2d(ctx, dX.p, Xp, bytes));
-    SD_TRY(sd_bcsd_predict_trend_dev(ctx, st, dX.as<double>(), st->C, group_id_p, trend_group_id, G_trend, Tp, dout.as<double>(), st->C,
-                                     cell_status));
-    SD_TRY(sd_copy_d2h(ctx, out, dout.p, bytes));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    const sd_host_field f[] = {sd_in(Xp, bytes), sd_out(out, bytes)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_bcsd_predict_trend_dev(ctx, st, (const double*)d[0], st->C, group_id_p, trend_group_id, G_trend, Tp, (double*)d[1], st->C,
+                                         cell_status);
+    });
 }
 
 int sd_bcsd_state_set_tails(sd_bcsd_state* st, int extrapolate, int n_endpoints) {
@@ -1313,10 +1273,7 @@ int sd_bcsd_state_info(const sd_bcsd_state* st, int* kind, int* G, int64_t* T, i
 int sd_bcsd_state_status(const sd_bcsd_state* st, int32_t* cell_status) {
     SD_CHECK_ARG(st && cell_status, "sd_bcsd_state_status: NULL argument");
     SD_HIP(hipSetDevice(st->ctx->device));
-    SD_HIP(hipMemcpyAsync(cell_status, st->status, sizeof(int32_t) * st->C, hipMemcpyDeviceToHost, st->ctx->stream));
-    SD_HIP(hipStreamSynchronize(st->ctx->stream));
-    for (int64_t c = 0; c < st->C; ++c) cell_status[c] = sd_public_status(cell_status[c]);
-    return SD_OK;
+    return sd_status_fold(st->ctx, st->status, nullptr, st->C, cell_status);
 }
 
 int sd_bcsd_state_export(const sd_bcsd_state* st, double* y_sorted, double* x_climo, double* y_climo,
@@ -1324,21 +1281,16 @@ int sd_bcsd_state_export(const sd_bcsd_state* st, double* y_sorted, double* x_cl
     SD_CHECK_ARG(st, "state is NULL");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    if (y_sorted) SD_HIP(hipMemcpyAsync(y_sorted, st->ys, sizeof(double) * st->T * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (x_climo) SD_HIP(hipMemcpyAsync(x_climo, st->x_climo, sizeof(double) * st->G * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    if (y_climo) SD_HIP(hipMemcpyAsync(y_climo, st->y_climo, sizeof(double) * st->G * st->C, hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    if (cell_status) SD_TRY(sd_bcsd_state_status(st, cell_status));
-    if (group_offsets)
-        for (int g = 0; g <= st->G; ++g) group_offsets[g] = st->goff[g];
-    return SD_OK;
+    SD_TRY(sd_state_copy(ctx, bcsd_bufs(st), {y_sorted, x_climo, y_climo}, hipMemcpyDeviceToHost));
+    if (group_offsets) std::copy(st->goff.begin(), st->goff.end(), group_offsets);  // (host data)
+    return sd_status_fold(ctx, st->status, nullptr, st->C, cell_status);
 }
 
 int sd_bcsd_state_get_trend(const sd_bcsd_state* st, double* y_trend) {
     SD_CHECK_ARG(st && y_trend, "sd_bcsd_state_get_trend: NULL argument");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    SD_HIP(hipMemcpyAsync(y_trend, st->y_trend, sizeof(double) * 2 * st->G * st->C, hipMemcpyDeviceToHost, ctx->stream));
+    SD_TRY(sd_state_copy(ctx, bcsd_bufs(st), {nullptr, nullptr, nullptr, y_trend}, hipMemcpyDeviceToHost));
     SD_HIP(hipStreamSynchronize(ctx->stream));
     return SD_OK;
 }
@@ -1348,7 +1300,7 @@ int sd_bcsd_state_set_trend(sd_bcsd_state* st, const double* y_trend) {
     SD_CHECK_ARG(st->detrend, "sd_bcsd_state_set_trend: the state was not created with SD_BCSD_QM_DETREND");
     sd_ctx* ctx = st->ctx;
     SD_HIP(hipSetDevice(ctx->device));
-    SD_HIP(hipMemcpyAsync(st->y_trend, y_trend, sizeof(double) * 2 * st->G * st->C, hipMemcpyHostToDevice, ctx->stream));
+    SD_TRY(sd_state_copy(ctx, bcsd_bufs(st), {nullptr, nullptr, nullptr, y_trend}, hipMemcpyHostToDevice));
     SD_HIP(hipStreamSynchronize(ctx->stream));
     return SD_OK;
 }
@@ -1361,34 +1313,17 @@ int sd_bcsd_state_import(sd_ctx* ctx, int kind, int G, int64_t T, int64_t C, int
     SD_CHECK_ARG(T > 0 && C > 0 && G > 0 && group_offsets[0] == 0 && group_offsets[G] == T, "sd_bcsd_state_import: bad sizes");
     SD_HIP(hipSetDevice(ctx->device));
     sd_bcsd_state* st = nullptr;
-    int rc = alloc_state(ctx, kind, G, T, C, return_anoms, &st);
-    if (rc != SD_OK) {
-        sd_bcsd_state_destroy(st);
-        return rc;
-    }
+    SD_TRY(new_state(ctx, kind, G, T, C, return_anoms, &st));
     st->goff.assign(group_offsets, group_offsets + G + 1);
-    std::vector<int32_t> off32(G + 1), bits(C, 0);
+    const std::vector<int32_t> off32(group_offsets, group_offsets + G + 1), bits = sd_status_bits(cell_status, C);
     st->nmax = 0;
-    for (int g = 0; g <= G; ++g) off32[g] = (int32_t)group_offsets[g];
     for (int g = 0; g < G; ++g) st->nmax = std::max(st->nmax, off32[g + 1] - off32[g]);
-    if (cell_status)
-        for (int64_t c = 0; c < C; ++c) bits[c] = sd_internal_status(cell_status[c]);
-    auto body = [&]() -> int {
-        SD_HIP(hipMemcpyAsync(st->ys, y_sorted, sizeof(double) * T * C, hipMemcpyHostToDevice, ctx->stream));
-        if (x_climo) SD_HIP(hipMemcpyAsync(st->x_climo, x_climo, sizeof(double) * G * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->y_climo, y_climo, sizeof(double) * G * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->status, bits.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipMemcpyAsync(st->goff_dev, off32.data(), sizeof(int32_t) * (G + 1), hipMemcpyHostToDevice, ctx->stream));
-        SD_HIP(hipStreamSynchronize(ctx->stream));
+    return sd_state_build(st, sd_bcsd_state_destroy, out, [&]() -> int {
+        SD_TRY(sd_state_alloc(ctx, bcsd_bufs(st)));
+        SD_TRY(sd_state_copy(ctx, bcsd_bufs(st), {y_sorted, x_climo, y_climo, nullptr, bits.data(), off32.data()}, hipMemcpyHostToDevice));
+        SD_HIP(hipStreamSynchronize(ctx->stream));  // (bits and off32 live until here)
         return SD_OK;
-    };
-    rc = body();
-    if (rc != SD_OK) {
-        sd_bcsd_state_destroy(st);
-        return rc;
-    }
-    *out = st;
-    return SD_OK;
+    });
 }
 
 }  // extern "C"

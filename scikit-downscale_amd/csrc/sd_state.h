@@ -1,7 +1,9 @@
-// Host scaffolding shared by the fitted states of the regressor families and quantile mapping (sd_linreg.hip, sd_zscore.hip,
+// Host scaffolding shared by every family with a fitted state (sd_bcsd.hip, sd_analog.hip, sd_linreg.hip, sd_zscore.hip,
 // sd_grouped.hip, sd_arrm.hip, sd_qm.hip): the buffer list of a state and what walks it, the per-cell status in both directions,
-// small uploads, and the host-buffer form of an entry point.  Host code only; a family keeps its struct, its buffer list, its plan,
-// its kernels and the argument checks of its entry points.
+// small uploads, and the host-buffer form of an entry point (that one also in sd_regrid.hip and sd_resample.hip, which have no
+// state).  Host code only; a family keeps its struct, its buffer list, its plan, its kernels and the argument checks of its entry
+// points.  BCSD and the analogs fold the status of a predict call on the device (status_public_kernel: the fit's code before the
+// call's; analog_status_public_kernel); of the two, only BCSD's export and status query go through sd_status_fold.
 #pragma once
 #include <algorithm>
 #include <initializer_list>
