@@ -100,6 +100,11 @@ extern "C" {
 #define SD_RESAMPLE_MEAN 0  /* NaN samples skipped; NaN for a bin without a sample */
 #define SD_RESAMPLE_SUM 1   /* NaN samples skipped; 0 for a bin without a sample (pandas' min_count=0) */
 
+/* sd_disagg: how the borrowed daily pattern of a month is brought to the monthly target */
+#define SD_DISAGG_SHIFT 0      /* out = x + (target - mean of the borrowed month): temperature */
+#define SD_DISAGG_SCALE_MEAN 1 /* out = x * (target / mean); a dry borrowed month gives target on every day: precipitation rates */
+#define SD_DISAGG_SCALE_SUM 2  /* out = x * (target / sum); a dry borrowed month gives target / days on every day: precipitation totals */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -417,6 +422,27 @@ int sd_resample_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, in
 /* host buffers: src [T, C], out [M, C]; upload, run, download */
 int sd_resample(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int64_t* offsets, int64_t M,
                 double* out_host);
+
+/* ---- temporal disaggregation: GridArray.disaggregate (the last step of BCSD, Wood et al. 2004) ---------------------
+ * A monthly target [M, C] float64 (rows ld_t >= C apart) becomes a daily field out [Tout, C] float64 (rows ld_out >= C apart): output
+ * row t borrows row src_row[t] of the daily observations obs [To, C] (float64, or float32 with obs_is_f32 != 0, widened per sample;
+ * rows ld_obs >= C apart), and bin m is the output rows offsets[m] .. offsets[m + 1] - 1.  Both tables are host arrays: src_row of
+ * Tout entries in [0, To), offsets of M + 1 entries that starts at 0, never decreases and ends at Tout.  Per bin and cell, with x_t the
+ * borrowed samples in time order, acc their plain running sum without the NaN ones and cnt the number of those (the statistic of
+ * sd_resample): SD_DISAGG_SHIFT out_t = x_t + (tgt - acc / cnt); SD_DISAGG_SCALE_MEAN out_t = x_t * (tgt / (acc / cnt)), and tgt on
+ * every non-NaN day where acc / cnt == 0; SD_DISAGG_SCALE_SUM out_t = x_t * (tgt / acc), and tgt / cnt on every non-NaN day where
+ * acc == 0.  tgt is target[m], or with a climatology climo [G, C] float64 (rows ld_c >= C apart) and group [M] (host, in [0, G)):
+ * climo[group[m]] + target[m] for the shift and climo[group[m]] * target[m] for the scale ops; climo and group are both given or both
+ * NULL.  A NaN sample stays NaN, a bin without a sample and a bin with a NaN target are NaN, inf follows IEEE arithmetic.  Every
+ * operation is a single add, subtract, multiply or divide.  An unknown op, sizes <= 0, a leading dimension below C, climo without
+ * group or the reverse, a table that breaks the rules above and a call too large for the grid are SD_ERR_INVALID. */
+int sd_disagg_dev(sd_ctx* ctx, int op, const double* target_dev, int64_t ld_t, const void* obs_dev, int obs_is_f32, int64_t ld_obs, int64_t To,
+                  int64_t C, const int64_t* src_row, int64_t Tout, const int64_t* offsets, int64_t M, const double* climo_dev_or_null,
+                  int64_t ld_c, int64_t G, const int32_t* group_or_null, double* out_dev, int64_t ld_out);
+/* host buffers: target [M, C], obs [To, C], climo [G, C] or NULL, out [Tout, C]; upload, run, download */
+int sd_disagg(sd_ctx* ctx, int op, const double* target_host, const void* obs_host, int obs_is_f32, int64_t To, int64_t C,
+              const int64_t* src_row, int64_t Tout, const int64_t* offsets, int64_t M, const double* climo_host_or_null, int64_t G,
+              const int32_t* group_or_null, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

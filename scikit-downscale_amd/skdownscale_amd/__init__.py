@@ -11,6 +11,7 @@ from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
 from .grouping import GroupedGridModel, GroupedRegressor
 from .regrid import InterpolatedGridArray, Regridder
 from .resample import GridResample, ResampledGridArray, time_bins
+from .disagg import DisaggregatedGridArray, time_map
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -51,5 +52,7 @@ __all__ = [
     "ResampledGridArray",
     "GridResample",
     "time_bins",
+    "DisaggregatedGridArray",
+    "time_map",
 ]
 __version__ = "0.1.0"

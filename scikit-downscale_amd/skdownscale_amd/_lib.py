@@ -25,6 +25,7 @@ EXTRAP_CODES = {None: 0, "1to1": 0, "min": 1, "max": 2, "both": 3}  # SD_EXTRAP_
 QM_EXTRAP_CODES = {None: 0, "min": 1, "max": 2, "both": 3, "1to1": 4}  # regressors (sd_qm_predict)
 REGRID_METHODS = {"linear": 0, "nearest": 1}  # SD_REGRID_*
 RESAMPLE_OPS = {"mean": 0, "sum": 1}  # SD_RESAMPLE_*
+DISAGG_OPS = {"shift": 0, "scale_mean": 1, "scale_sum": 2}  # SD_DISAGG_*
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -131,6 +132,8 @@ SIGNATURES = {
     "sd_regrid_apply": [_p, _p, _p, _int, _i64, _p],
     "sd_resample_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64],
     "sd_resample": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p],
+    "sd_disagg_dev": [_p, _int, _p, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _i64],
+    "sd_disagg": [_p, _int, _p, _p, _int, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -127,6 +127,20 @@ class GridArray:
         (dim, rule), = named.items()
         return GridResample(self, dim, rule, kwargs, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
+        """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
+        daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and
+        shifting it (``kind='shift'``: the monthly mean equals this array) or scaling it (``kind='scale'`` with ``stat='mean'`` or
+        ``'sum'``: that statistic equals this array; a dry borrowed month spreads the value evenly).  ``years``: ``None`` draws the
+        source year of every month with ``np.random.default_rng(seed)`` among the years whose month is complete in ``daily_obs``, an
+        int array ``[M]`` names them, ``'same'`` takes each label's own year.  ``climatology``: a ``GridArray`` or ndarray
+        ``[12, *spatial]`` selected by calendar month when this array holds anomalies (``return_anoms=True`` outputs): added for the
+        shift, multiplied for the scale.  ``scratch_bytes``: device scratch of one block of whole months when the field is
+        downloaded.  -> a lazy ``DisaggregatedGridArray`` (float64) whose ``dim`` holds all days of the labelled months."""
+        from .disagg import DisaggregatedGridArray
+
+        return DisaggregatedGridArray(self, daily_obs, dim, kind, stat, years, seed, climatology, scratch_bytes=scratch_bytes)
+
     def __repr__(self):
         return f"<GridArray {self.sizes}>"
 

@@ -1,0 +1,297 @@
+"""Temporal disaggregation on the GPU: the last step of BCSD (Wood et al. 2004; the reference's driver ends with it,
+``scripts/run_bcsd.py``: ``disagg(ds_obs_daily[obs_var], anoms[obs_var], var=obs_var)``).  Every downscaled month becomes daily weather
+by borrowing the daily pattern of a historical month of the same calendar month from the observations and shifting it (temperature) or
+scaling it (precipitation) so that its monthly statistic equals the downscaled value.  Every cell borrows the same historical month, so
+the weather stays spatially coherent.
+
+``time_map`` makes the calendar -- it is the only place that touches pandas --, ``DisaggregatedGridArray`` is what
+``GridArray.disaggregate`` returns: the monthly field, the observations and the row map, computed when the field is asked for -- on the
+host through ``values`` (block by block: the device holds the observations and one block), or as a ``[Tout, C]`` ``DeviceArray``
+through ``device_field``.
+
+The rule, per output month and cell, with ``x_t`` the borrowed samples in time order, ``acc`` their plain sum without the NaN ones and
+``cnt`` the number of those: ``shift`` gives ``x_t + (tgt - acc / cnt)``; ``scale`` with ``stat='mean'`` gives ``x_t * (tgt / (acc /
+cnt))``, with ``stat='sum'`` ``x_t * (tgt / acc)``; a dry borrowed month (statistic 0) gives every non-NaN day ``tgt`` (mean) or ``tgt /
+cnt`` (sum).  A NaN sample stays NaN; a month without a sample and a month with a NaN target are NaN.  The result is float64.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pandas as pd
+
+from .core import GridArray
+from .resample import DEFAULT_SCRATCH_BYTES, ResampledGridArray, _bin_blocks
+
+KINDS = ("shift", "scale")
+
+
+def _datetime_index(time, what):
+    index = time if isinstance(time, pd.Index) else pd.Index(np.asarray(time))
+    if not isinstance(index, pd.DatetimeIndex):
+        raise ValueError(f"the {what} time coordinate must be a DatetimeIndex, got {type(index).__name__} of {index.dtype} "
+                         "(cftime calendars are not supported)")
+    return index
+
+
+def time_map(monthly_time, daily_time, years=None, seed=0):
+    """The calendar of a disaggregation: ``(out_time, src_row, offsets)``.  ``out_time`` holds all calendar days of every labelled month
+    of ``monthly_time`` (``Tout`` entries; the day within the month of a label is ignored, gaps between months are allowed), ``offsets``
+    int64 ``[M + 1]`` the rows of each month in it, and ``src_row`` int64 ``[Tout]`` the position in ``daily_time`` every output day
+    borrows.  A month (year, month) of ``daily_time`` is eligible as a source if ``daily_time`` holds every calendar day of it exactly
+    once.  ``years`` chooses the source year of every output month: ``None`` draws with ``np.random.default_rng(seed).choice`` among
+    the eligible years of that calendar month, one draw per output month, in order; an int array ``[M]`` is taken as given;
+    ``'same'`` takes the label's own year.  Output day ``d`` borrows source day ``min(d, n_src - 1)``: a 29-day month on a 28-day
+    source repeats the last day, a 28-day month on a 29-day source drops it."""
+    monthly, daily = _datetime_index(monthly_time, "monthly"), _datetime_index(daily_time, "daily")
+    M = len(monthly)
+    if M == 0 or len(daily) == 0:
+        raise ValueError(f"nothing to disaggregate: {M} months, {len(daily)} daily samples")
+    dv = daily.asi8
+    back = np.flatnonzero(dv[1:] <= dv[:-1])
+    if len(back) or daily.hasnans:
+        i = int(back[0]) + 1 if len(back) else int(np.flatnonzero(daily.isna())[0])
+        raise ValueError(f"the daily time coordinate is not strictly increasing at position {i} ({daily[i]})")
+    if monthly.hasnans:
+        raise ValueError("the monthly time coordinate holds NaT")
+    mkey = monthly.year.to_numpy().astype(np.int64) * 12 + (monthly.month.to_numpy() - 1)
+    back = np.flatnonzero(mkey[1:] <= mkey[:-1])
+    if len(back):
+        i = int(back[0]) + 1
+        raise ValueError(f"the monthly labels must have strictly increasing (year, month): position {i} ({monthly[i]}) does not lie "
+                         f"after position {i - 1} ({monthly[i - 1]})")
+    # the eligible source months: (year, month) -> first row, for the months whose days are exactly 1 .. days_in_month
+    dkey = daily.year.to_numpy().astype(np.int64) * 12 + (daily.month.to_numpy() - 1)
+    day, dim = daily.day.to_numpy(), daily.days_in_month.to_numpy()
+    starts = np.concatenate([[0], np.flatnonzero(np.diff(dkey)) + 1, [len(daily)]])
+    first_row, length = {}, {}
+    for a, b in zip(starts[:-1], starts[1:]):
+        if b - a == dim[a] and np.array_equal(day[a:b], np.arange(1, b - a + 1)):
+            first_row[int(dkey[a])], length[int(dkey[a])] = int(a), int(b - a)
+    eligible = {mo: np.array(sorted(k // 12 for k in first_row if k % 12 == mo), dtype=np.int64) for mo in range(12)}
+
+    if years is None:
+        rng = np.random.default_rng(seed)
+        chosen = []
+        for i in range(M):
+            pool = eligible[int(mkey[i] % 12)]
+            if len(pool) == 0:
+                raise ValueError(f"the observations hold no complete month to borrow for {monthly[i]:%Y-%m}")
+            chosen.append(int(rng.choice(pool)))
+        chosen = np.array(chosen, dtype=np.int64)
+    elif isinstance(years, str):
+        if years != "same":
+            raise ValueError(f"years={years!r}: expected None, 'same' or one year per month")
+        chosen = mkey // 12
+    else:
+        chosen = np.asarray(years)
+        if chosen.shape != (M,) or not np.issubdtype(chosen.dtype, np.integer):
+            raise ValueError(f"years: expected {M} integer years, one per month, got shape {chosen.shape} of {chosen.dtype}")
+        chosen = chosen.astype(np.int64)
+    n_out = monthly.days_in_month.to_numpy().astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(n_out)]).astype(np.int64)
+    src_row = np.empty(int(offsets[-1]), dtype=np.int64)
+    for i in range(M):
+        key = int(chosen[i] * 12 + mkey[i] % 12)
+        if key not in first_row:
+            raise ValueError(f"the observations do not hold every day of {int(chosen[i]):04d}-{int(mkey[i] % 12) + 1:02d} exactly once: it "
+                             f"cannot be borrowed for {monthly[i]:%Y-%m}")
+        src_row[offsets[i]:offsets[i + 1]] = first_row[key] + np.minimum(np.arange(n_out[i]), length[key] - 1)
+    wall = monthly if monthly.tz is None else monthly.tz_localize(None)  # (days are counted on the wall clock)
+    first_day = (wall.normalize() - pd.to_timedelta(wall.day.to_numpy() - 1, unit="D")).to_numpy().astype("datetime64[D]")
+    out_time = pd.DatetimeIndex(np.concatenate([first_day[i] + np.arange(n_out[i]) for i in range(M)]).astype("datetime64[ns]"))
+    return (out_time if monthly.tz is None else out_time.tz_localize(monthly.tz)), src_row, offsets
+
+
+def disagg_op(kind, stat=None):
+    """the engine's op of ``GridArray.disaggregate(kind=, stat=)``"""
+    if kind not in KINDS:
+        raise ValueError(f"kind={kind!r}: expected 'shift' or 'scale'")
+    if kind == "shift":
+        if stat not in (None, "mean"):
+            raise ValueError(f"kind='shift' matches the monthly mean; stat={stat!r} is not offered")
+        return "shift"
+    if stat not in ("mean", "sum"):
+        raise ValueError(f"kind='scale' needs stat='mean' or stat='sum' (the statistic the monthly field holds), got stat={stat!r}")
+    return "scale_" + stat
+
+
+class DisaggregatedGridArray(GridArray):
+    """A monthly ``GridArray`` turned into daily weather: same dims, ``dim`` at the number of days of the labelled months with the
+    daily coordinate, float64.  Nothing is computed until the field is asked for; ``values`` keeps what it has downloaded."""
+
+    chunksizes = None
+
+    def __init__(self, monthly, daily_obs, dim="time", kind="shift", stat=None, years=None, seed=0, climatology=None, ctx=None,
+                 scratch_bytes=DEFAULT_SCRATCH_BYTES):
+        self._op = disagg_op(kind, stat)
+        if not isinstance(daily_obs, GridArray):
+            raise ValueError(f"daily_obs: expected a GridArray, got {type(daily_obs).__name__}")
+        for name, a in (("this array", monthly), ("daily_obs", daily_obs)):
+            if dim not in a.dims:
+                raise ValueError(f"dim {dim!r} is not a dim of {name} {a.dims}")
+            if dim not in a.coords:
+                raise ValueError(f"{name} has no coordinate for dim {dim!r}")
+        rest = tuple(d for d in monthly.dims if d != dim)
+        if set(daily_obs.dims) != {dim, *rest} or any(daily_obs.sizes[d] != monthly.sizes[d] for d in rest):
+            raise ValueError(f"daily_obs has sizes {daily_obs.sizes}; expected the dims {rest} of this array at its sizes "
+                             f"{ {d: monthly.sizes[d] for d in rest} } and {dim!r}")
+        self._monthly, self._obs, self._dim, self._rest = monthly, daily_obs, dim, rest
+        self._ctx, self._scratch_bytes = ctx, int(scratch_bytes)
+        self._time, self._src_row, self._offsets = time_map(monthly.coords[dim], daily_obs.coords[dim], years, seed)
+        self._climo = self._group = None
+        if climatology is not None:
+            shape = (12,) + tuple(monthly.sizes[d] for d in rest)
+            if isinstance(climatology, GridArray):
+                lead = [d for d in climatology.dims if d not in rest]
+                if len(lead) != 1 or set(climatology.dims) != {lead[0], *rest}:
+                    raise ValueError(f"climatology has dims {climatology.dims}; expected a month dim and {rest}")
+                climatology = climatology.transpose(lead[0], *rest).values
+            c = np.asarray(climatology, dtype=np.float64)
+            if c.shape != shape:
+                raise ValueError(f"climatology has shape {c.shape}; expected {shape}: one field per calendar month")
+            self._climo = np.ascontiguousarray(c).reshape(12, -1)
+            self._group = (_datetime_index(monthly.coords[dim], "monthly").month.to_numpy() - 1).astype(np.int32)
+        self._full = None
+        self.dims = tuple(monthly.dims)
+        self.coords = dict(monthly.coords)
+        self.coords[dim] = self._time
+        self.name = monthly.name
+
+    # ---- the GridArray surface ----
+    @property
+    def sizes(self):
+        s = dict(self._monthly.sizes)
+        s[self._dim] = len(self._time)
+        return s
+
+    @property
+    def shape(self):
+        return tuple(self.sizes[d] for d in self.dims)
+
+    @property
+    def dtype(self):
+        return np.dtype(np.float64)
+
+    @property
+    def src_row(self):
+        return self._src_row
+
+    @property
+    def offsets(self):
+        return self._offsets
+
+    @property
+    def computed(self):
+        return self._full is not None
+
+    def isel(self, **indexers):
+        return self.compute().isel(**indexers)
+
+    def transpose(self, *dims):
+        return self.compute().transpose(*dims)
+
+    def compute(self):
+        return GridArray(self.values, self.dims, self.coords, self.name)
+
+    # ---- the daily field ----
+    def _context(self, ctx):
+        if ctx is None:
+            ctx = self._ctx
+        if ctx is None:
+            from .engine import default_context
+
+            ctx = default_context()
+        return ctx
+
+    def _obs_rows(self):
+        """the observations as a host [To, C] array in this array's cell order; float32 stays float32"""
+        order = (self._dim,) + self._rest
+        src = self._obs if tuple(self._obs.dims) == order else self._obs.transpose(*order)
+        v = np.asarray(src.values)
+        if v.dtype != np.float32:
+            v = np.asarray(v, dtype=np.float64)
+        return np.ascontiguousarray(v).reshape(v.shape[0], -1)
+
+    def _target(self, ctx):
+        """the monthly field as an [M, C] float64 DeviceArray: a resampled field in this order is reduced in HBM, any other goes up once"""
+        order = (self._dim,) + self._rest
+        m = self._monthly
+        if isinstance(m, ResampledGridArray) and tuple(m.dims) == order and not m.computed:
+            return m.device_field(ctx)
+        v = np.asarray((m if tuple(m.dims) == order else m.transpose(*order)).values, dtype=np.float64)
+        return ctx.to_device(np.ascontiguousarray(v).reshape(v.shape[0], -1))
+
+    def _walk(self, ctx, block_out, done):
+        """blocks of whole months of at most ``scratch_bytes`` of output: ``block_out(r0, r1)`` names the [r1 - r0, C] DeviceArray
+        that takes the rows, ``done(r0, r1, block)`` is called when they are there.  A month is always made within one block by the
+        same lane: the result does not depend on the block size."""
+        off, M = self._offsets, len(self._offsets) - 1
+        obs = self._obs_rows()
+        C = obs.shape[1]
+        if C < 1:
+            raise ValueError(f"nothing to disaggregate: the array has sizes {self._monthly.sizes}")
+        d_obs = ctx.to_device(obs, obs.dtype)
+        target = self._target(ctx)
+        assert target.shape == (M, C), (target.shape, M, C)
+        climo = None if self._climo is None else ctx.to_device(self._climo)
+        try:
+            for a, b in _bin_blocks(off, max(1, self._scratch_bytes // (C * 8))):
+                r0, r1 = int(off[a]), int(off[b])
+                block = block_out(r0, r1, C)
+                ctx.disaggregate(target.rows(a, b), d_obs, self._src_row[r0:r1], off[a:b + 1] - r0, self._op, climo,
+                                 None if climo is None else self._group[a:b], out=block)
+                done(r0, r1, block)
+        finally:
+            for d in (d_obs, target, climo):
+                if d is not None:
+                    d.free()
+
+    def _largest_block(self, C):
+        off = self._offsets
+        return max(int(off[b] - off[a]) for a, b in _bin_blocks(off, max(1, self._scratch_bytes // (C * 8))))
+
+    def device_field(self, ctx=None):
+        """the daily field as a [Tout, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest)"""
+        ctx = self._context(ctx)
+        out = []
+
+        def block_out(r0, r1, C):
+            if not out:
+                out.append(ctx.empty((len(self._time), C)))
+            return out[0].rows(r0, r1)
+
+        self._walk(ctx, block_out, lambda r0, r1, block: None)
+        return out[0]
+
+    def _compute_values(self):
+        ctx = self._context(None)
+        Tout = len(self._time)
+        state = {}
+
+        def block_out(r0, r1, C):
+            if not state:
+                state["scratch"] = ctx.empty((self._largest_block(C), C))
+                state["host"] = np.empty((Tout, C))
+            return state["scratch"].rows(0, r1 - r0)
+
+        def done(r0, r1, block):
+            state["host"][r0:r1] = block.to_host()
+
+        try:
+            self._walk(ctx, block_out, done)
+        finally:
+            if state:
+                state["scratch"].free()
+        vals = state["host"].reshape((Tout,) + tuple(self.sizes[d] for d in self._rest))
+        order = (self._dim,) + self._rest
+        return vals.transpose([order.index(d) for d in self.dims])
+
+    @property
+    def values(self):
+        if self._full is None:
+            self._full = self._compute_values()
+        return self._full
+
+    def __repr__(self):
+        return (f"<DisaggregatedGridArray {self.sizes} {self._op} of {self._monthly.sizes} on {self._obs.sizes} "
+                f"computed={self.computed}>")

@@ -998,6 +998,84 @@ class Context:
         check(self.lib.sd_resample(self.handle, code, ptr(field), f32, T, Cc, ptr(offsets), M, ptr(out)))
         return out
 
+    # ---- temporal disaggregation (GridArray.disaggregate) ----
+    @staticmethod
+    def _disagg_args(target, obs, src_row, offsets, op, climo, group):
+        if op not in _lib.DISAGG_OPS:
+            raise NotImplementedError(f"disaggregation op {op!r}: only 'shift', 'scale_mean' and 'scale_sum' are implemented")
+        if not isinstance(obs, DeviceArray):
+            obs = np.ascontiguousarray(obs, dtype=np.float32 if getattr(obs, "dtype", None) == np.float32 else np.float64)
+        if len(obs.shape) != 2 or obs.dtype not in (np.float32, np.float64):
+            raise ValueError(f"obs: expected a float32 or float64 [To, C] field, got shape {tuple(obs.shape)} of {obs.dtype}")
+        fields = {"target": target, "climo": climo}
+        for name, a in fields.items():
+            if a is None:
+                continue
+            if not isinstance(a, DeviceArray):
+                a = fields[name] = np.ascontiguousarray(a, dtype=np.float64)
+            if len(a.shape) != 2 or a.dtype != np.float64 or a.shape[1] != obs.shape[1]:
+                raise ValueError(f"{name}: expected a float64 [{'M' if name == 'target' else 'G'}, {obs.shape[1]}] field, got shape "
+                                 f"{tuple(a.shape)} of {a.dtype}")
+        src_row = np.ascontiguousarray(src_row, dtype=np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if src_row.ndim != 1:
+            raise ValueError(f"src_row: expected a table of Tout entries, got shape {src_row.shape}")
+        if offsets.ndim != 1 or len(offsets) != fields["target"].shape[0] + 1:
+            raise ValueError(f"offsets: expected a table of M + 1 = {fields['target'].shape[0] + 1} entries, got shape {offsets.shape}")
+        if (climo is None) != (group is None):
+            raise ValueError(f"sd_downscale: sd_disagg: {'group without climo' if climo is None else 'climo without group'}")
+        if group is not None:
+            group = np.ascontiguousarray(group, dtype=np.int32)
+            if group.shape != (fields["target"].shape[0],):
+                raise ValueError(f"group: expected one climatology row per bin ({fields['target'].shape[0]}), got shape {group.shape}")
+        return fields["target"], obs, src_row, offsets, _lib.DISAGG_OPS[op], int(obs.dtype == np.float32), fields["climo"], group
+
+    def disaggregate(self, target, obs, src_row, offsets, op="shift", climo=None, group=None, out=None):
+        """target [M, C] float64 and obs [To, C] float32 / float64: host arrays or DeviceArrays (rows ``ld`` apart); src_row: host int64
+        [Tout], the row of obs every output row borrows; offsets: host int64 [M + 1], bin m = output rows offsets[m] .. offsets[m + 1]
+        - 1; climo [G, C] float64 with group: host int32 [M] when the target is an anomaly -> [Tout, C] float64 DeviceArray (``out``:
+        a [Tout, C] DeviceArray, possibly a view of a wider or longer one).  op 'shift' | 'scale_mean' | 'scale_sum' (sd_disagg_dev)."""
+        target, obs, src_row, offsets, code, f32, climo, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
+        mine = []  # (what this call uploads, freed when it is over)
+
+        def resident(a, dtype):
+            if isinstance(a, DeviceArray):
+                return a
+            mine.append(self.to_device(a, dtype))
+            return mine[-1]
+
+        To, Cc = obs.shape
+        M, Tout = target.shape[0], len(src_row)
+        if min(To, Cc, Tout, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_disagg: bad sizes (To={To}, C={Cc}, Tout={Tout}, M={M})")
+        out = self._result_buffer(out, (Tout, Cc), True)
+        try:
+            target, obs = resident(target, np.float64), resident(obs, obs.dtype)
+            climo = None if climo is None else resident(climo, np.float64)
+            for name, a in (("target", target), ("obs", obs), ("climo", climo), ("out", out)):
+                if a is not None and a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_disagg: `{name}` belongs to another context")
+            check(self.lib.sd_disagg_dev(self.handle, code, target.vptr, target.ld, obs.vptr, f32, obs.ld, To, Cc, ptr(src_row), Tout, ptr(offsets),
+                                         M, None if climo is None else climo.vptr, 0 if climo is None else climo.ld,
+                                         0 if climo is None else climo.shape[0], None if group is None else ptr(group), out.vptr, out.ld))
+        finally:
+            for a in mine:
+                a.free()
+        return out
+
+    def disaggregate_host(self, target, obs, src_row, offsets, op="shift", climo=None, group=None):
+        """host target [M, C], obs [To, C] -> host [Tout, C] through sd_disagg (upload, run, download in one call)"""
+        target, obs, src_row, offsets, code, f32, climo, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
+        if any(isinstance(a, DeviceArray) for a in (target, obs, climo)):
+            raise ValueError("disaggregate_host: expected host arrays")
+        To, Cc = obs.shape
+        M, Tout = target.shape[0], len(src_row)
+        out = np.empty((Tout, Cc))
+        check(self.lib.sd_disagg(self.handle, code, ptr(target), ptr(obs), f32, To, Cc, ptr(src_row), Tout, ptr(offsets), M,
+                                 None if climo is None else ptr(climo), 0 if climo is None else climo.shape[0],
+                                 None if group is None else ptr(group), ptr(out)))
+        return out
+
 
 _default_ctx = None
 

@@ -194,9 +194,66 @@ def bench_resample(ctx, args):
     return res
 
 
+def bench_disagg(ctx, args):
+    """disagg_kernel: the monthly means of a 40-year daily record (480 months) back to daily rows on 100 000 cells, every month borrowing
+    a seeded year of the record, shift, float64 and float32 observations; GB/s by algorithmic bytes (the borrowed rows read once + 8 * M
+    * C read + 8 * Tout * C written), beside sd_memcpy_d2d of the same source bytes in the same run, the first 256 cells compared bit
+    for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _disagg_oracle as do
+    import pandas as pd
+    from skdownscale_amd.disagg import time_map
+    from skdownscale_amd.resample import time_bins
+
+    years, C = max(1, round(args.times / 365)), 100_000
+    index = pd.date_range("1980-01-01", f"{1980 + years - 1}-12-31", freq="D")
+    To = len(index)
+    months = pd.date_range("2020-01-01", periods=12 * years, freq="MS")
+    _, src_row, offsets = time_map(months, index, None, 0)
+    Tout, M = len(src_row), len(months)
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((To, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    d64, first = fill(C), fill(256).to_host()
+    target = ctx.resample(d64, time_bins(index, "MS")[1], "mean")  # month k of the output is brought to the mean of month k of the record
+    t_first = target.cells(0, 256).to_host()
+    out, spare = ctx.empty((Tout, C)), ctx.empty((Tout, C))
+    repeats = max(args.steps, 7)
+    res = {"workload": f"disagg {M} months -> {Tout} daily rows x {C} cells on a {To}-day record, shift, seeded years", "repeats": repeats}
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        if dtype == np.float32:
+            d = ctx.empty((To, C), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, d64.vptr, To * C, d.vptr))
+            ctx.synchronize()
+        else:
+            d = d64
+        ctx.disaggregate(target, d, src_row, offsets, "shift", out=out)
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            ctx.disaggregate(target, d, src_row, offsets, "shift", out=out)
+            times.append(ctx.prof()["disagg_kernel"]["ms"])
+        ctx.prof_enable(False)
+        ms = float(np.median(times))
+        src_bytes = Tout * C * np.dtype(dtype).itemsize
+        nbytes = src_bytes + 8 * Tout * C + 8 * M * C
+        got, want = out.cells(0, 256).to_host(), do.disaggregate(t_first, first.astype(dtype), src_row, offsets, "shift")
+        copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+        res[name] = {"kernel_ms": ms, "kernel_ms_min_max": [min(times), max(times)], "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                     "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": bool(np.array_equal(got, want, equal_nan=True)),
+                     "device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6},
+                     "kernel_over_copy_ms": ms / copy_ms, "GBps_over_copy_GBps": (nbytes / ms) / (src_bytes / copy_ms)}
+        if d is not d64:
+            d.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -207,8 +264,8 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload in ("regrid", "regrid_e2e", "resample"):
-        line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample}[args.workload](ctx, args))
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg"):
+        line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
