@@ -16,6 +16,7 @@
 // 8-byte store).  A NaN node gives a NaN slope and a target outside the source range a NaN distance: no branch.
 #include <vector>
 
+#include "sd_bins.h"
 #include "sd_internal.h"
 #include "sd_regrid_plan.h"
 #include "sd_state.h"
@@ -96,13 +97,7 @@ __global__ void __launch_bounds__(kLanes* kWaves) regrid_kernel(const S* __restr
         }
 #pragma unroll
         for (int u = 0; u < kBatch; ++u)
-            if (tb + u < t1) {
-                double* o = orow + (tb + u) * ld_out;
-                if constexpr (V == 2)
-                    *reinterpret_cast<double2*>(o) = make_double2(res[u][0], res[u][1]);
-                else
-                    *o = res[u][0];
-            }
+            if (tb + u < t1) sdbn::store_doubles<V>(orow + (tb + u) * ld_out, res[u]);
     }
 }
 

@@ -16,11 +16,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 #include <limits>
 #include <vector>
 
-#include "../../include/sd_downscale.h"
+#include "sd_bins_plan.h"
 
 namespace sdrg {
 constexpr int kLanes = 64;
@@ -49,18 +48,9 @@ struct RegridPlan {
     int64_t blocks = 0;   // xtiles * Ny * nchunks, column tile fastest, then the target row, then the time chunk
 };
 
-namespace regrid_plan_detail {
-template <class... A>
-RegridPlan fail(RegridPlan pl, int code, const char* fmt, A... a) {
-    snprintf(pl.message, sizeof pl.message, fmt, a...);
-    pl.error = code;
-    return pl;
-}
-}  // namespace regrid_plan_detail
-
 inline RegridPlan regrid_plan(const RegridCall& c) {
     using namespace sdrg;
-    using regrid_plan_detail::fail;
+    using sdbn::fail;
     RegridPlan pl;
     if (!(c.method == SD_REGRID_LINEAR || c.method == SD_REGRID_NEAREST))
         return fail(pl, SD_ERR_INVALID, "sd_regrid: unknown method code %d", c.method);

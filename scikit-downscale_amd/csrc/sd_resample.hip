@@ -2,14 +2,10 @@
 // .mean() / .sum() per cell): bin m is the run of rows offsets[m] .. offsets[m + 1] - 1, made by pandas on the host.  The launch plan
 // and the refusals are in sd_resample_plan.h.
 //
-// resample_kernel<S, V, OP>: a workgroup of four waves owns one tile of 64 * V adjacent cells and a run of kBinsPerGroup consecutive
-// bins; each wave takes kBinsPerWave whole bins, one after the other.  A lane owns its V cells for the whole bin and adds their
-// samples in time order, so a result depends neither on the launch geometry nor on how a caller cuts the time axis into blocks of
-// whole bins.  One row of the tile is one coalesced load per wave (V * sizeof(S) bytes per lane, 16 where the plan allows); the loads
-// of a batch of kBatch rows are issued before any of their arithmetic.  A row past the end of the bin reads the bin's last row again
-// and is not counted, so a bin of any length -- 1 and a partial batch included -- runs the same code; an empty bin runs no batch at
-// all.  NaN samples are skipped by a select, the count is an int per cell.  One store of V doubles per lane and bin; no LDS, no
-// atomics.  Algorithmic bytes: sizeof(S) * T * C read + 8 * M * C written.
+// resample_kernel<S, V, OP>: the geometry, the batched loads and the statistic of a bin are those of sd_bins.h.  A lane adds the
+// samples of its V cells in time order, so a result depends neither on the launch geometry nor on how a caller cuts the time axis
+// into blocks of whole bins.  One store of V doubles per lane and bin; no LDS, no atomics.  Algorithmic bytes: sizeof(S) * T * C read
+// + 8 * M * C written.
 //
 // mean: sum / count, NaN without a sample (an empty bin and an all-NaN bin alike).  sum: 0 without a sample (pandas' min_count=0).
 // inf follows IEEE arithmetic.  Plain summation (pandas compensates; both stay within n * 2^-53 * sum|x| of the exact sum).
@@ -17,54 +13,27 @@
 // A bin is never split across lanes: one very long bin over few cells has little parallelism.  That is the price of the fixed order.
 #include <vector>
 
+#include "sd_bins.h"
 #include "sd_internal.h"
 #include "sd_resample_plan.h"
 #include "sd_state.h"
 
 namespace {
-using namespace sdrs;
-
-template <typename S, int V>
-struct alignas(sizeof(S) * V) Cells {
-    S v[V];
-};
+using namespace sdbn;
 
 template <typename S, int V, int OP>
 __global__ void __launch_bounds__(kLanes* kWaves) resample_kernel(const S* __restrict__ src, int64_t ld, int64_t C,
                                                                  const int64_t* __restrict__ offsets, int64_t M, int64_t ctiles,
                                                                  double* __restrict__ out, int64_t ld_out) {
-    const int lane = threadIdx.x % kLanes, wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kLanes);
-    const int64_t ctile = blockIdx.x % ctiles, group = blockIdx.x / ctiles;
-    const int64_t c0 = (ctile * kLanes + lane) * V;  // (V divides C: the V cells are inside or outside together)
-    if (c0 >= C) return;
-    const int64_t m0 = group * kBinsPerGroup + (int64_t)wave * kBinsPerWave;
-    const S* const col = src + c0;
+    int64_t c0, m0;
+    if (!lane_place<V>(ctiles, C, c0, m0)) return;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     for (int b = 0; b < kBinsPerWave; ++b) {
         const int64_t m = m0 + b;
         if (m >= M) break;  // wave-uniform
-        const int64_t r0 = offsets[m], r1 = offsets[m + 1];
-        double acc[V];
+        double acc[V], res[V];
         int cnt[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = 0.0, cnt[v] = 0;
-        for (int64_t r = r0; r < r1; r += kBatch) {
-            Cells<S, V> q[kBatch];
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) q[u] = *reinterpret_cast<const Cells<S, V>*>(col + min(r + u, r1 - 1) * ld);
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                const bool inside = r + u < r1;
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const double x = (double)q[u].v[v];
-                    const bool take = inside && x == x;
-                    acc[v] += take ? x : 0.0;
-                    cnt[v] += take ? 1 : 0;
-                }
-            }
-        }
-        double res[V];
+        bin_statistic<S, V>(src + c0, ld, offsets[m], offsets[m + 1], [](int64_t r) { return r; }, acc, cnt);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             if constexpr (OP == SD_RESAMPLE_MEAN)
@@ -72,37 +41,23 @@ __global__ void __launch_bounds__(kLanes* kWaves) resample_kernel(const S* __res
             else
                 res[v] = acc[v];
         }
-        double* const o = out + m * ld_out + c0;
-        if constexpr (V == 1) {
-            *o = res[0];
-        } else {
-#pragma unroll
-            for (int v = 0; v < V; v += 2) *reinterpret_cast<double2*>(o + v) = make_double2(res[v], res[v + 1]);
-        }
+        store_doubles<V>(out + m * ld_out + c0, res);
     }
-}
-
-template <typename S, int V>
-int launch_op(sd_ctx* ctx, const ResampleCall& c, const ResamplePlan& pl, const S* src, const int64_t* offsets, double* out) {
-    const dim3 grid((unsigned)pl.blocks), block((unsigned)pl.block);
-    if (c.op == SD_RESAMPLE_MEAN)
-        SD_LAUNCH(ctx, "resample_kernel", (resample_kernel<S, V, SD_RESAMPLE_MEAN>), grid, block, 0, src, c.ld, c.C, offsets, c.M, pl.ctiles, out,
-                  c.ld_out);
-    else
-        SD_LAUNCH(ctx, "resample_kernel", (resample_kernel<S, V, SD_RESAMPLE_SUM>), grid, block, 0, src, c.ld, c.C, offsets, c.M, pl.ctiles, out,
-                  c.ld_out);
-    return SD_OK;
 }
 
 int launch(sd_ctx* ctx, const ResampleCall& c, const ResamplePlan& pl, const void* src, const int64_t* offsets, double* out) {
-    if (c.src_is_f32) {
-        const float* s = (const float*)src;
-        return pl.cols == 4 ? launch_op<float, 4>(ctx, c, pl, s, offsets, out)
-               : pl.cols == 2 ? launch_op<float, 2>(ctx, c, pl, s, offsets, out)
-                              : launch_op<float, 1>(ctx, c, pl, s, offsets, out);
-    }
-    const double* s = (const double*)src;
-    return pl.cols == 2 ? launch_op<double, 2>(ctx, c, pl, s, offsets, out) : launch_op<double, 1>(ctx, c, pl, s, offsets, out);
+    const dim3 grid((unsigned)pl.blocks), block((unsigned)pl.block);
+    return with_cells(c.src_is_f32, pl.cols, src, [&](auto* s, auto cols) {
+        using S = std::remove_const_t<std::remove_pointer_t<decltype(s)>>;
+        constexpr int V = decltype(cols)::value;
+        if (c.op == SD_RESAMPLE_MEAN)
+            SD_LAUNCH(ctx, "resample_kernel", (resample_kernel<S, V, SD_RESAMPLE_MEAN>), grid, block, 0, s, c.ld, c.C, offsets, c.M, pl.ctiles, out,
+                      c.ld_out);
+        else
+            SD_LAUNCH(ctx, "resample_kernel", (resample_kernel<S, V, SD_RESAMPLE_SUM>), grid, block, 0, s, c.ld, c.C, offsets, c.M, pl.ctiles, out,
+                      c.ld_out);
+        return (int)SD_OK;
+    });
 }
 
 ResampleCall call_of(int op, int src_is_f32, int64_t ld, int64_t T, int64_t C, int64_t M, int64_t ld_out, const void* src, const void* out) {

@@ -205,5 +205,10 @@ def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def as_field(a):
+    """a host field as the engine takes it: contiguous, float32 stays float32 (it is widened on the device), anything else is float64"""
+    return np.ascontiguousarray(a, dtype=np.float32 if getattr(a, "dtype", None) == np.float32 else np.float64)
+
+
 def as_i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)

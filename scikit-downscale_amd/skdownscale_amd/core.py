@@ -19,6 +19,7 @@ import pandas as pd
 from . import _lib
 from .arrm import ArrmGridModel, PiecewiseLinearRegression
 from .bcsd import BcsdBase, check_supported
+from .engine import default_context
 from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression, RegressionGridModel
 from .quantile import (CunnaneGridModel, CunnaneTransformer, QmGridModel, QuantileMapper, QuantileMapperGridModel,
                        QuantileMappingReressor, check_extrapolate)
@@ -26,6 +27,17 @@ from .grouping import GroupedGridModel, GroupedRegressor
 from .zscore import ZScoreGridModel, ZScoreRegressor
 
 DEFAULT_FEATURE_DIM = "variable"
+
+
+def chunk_lengths(sizes, chunks):
+    """dim -> block lengths of an array of these ``sizes`` under ``chunks``: dim -> block length (-1, None or a length past the end:
+    one block), like ``xarray.DataArray.chunk``"""
+    cs = {}
+    for d, n in sizes.items():
+        b = chunks.get(d, -1) if chunks else -1
+        b = n if b in (-1, None) or b >= n else int(b)
+        cs[d] = tuple([b] * (n // b) + ([n % b] if n % b else [])) if n else (0,)
+    return cs
 
 
 class GridArray:
@@ -62,12 +74,7 @@ class GridArray:
     def chunk(self, chunks):
         """``chunks``: dim -> block length (or -1 for one block), like ``xarray.DataArray.chunk``"""
         g = GridArray(self.values, self.dims, self.coords, self.name)
-        cs = {}
-        for d, n in self.sizes.items():
-            b = chunks.get(d, -1) if chunks else -1
-            b = n if b in (-1, None) or b >= n else int(b)
-            cs[d] = tuple([b] * (n // b) + ([n % b] if n % b else [])) if n else (0,)
-        g.chunksizes = cs
+        g.chunksizes = chunk_lengths(self.sizes, chunks)
         return g
 
     def isel(self, **indexers):
@@ -218,6 +225,50 @@ class LazyGridArray(GridArray):
 
     def __repr__(self):
         return f"<LazyGridArray {self.sizes} blocks={len(self._thunks)} computed={self.computed}>"
+
+
+class DeferredGridArray(GridArray):
+    """A float64 field that is computed when it is asked for, the base of what ``interp_like``, ``resample`` and ``disaggregate``
+    return.  A subclass sets ``dims``, ``coords`` and ``name`` and gives ``sizes`` and ``_compute_values()``; ``values`` keeps what that
+    returned.  ``isel`` and ``transpose`` work on the computed field unless the subclass can stay lazy."""
+
+    _full = None
+    _ctx = None
+
+    @property
+    def shape(self):
+        return tuple(self.sizes[d] for d in self.dims)
+
+    @property
+    def dtype(self):
+        return np.dtype(np.float64)  # float32 sources are widened on the device
+
+    @property
+    def computed(self):
+        return self._full is not None
+
+    @property
+    def values(self):
+        if self._full is None:
+            self._full = self._compute_values()
+        return self._full
+
+    def compute(self):
+        return GridArray(self.values, self.dims, self.coords, self.name)
+
+    def isel(self, **indexers):
+        return self.compute().isel(**indexers)
+
+    def transpose(self, *dims):
+        return self.compute().transpose(*dims)
+
+    def _context(self, ctx=None):
+        """``ctx``, else the context the array was made with, else the process-wide one"""
+        return ctx or self._ctx or default_context()
+
+    def _in_dims(self, field, order):
+        """a host field whose axes are the dims ``order`` (the trailing ones possibly flattened) as an array of ``self.dims``"""
+        return field.reshape(tuple(self.sizes[d] for d in order)).transpose([order.index(d) for d in self.dims])
 
 
 class GridDataset(dict):

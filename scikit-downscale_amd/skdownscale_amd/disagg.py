@@ -19,7 +19,8 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
-from .core import GridArray
+from . import _lib
+from .core import DeferredGridArray, GridArray
 from .resample import DEFAULT_SCRATCH_BYTES, ResampledGridArray, _bin_blocks
 
 KINDS = ("shift", "scale")
@@ -115,11 +116,9 @@ def disagg_op(kind, stat=None):
     return "scale_" + stat
 
 
-class DisaggregatedGridArray(GridArray):
+class DisaggregatedGridArray(DeferredGridArray):
     """A monthly ``GridArray`` turned into daily weather: same dims, ``dim`` at the number of days of the labelled months with the
-    daily coordinate, float64.  Nothing is computed until the field is asked for; ``values`` keeps what it has downloaded."""
-
-    chunksizes = None
+    daily coordinate."""
 
     def __init__(self, monthly, daily_obs, dim="time", kind="shift", stat=None, years=None, seed=0, climatology=None, ctx=None,
                  scratch_bytes=DEFAULT_SCRATCH_BYTES):
@@ -151,7 +150,6 @@ class DisaggregatedGridArray(GridArray):
                 raise ValueError(f"climatology has shape {c.shape}; expected {shape}: one field per calendar month")
             self._climo = np.ascontiguousarray(c).reshape(12, -1)
             self._group = (_datetime_index(monthly.coords[dim], "monthly").month.to_numpy() - 1).astype(np.int32)
-        self._full = None
         self.dims = tuple(monthly.dims)
         self.coords = dict(monthly.coords)
         self.coords[dim] = self._time
@@ -165,14 +163,6 @@ class DisaggregatedGridArray(GridArray):
         return s
 
     @property
-    def shape(self):
-        return tuple(self.sizes[d] for d in self.dims)
-
-    @property
-    def dtype(self):
-        return np.dtype(np.float64)
-
-    @property
     def src_row(self):
         return self._src_row
 
@@ -180,37 +170,13 @@ class DisaggregatedGridArray(GridArray):
     def offsets(self):
         return self._offsets
 
-    @property
-    def computed(self):
-        return self._full is not None
-
-    def isel(self, **indexers):
-        return self.compute().isel(**indexers)
-
-    def transpose(self, *dims):
-        return self.compute().transpose(*dims)
-
-    def compute(self):
-        return GridArray(self.values, self.dims, self.coords, self.name)
-
     # ---- the daily field ----
-    def _context(self, ctx):
-        if ctx is None:
-            ctx = self._ctx
-        if ctx is None:
-            from .engine import default_context
-
-            ctx = default_context()
-        return ctx
-
     def _obs_rows(self):
         """the observations as a host [To, C] array in this array's cell order; float32 stays float32"""
         order = (self._dim,) + self._rest
         src = self._obs if tuple(self._obs.dims) == order else self._obs.transpose(*order)
-        v = np.asarray(src.values)
-        if v.dtype != np.float32:
-            v = np.asarray(v, dtype=np.float64)
-        return np.ascontiguousarray(v).reshape(v.shape[0], -1)
+        v = _lib.as_field(src.values)
+        return v.reshape(v.shape[0], -1)
 
     def _target(self, ctx):
         """the monthly field as an [M, C] float64 DeviceArray: a resampled field in this order is reduced in HBM, any other goes up once"""
@@ -218,8 +184,8 @@ class DisaggregatedGridArray(GridArray):
         m = self._monthly
         if isinstance(m, ResampledGridArray) and tuple(m.dims) == order and not m.computed:
             return m.device_field(ctx)
-        v = np.asarray((m if tuple(m.dims) == order else m.transpose(*order)).values, dtype=np.float64)
-        return ctx.to_device(np.ascontiguousarray(v).reshape(v.shape[0], -1))
+        v = _lib.as_f64((m if tuple(m.dims) == order else m.transpose(*order)).values)
+        return ctx.to_device(v.reshape(v.shape[0], -1))
 
     def _walk(self, ctx, block_out, done):
         """blocks of whole months of at most ``scratch_bytes`` of output: ``block_out(r0, r1)`` names the [r1 - r0, C] DeviceArray
@@ -264,7 +230,7 @@ class DisaggregatedGridArray(GridArray):
         return out[0]
 
     def _compute_values(self):
-        ctx = self._context(None)
+        ctx = self._context()
         Tout = len(self._time)
         state = {}
 
@@ -282,15 +248,7 @@ class DisaggregatedGridArray(GridArray):
         finally:
             if state:
                 state["scratch"].free()
-        vals = state["host"].reshape((Tout,) + tuple(self.sizes[d] for d in self._rest))
-        order = (self._dim,) + self._rest
-        return vals.transpose([order.index(d) for d in self.dims])
-
-    @property
-    def values(self):
-        if self._full is None:
-            self._full = self._compute_values()
-        return self._full
+        return self._in_dims(state["host"], (self._dim,) + self._rest)
 
     def __repr__(self):
         return (f"<DisaggregatedGridArray {self.sizes} {self._op} of {self._monthly.sizes} on {self._obs.sizes} "

@@ -285,7 +285,7 @@ class RegridState(_State):
     @staticmethod
     def _source(src, i):
         if not isinstance(src, DeviceArray):
-            src = np.ascontiguousarray(src, dtype=np.float32 if getattr(src, "dtype", None) == np.float32 else np.float64)
+            src = _lib.as_field(src)
         if len(src.shape) != 3 or tuple(src.shape[1:]) != (i["ny"], i["nx"]) or src.shape[0] < 1:
             raise ValueError(f"src: expected a [T, {i['ny']}, {i['nx']}] field, got shape {tuple(src.shape)}")
         if isinstance(src, DeviceArray) and (src.dtype not in (np.float32, np.float64) or src.ld != src.shape[-1]):
@@ -961,7 +961,7 @@ class Context:
         if op not in _lib.RESAMPLE_OPS:
             raise NotImplementedError(f"resample reduction {op!r}: only 'mean' and 'sum' are implemented")
         if not isinstance(field, DeviceArray):
-            field = np.ascontiguousarray(field, dtype=np.float32 if getattr(field, "dtype", None) == np.float32 else np.float64)
+            field = _lib.as_field(field)
         if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
             raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -1004,7 +1004,7 @@ class Context:
         if op not in _lib.DISAGG_OPS:
             raise NotImplementedError(f"disaggregation op {op!r}: only 'shift', 'scale_mean' and 'scale_sum' are implemented")
         if not isinstance(obs, DeviceArray):
-            obs = np.ascontiguousarray(obs, dtype=np.float32 if getattr(obs, "dtype", None) == np.float32 else np.float64)
+            obs = _lib.as_field(obs)
         if len(obs.shape) != 2 or obs.dtype not in (np.float32, np.float64):
             raise ValueError(f"obs: expected a float32 or float64 [To, C] field, got shape {tuple(obs.shape)} of {obs.dtype}")
         fields = {"target": target, "climo": climo}

@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .core import DEFAULT_FEATURE_DIM, GridArray, _block_slices
+from . import _lib
+from .core import DEFAULT_FEATURE_DIM, DeferredGridArray, _block_slices, chunk_lengths
 
 METHODS = ("linear", "nearest")
 PASS_THROUGH_DIMS = ("time", DEFAULT_FEATURE_DIM)  # never interpolated over
@@ -102,9 +103,8 @@ def interp_dims(array, target_names):
     return dims
 
 
-class InterpolatedGridArray(GridArray):
-    """A coarse ``GridArray`` seen on a finer grid: same dims, the two interpolated dims at the target's sizes and coordinates.
-    Nothing is computed until the field is asked for; ``values`` keeps what it has downloaded."""
+class InterpolatedGridArray(DeferredGridArray):
+    """A coarse ``GridArray`` seen on a finer grid: same dims, the two interpolated dims at the target's sizes and coordinates."""
 
     def __init__(self, source, target_coords, method="linear", ctx=None, chunksizes=None):
         self._source = source
@@ -113,7 +113,6 @@ class InterpolatedGridArray(GridArray):
         self._ctx = ctx
         # validates the coordinates now; one plan for the whole grid (a chunked array builds one per block instead)
         self._regridder = Regridder({d: source.coords[d] for d in self._spatial}, {d: target_coords[d] for d in self._spatial}, method, ctx)
-        self._full = None
         self.dims = tuple(source.dims)
         self.coords = dict(source.coords)
         self.coords.update({d: np.asarray(target_coords[d]) for d in self._spatial})
@@ -128,31 +127,14 @@ class InterpolatedGridArray(GridArray):
         return s
 
     @property
-    def shape(self):
-        return tuple(self.sizes[d] for d in self.dims)
-
-    @property
-    def dtype(self):
-        return np.dtype(np.float64)  # float32 sources are widened on the device
-
-    @property
     def source(self):
         return self._source
-
-    @property
-    def computed(self):
-        return self._full is not None
 
     def _target(self):
         return {d: self.coords[d] for d in self._spatial}
 
     def chunk(self, chunks):
-        cs = {}  # dim -> block lengths, as GridArray.chunk
-        for d, n in self.sizes.items():
-            b = chunks.get(d, -1) if chunks else -1
-            b = n if b in (-1, None) or b >= n else int(b)
-            cs[d] = tuple([b] * (n // b) + ([n % b] if n % b else [])) if n else (0,)
-        return InterpolatedGridArray(self._source, self._target(), self._method, self._ctx, cs)
+        return InterpolatedGridArray(self._source, self._target(), self._method, self._ctx, chunk_lengths(self.sizes, chunks))
 
     def unchunked(self):
         return self if self.chunksizes is None else InterpolatedGridArray(self._source, self._target(), self._method, self._ctx)
@@ -163,23 +145,14 @@ class InterpolatedGridArray(GridArray):
         source = self._source.isel(**{d: s for d, s in indexers.items() if d not in self._spatial})
         return InterpolatedGridArray(source, target, self._method, self._ctx)
 
-    def transpose(self, *dims):
-        return self.compute().transpose(*dims)
-
-    def compute(self):
-        return GridArray(self.values, self.dims, self.coords, self.name)
-
     # ---- the fine field ----
     def _lead_dims(self):
         return tuple(d for d in self.dims if d not in self._spatial)
 
     def _coarse_stack(self):
         """the coarse data as [T', ny, nx]: the other dims flattened in front, the interpolated ones in the order of the field"""
-        src = self._source.transpose(*self._lead_dims(), *self._spatial)
-        v = src.values
-        if v.dtype != np.float32:
-            v = np.asarray(v, dtype=np.float64)
-        return np.ascontiguousarray(v).reshape((-1,) + v.shape[-2:])
+        v = _lib.as_field(self._source.transpose(*self._lead_dims(), *self._spatial).values)
+        return v.reshape((-1,) + v.shape[-2:])
 
     def _blocks(self):
         """(selection, unchunked block) of a chunked array, each with a plan of its own from the block's target coordinates"""
@@ -192,31 +165,26 @@ class InterpolatedGridArray(GridArray):
             raise ValueError(f"device_field needs dims (time, y, x); this array has {self.dims}")
         if self.chunksizes is not None and any(len(self.chunksizes[d]) > 1 for d in self._spatial):
             raise ValueError("device_field of a chunked array: take it per block (isel)")
+        return self._regridder_on(ctx).regrid(self._coarse_stack())
+
+    def _regridder_on(self, ctx):
+        """the regridder, with its tables on ``ctx`` if one is named (they live on the context that runs the model)"""
         rg = self._regridder
-        if ctx is not None and rg._ctx is not ctx:  # (the tables live on the context that runs the model)
+        if ctx is not None and rg._ctx is not ctx:
             rg = self._regridder = Regridder(rg.src_coords, rg.dst_coords, self._method, ctx)
-        return rg.regrid(self._coarse_stack())
+        return rg
 
     def _compute_values(self):
-        lead = self._lead_dims()
-        lead_shape = tuple(self.sizes[d] for d in lead)
+        order = self._lead_dims() + self._spatial
         stack = self._coarse_stack()
         if self.chunksizes is None:
-            fine = self._regridder.regrid(stack).to_host().reshape(lead_shape + self._regridder.shape_out)
-        else:
-            fine = np.empty(lead_shape + tuple(self.sizes[d] for d in self._spatial))
-            for sel, block in self._blocks():
-                rg = block._regridder
-                fine[(Ellipsis,) + tuple(sel[d] for d in self._spatial)] = rg.regrid(stack).to_host().reshape(lead_shape + rg.shape_out)
-                rg.close()
-        order = lead + self._spatial
-        return fine.transpose([order.index(d) for d in self.dims])
-
-    @property
-    def values(self):
-        if self._full is None:
-            self._full = self._compute_values()
-        return self._full
+            return self._in_dims(self._regridder.regrid(stack).to_host(), order)
+        fine = np.empty(tuple(self.sizes[d] for d in order))
+        for sel, block in self._blocks():
+            rg = block._regridder
+            fine[(Ellipsis,) + tuple(sel[d] for d in self._spatial)] = rg.regrid(stack).to_host().reshape(fine.shape[:-2] + rg.shape_out)
+            rg.close()
+        return self._in_dims(fine, order)
 
     def __repr__(self):
         return f"<InterpolatedGridArray {self.sizes} from {self._source.sizes} method={self._method!r} computed={self.computed}>"

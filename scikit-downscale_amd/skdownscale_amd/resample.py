@@ -17,7 +17,8 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
-from .core import GridArray
+from . import _lib
+from .core import DeferredGridArray, chunk_lengths
 
 OPS = ("mean", "sum")
 DEFAULT_SCRATCH_BYTES = 1 << 30
@@ -99,9 +100,9 @@ class GridResample:
         return f"<GridResample {self._dim}={self._rule!r}: {len(self.labels)} bins of {self._source.sizes[self._dim]} samples>"
 
 
-class ResampledGridArray(GridArray):
+class ResampledGridArray(DeferredGridArray):
     """A ``GridArray`` whose ``dim`` is reduced over pandas' bins of ``rule``: same dims, ``dim`` at the number of bins with the bin
-    labels as its coordinate, float64.  Nothing is computed until the field is asked for; ``values`` keeps what it has downloaded."""
+    labels as its coordinate."""
 
     def __init__(self, source, dim, rule, op="mean", kw=None, ctx=None, scratch_bytes=DEFAULT_SCRATCH_BYTES, chunksizes=None, bins=None):
         if op not in OPS:
@@ -110,7 +111,6 @@ class ResampledGridArray(GridArray):
         self._ctx = ctx
         self._scratch_bytes = int(scratch_bytes)
         self._labels, self._offsets = bins if bins is not None else time_bins(source.coords[dim], rule, **self._kw)
-        self._full = None
         self.dims = tuple(source.dims)
         self.coords = dict(source.coords)
         self.coords[dim] = self._labels
@@ -130,14 +130,6 @@ class ResampledGridArray(GridArray):
         return s
 
     @property
-    def shape(self):
-        return tuple(self.sizes[d] for d in self.dims)
-
-    @property
-    def dtype(self):
-        return np.dtype(np.float64)  # float32 sources are widened on the device
-
-    @property
     def source(self):
         return self._source
 
@@ -145,17 +137,8 @@ class ResampledGridArray(GridArray):
     def offsets(self):
         return self._offsets
 
-    @property
-    def computed(self):
-        return self._full is not None
-
     def chunk(self, chunks):
-        cs = {}  # dim -> block lengths, as GridArray.chunk
-        for d, n in self.sizes.items():
-            b = chunks.get(d, -1) if chunks else -1
-            b = n if b in (-1, None) or b >= n else int(b)
-            cs[d] = tuple([b] * (n // b) + ([n % b] if n % b else [])) if n else (0,)
-        return self._like(chunksizes=cs)
+        return self._like(chunksizes=chunk_lengths(self.sizes, chunks))
 
     def unchunked(self):
         return self if self.chunksizes is None else self._like()
@@ -167,24 +150,9 @@ class ResampledGridArray(GridArray):
             return self.compute().isel(**indexers)
         return self._like(source=self._source.isel(**indexers))
 
-    def transpose(self, *dims):
-        return self.compute().transpose(*dims)
-
-    def compute(self):
-        return GridArray(self.values, self.dims, self.coords, self.name)
-
     # ---- the reduced field ----
     def _rest_dims(self):
         return tuple(d for d in self.dims if d != self._dim)
-
-    def _context(self, ctx):
-        if ctx is None:
-            ctx = self._ctx
-        if ctx is None:
-            from .engine import default_context
-
-            ctx = default_context()
-        return ctx
 
     def _resident_source(self):
         """(regridder of the source, its coarse [T, ny, nx] stack) when the source is an unchunked ``coarse.interp_like(obs)`` with
@@ -201,10 +169,8 @@ class ResampledGridArray(GridArray):
     def _host_rows(self):
         """the source as a host [T, C] array, the other dims flattened in their order; float32 stays float32"""
         src = self._source.transpose(self._dim, *self._rest_dims()) if self.dims[0] != self._dim else self._source
-        v = np.asarray(src.values)
-        if v.dtype != np.float32:
-            v = np.asarray(v, dtype=np.float64)
-        return np.ascontiguousarray(v).reshape(v.shape[0], -1)
+        v = _lib.as_field(src.values)
+        return v.reshape(v.shape[0], -1)
 
     def device_field(self, ctx=None):
         """the reduced field as an [M, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest).  The
@@ -216,11 +182,7 @@ class ResampledGridArray(GridArray):
         M = len(off) - 1
         resident = self._resident_source()
         if resident is not None:
-            from .regrid import Regridder
-
-            rg = resident._regridder
-            if rg.ctx is not ctx:  # (the tables live on the context that runs the model)
-                rg = resident._regridder = Regridder(rg.src_coords, rg.dst_coords, resident._method, ctx)
+            rg = resident._regridder_on(ctx)
             rows, dtype = resident._coarse_stack(), np.dtype(np.float64)
             C = int(np.prod(rg.shape_out, dtype=np.int64))
         else:
@@ -244,18 +206,10 @@ class ResampledGridArray(GridArray):
         return out
 
     def _compute_values(self):
-        rest = self._rest_dims()
         field = self.device_field()
-        vals = field.to_host().reshape((len(self._labels),) + tuple(self.sizes[d] for d in rest))
+        vals = self._in_dims(field.to_host(), (self._dim,) + self._rest_dims())
         field.free()
-        order = (self._dim,) + rest
-        return vals.transpose([order.index(d) for d in self.dims])
-
-    @property
-    def values(self):
-        if self._full is None:
-            self._full = self._compute_values()
-        return self._full
+        return vals
 
     def __repr__(self):
         return (f"<ResampledGridArray {self.sizes} {self._op} over {self._dim}={self._rule!r} of {self._source.sizes} "

@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from _bins_offsets import BAD_OFFSETS, ROWS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIFT, SCALE_MEAN, SCALE_SUM = 0, 1, 2
 INVALID = 1
@@ -138,6 +140,12 @@ def test_tables(plan):
     assert check(rows, [0, 6], op=7)["message"] == "sd_disagg: unknown op code 7"
     assert check([3, 10, 5], [0, 2])["message"].startswith("sd_disagg: offsets[M]")
     assert check([3, 10, 5], [0, 3], groups=[9])["message"].startswith("sd_disagg: src_row[1]")
+
+
+@pytest.mark.parametrize("offsets,words", BAD_OFFSETS)
+def test_offsets_refusals_in_the_words_shared_with_resample(plan, offsets, words):
+    got = plan("tables", To=ROWS, C=4, Tout=ROWS, M=len(offsets) - 1, src_row=[0] * ROWS, offsets=offsets)
+    assert got == dict(error=INVALID, message=words.format(who="sd_disagg", rows="Tout"))
 
 
 def test_the_limit_of_two_to_the_31(plan):

@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+from _bins_offsets import BAD_OFFSETS, ROWS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MEAN, SUM = 0, 1
 INVALID = 1
@@ -109,6 +111,12 @@ def test_offsets_tables(plan):
     assert check([0, -1, 10])["message"] == "sd_resample: offsets decrease at bin 0 (-1 after 0)"
     # a refusal of the plan comes first and the table is not read
     assert check([0, 10], op=7)["message"] == "sd_resample: unknown op code 7"
+
+
+@pytest.mark.parametrize("offsets,words", BAD_OFFSETS)
+def test_offsets_refusals_in_the_words_shared_with_disagg(plan, offsets, words):
+    got = plan(T=ROWS, C=4, M=len(offsets) - 1, offsets=offsets)
+    assert got == dict(error=INVALID, message=words.format(who="sd_resample", rows="T"))
 
 
 def test_the_limit_of_two_to_the_31(plan):
