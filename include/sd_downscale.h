@@ -105,6 +105,15 @@ extern "C" {
 #define SD_DISAGG_SCALE_MEAN 1 /* out = x * (target / mean); a dry borrowed month gives target on every day: precipitation rates */
 #define SD_DISAGG_SCALE_SUM 2  /* out = x * (target / sum); a dry borrowed month gives target / days on every day: precipitation totals */
 
+/* sd_groupby_reduce: reduction over the rows of a group */
+#define SD_GROUPBY_MEAN 0  /* NaN samples skipped; NaN for a group without a sample */
+#define SD_GROUPBY_SUM 1   /* NaN samples skipped; 0 for a group without a sample (pandas' min_count=0) */
+/* sd_groupby_apply: out = src (op) table[group] */
+#define SD_GROUPBY_SUB 0
+#define SD_GROUPBY_ADD 1
+#define SD_GROUPBY_MUL 2
+#define SD_GROUPBY_DIV 3
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -443,6 +452,38 @@ int sd_disagg_dev(sd_ctx* ctx, int op, const double* target_dev, int64_t ld_t, c
 int sd_disagg(sd_ctx* ctx, int op, const double* target_host, const void* obs_host, int obs_is_f32, int64_t To, int64_t C,
               const int64_t* src_row, int64_t Tout, const int64_t* offsets, int64_t M, const double* climo_host_or_null, int64_t G,
               const int32_t* group_or_null, double* out_host);
+
+/* ---- grouping of the time axis: GridArray.groupby(...).mean() / .sum() and gb - clim, gb + clim, gb * clim, gb / clim ----------
+ * Every row t of a [T, C] field (cells fastest, rows ld >= C elements apart; float64, or float32 with src_is_f32 != 0, widened per
+ * sample in the kernel) carries a group id group[t] in [0, G); group is a host array of T entries.  Unlike the bins of sd_resample the
+ * rows of a group need not be consecutive, and a group may recur in a later call.
+ *
+ * reduce: the rows of the call are added, in row order, onto row group[t] of the accumulators sum [G, C] float64 and count [G, C]
+ * int32 (rows ld_acc >= C apart).  Per (group, cell) the non-NaN samples are added by a plain running sum that starts at the carried
+ * value; NaN samples are skipped by a select; count is the number of samples added.  carry == 0: the accumulators start from zero
+ * (they need not be initialised); carry != 0: they continue from what an earlier call left.  So cutting [0, T) into any sequence of
+ * calls with carry gives the same bits as one call, and the result depends neither on the launch geometry, nor on the layout, nor on
+ * the number of cells per lane.  out_dev_or_null != NULL: the result [G, C] float64 (rows ld_out >= C apart) is written from the
+ * accumulators after this call's rows: SD_GROUPBY_MEAN sum / count, NaN where count == 0 (a group id that never occurs and an
+ * all-NaN group alike); SD_GROUPBY_SUM sum, 0.0 where count == 0 (pandas' min_count=0).  inf follows IEEE arithmetic.  Where the
+ * groups are runs of consecutive rows the result is that of sd_resample bit for bit.
+ *
+ * apply: out[t, c] = src[t, c] (op) table[group[t], c] with table [G, C] float64 (rows ld_t >= C apart) and out [T, C] float64 (rows
+ * ld_out >= C apart): one IEEE subtract, add, multiply or divide per element (a zero in the table under SD_GROUPBY_DIV gives inf or
+ * NaN, a NaN stays NaN).
+ *
+ * An unknown op, sizes <= 0, G <= 0, a leading dimension below C, a group id outside [0, G) and a call too large for the grid are
+ * SD_ERR_INVALID, refused before anything is allocated or launched. */
+int sd_groupby_reduce_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C, const int32_t* group,
+                          int64_t G, double* sum_dev, int32_t* count_dev, int64_t ld_acc, int carry, double* out_dev_or_null, int64_t ld_out);
+/* host buffers: src [T, C], out [G, C]; one shot: upload, run, download */
+int sd_groupby_reduce(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int32_t* group, int64_t G,
+                      double* out_host);
+int sd_groupby_apply_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C, const int32_t* group,
+                         int64_t G, const double* table_dev, int64_t ld_t, double* out_dev, int64_t ld_out);
+/* host buffers: src [T, C], table [G, C], out [T, C]; upload, run, download */
+int sd_groupby_apply(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int32_t* group, int64_t G,
+                     const double* table_host, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

@@ -1,5 +1,5 @@
-// Device side of the binned time-axis kernels (resample_kernel: sd_resample.hip, disagg_kernel: sd_disagg.hip); the geometry is that
-// of sd_bins_plan.h.  A workgroup of kWaves waves owns one tile of 64 * V adjacent cells and a run of kBinsPerGroup consecutive bins;
+// Device side of the binned time-axis kernels (resample_kernel: sd_resample.hip, disagg_kernel: sd_disagg.hip, groupby_reduce_kernel
+// and groupby_apply_kernel: sd_groupby.hip); the geometry is that of sd_bins_plan.h.  A workgroup of kWaves waves owns one tile of 64 * V adjacent cells and a run of kBinsPerGroup consecutive bins;
 // each wave takes kBinsPerWave whole bins, one after the other, and a lane owns its V cells for the whole bin.  One row of the tile
 // is one coalesced load per wave (V * sizeof(S) bytes per lane, 16 where the plan allows); the loads of a batch of kBatch rows are
 // issued before any of their arithmetic.  A row past the end of the bin reads the bin's last row again and is not counted, so a bin
@@ -7,7 +7,8 @@
 //
 // bin_statistic is the one statistic of both kernels: the samples of a cell in time order, NaN samples skipped by a select, acc
 // their plain running sum and cnt the number of the others.  resample then disaggregate(years='same') gives the observations back
-// bit for bit because both kernels call it.
+// bit for bit because both kernels call it.  bin_accumulate is its seeded form: acc and cnt continue from what the caller put there
+// (groupby_reduce_kernel carries them from one block of the time axis to the next).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,12 +49,13 @@ __device__ __forceinline__ void store_doubles(double* p, const double (&x)[V]) {
 
 // the place of a lane in a grid of ctiles cell tiles by runs of bins: its first cell c0 and its wave's first bin m0 (wave-uniform).
 // false: the lane's cells lie past C (V divides C: the V cells are inside or outside together)
-template <int V>
+// (BPW: the whole bins of a wave, kBinsPerWave unless a plan chose otherwise)
+template <int V, int BPW = kBinsPerWave>
 __device__ __forceinline__ bool lane_place(int64_t ctiles, int64_t C, int64_t& c0, int64_t& m0) {
     const int lane = threadIdx.x % kLanes, wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kLanes);
     const int64_t ctile = blockIdx.x % ctiles, bins = blockIdx.x / ctiles;
     c0 = (ctile * kLanes + lane) * V;
-    m0 = bins * kBinsPerGroup + (int64_t)wave * kBinsPerWave;
+    m0 = bins * (kWaves * BPW) + (int64_t)wave * BPW;
     return c0 < C;
 }
 
@@ -66,9 +68,7 @@ __device__ __forceinline__ void load_batch(Cells<S, V> (&q)[kBatch], const S* co
 }
 
 template <typename S, int V, class Row>
-__device__ __forceinline__ void bin_statistic(const S* col, int64_t ld, int64_t r0, int64_t r1, Row row_of, double (&acc)[V], int (&cnt)[V]) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) acc[v] = 0.0, cnt[v] = 0;
+__device__ __forceinline__ void bin_accumulate(const S* col, int64_t ld, int64_t r0, int64_t r1, Row row_of, double (&acc)[V], int (&cnt)[V]) {
     for (int64_t r = r0; r < r1; r += kBatch) {
         Cells<S, V> q[kBatch];
         load_batch(q, col, ld, r, r1, row_of);
@@ -84,6 +84,13 @@ __device__ __forceinline__ void bin_statistic(const S* col, int64_t ld, int64_t 
             }
         }
     }
+}
+
+template <typename S, int V, class Row>
+__device__ __forceinline__ void bin_statistic(const S* col, int64_t ld, int64_t r0, int64_t r1, Row row_of, double (&acc)[V], int (&cnt)[V]) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = 0.0, cnt[v] = 0;
+    bin_accumulate<S, V>(col, ld, r0, r1, row_of, acc, cnt);
 }
 
 // f(the source as const float* or const double*, std::integral_constant<int, cols>) for the (is_f32, cols) of a plan

@@ -1,4 +1,5 @@
-// What the launch plans of the binned time-axis kernels share (resample_kernel: sd_resample_plan.h, disagg_kernel: sd_disagg_plan.h),
+// What the launch plans of the binned time-axis kernels share (resample_kernel: sd_resample_plan.h, disagg_kernel: sd_disagg_plan.h,
+// the groupby kernels: sd_groupby_plan.h),
 // as pure host functions (no HIP header: the plan drivers under tests/ compile it with g++ alone).  Both kernels walk a [rows, C]
 // field, cells fastest, by bins of consecutive rows that pandas made on the host: a table offsets [M + 1], bin m = rows
 // offsets[m] .. offsets[m + 1] - 1; an empty bin has offsets[m] == offsets[m + 1].

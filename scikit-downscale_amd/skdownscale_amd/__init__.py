@@ -12,6 +12,7 @@ from .grouping import GroupedGridModel, GroupedRegressor
 from .regrid import InterpolatedGridArray, Regridder
 from .resample import GridResample, ResampledGridArray, time_bins
 from .disagg import DisaggregatedGridArray, time_map
+from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, group_labels
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -54,5 +55,9 @@ __all__ = [
     "time_bins",
     "DisaggregatedGridArray",
     "time_map",
+    "GridGroupBy",
+    "GroupReducedGridArray",
+    "GroupAppliedGridArray",
+    "group_labels",
 ]
 __version__ = "0.1.0"

@@ -26,6 +26,8 @@ QM_EXTRAP_CODES = {None: 0, "min": 1, "max": 2, "both": 3, "1to1": 4}  # regress
 REGRID_METHODS = {"linear": 0, "nearest": 1}  # SD_REGRID_*
 RESAMPLE_OPS = {"mean": 0, "sum": 1}  # SD_RESAMPLE_*
 DISAGG_OPS = {"shift": 0, "scale_mean": 1, "scale_sum": 2}  # SD_DISAGG_*
+GROUPBY_REDUCE_OPS = {"mean": 0, "sum": 1}  # SD_GROUPBY_MEAN / _SUM
+GROUPBY_APPLY_OPS = {"sub": 0, "add": 1, "mul": 2, "div": 3}  # SD_GROUPBY_SUB .. _DIV
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -134,6 +136,10 @@ SIGNATURES = {
     "sd_resample": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p],
     "sd_disagg_dev": [_p, _int, _p, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _i64],
     "sd_disagg": [_p, _int, _p, _p, _int, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p],
+    "sd_groupby_reduce_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _int, _p, _i64],
+    "sd_groupby_reduce": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p],
+    "sd_groupby_apply_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64],
+    "sd_groupby_apply": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -134,6 +134,20 @@ class GridArray:
         (dim, rule), = named.items()
         return GridResample(self, dim, rule, kwargs, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def groupby(self, group=None, scratch_bytes=None, name="group", **named):
+        """``groupby("time.month").mean()`` / ``.sum()`` and ``gb - clim`` / ``+`` / ``*`` / ``/``: climatologies and anomalies per cell
+        on the GPU (``xarray``'s ``da.groupby`` for these; pandas' ``DataFrame.groupby(key).mean()`` / ``.sum()`` per cell).  ``group``:
+        ``"<dim>.<field>"`` with ``field`` an attribute of the dim's ``DatetimeIndex`` (``month``, ``dayofyear``, ``year``, ``day``,
+        ``hour``, ``quarter``, ``dayofweek`` ...) or ``season`` (``DJF`` / ``JJA`` / ``MAM`` / ``SON``): the group dim is named after the
+        field.  Or one ``dim=labels`` (one label per step) / ``dim=callable`` (applied to every timestamp: ``MONTH_GROUPER``): the group
+        dim is named ``name``.  The groups are the sorted unique labels present.  NaN samples are skipped; a group without a non-NaN
+        sample gives NaN for ``mean`` and 0.0 for ``sum``.  ``scratch_bytes``: device scratch of one block of time steps (default
+        1 GiB).  -> ``GridGroupBy``: the labels are made, nothing is computed yet."""
+        from .groupby import GridGroupBy
+        from .resample import DEFAULT_SCRATCH_BYTES
+
+        return GridGroupBy(self, group, named, name, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
         """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
         daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and

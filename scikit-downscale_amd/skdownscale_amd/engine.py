@@ -1076,6 +1076,107 @@ class Context:
                                  None if group is None else ptr(group), ptr(out)))
         return out
 
+    # ---- grouping of the time axis (GridArray.groupby) ----
+    @staticmethod
+    def _groupby_args(who, field, group, G, op, ops):
+        if op not in ops:
+            raise NotImplementedError(f"{who} op {op!r}: only {', '.join(repr(k) for k in ops)} are implemented")
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (field.shape[0],):
+            raise ValueError(f"group: expected one group id per row ({field.shape[0]}), got shape {group.shape}")
+        T, Cc = field.shape
+        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
+            raise ValueError(f"sd_downscale: sd_{who}: bad sizes (T={T}, C={Cc})")
+        if int(G) < 1:
+            raise ValueError(f"sd_downscale: sd_{who}: bad sizes (G={int(G)})")
+        return field, group, int(G), ops[op], int(field.dtype == np.float32)
+
+    def groupby_reduce(self, field, group, G, op="mean", acc=None, out=None, finish=True):
+        """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); group:
+        host int32 [T], every id in [0, G).  The rows are added, in row order, onto row ``group[t]`` of the accumulators ``acc`` = (sum
+        [G, C] float64, count [G, C] int32, two DeviceArrays of one ``ld``): the pair an earlier call returned, which this call
+        continues, or None for new ones that start from zero.  -> ``(result, acc)``: with ``finish`` the [G, C] float64 DeviceArray
+        of op 'mean' | 'sum' over everything added so far (``out``: a [G, C] DeviceArray, possibly a view of a wider or longer one),
+        else None; NaN samples skipped (sd_groupby_reduce_dev).  Any cut of the rows into calls gives the bits of one call."""
+        field, group, G, code, f32 = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
+        mine = None
+        if not isinstance(field, DeviceArray):
+            field = mine = self.to_device(field, field.dtype)
+        T, Cc = field.shape
+        carry = acc is not None
+        if carry:
+            s, n = acc
+            if (tuple(s.shape), s.dtype, tuple(n.shape), n.dtype) != ((G, Cc), np.float64, (G, Cc), np.int32) or s.ld != n.ld:
+                raise ValueError(f"acc: expected the (sum float64, count int32) pair of [{G}, {Cc}] DeviceArrays of an earlier call")
+        else:
+            s, n = self.empty((G, Cc)), self.empty((G, Cc), np.int32)
+        out = self._result_buffer(out, (G, Cc), True) if finish else None
+        try:
+            for name, a in (("field", field), ("sum", s), ("count", n), ("out", out)):
+                if a is not None and a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_groupby_reduce: `{name}` belongs to another context")
+            check(self.lib.sd_groupby_reduce_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, s.vptr, n.vptr, s.ld,
+                                                 int(carry), None if out is None else out.vptr, 0 if out is None else out.ld))
+        finally:
+            if mine is not None:
+                mine.free()
+        return out, (s, n)
+
+    def groupby_reduce_host(self, field, group, G, op="mean"):
+        """host [T, C] -> host [G, C] through sd_groupby_reduce (upload, run, download in one call)"""
+        field, group, G, code, f32 = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
+        if isinstance(field, DeviceArray):
+            raise ValueError("groupby_reduce_host: expected a host array")
+        T, Cc = field.shape
+        out = np.empty((G, Cc))
+        check(self.lib.sd_groupby_reduce(self.handle, code, ptr(field), f32, T, Cc, ptr(group), G, ptr(out)))
+        return out
+
+    def groupby_apply(self, field, group, table, op, out=None):
+        """field [T, C] as for ``groupby_reduce``; table [G, C] float64: a host array or DeviceArray; group: host int32 [T] in [0, G)
+        -> [T, C] float64 DeviceArray ``field (op) table[group]``, op 'sub' | 'add' | 'mul' | 'div', one IEEE operation per element
+        (``out``: a [T, C] DeviceArray, possibly a view of a wider or longer one) (sd_groupby_apply_dev)."""
+        if not isinstance(table, DeviceArray):
+            table = np.ascontiguousarray(table, dtype=np.float64)
+        if len(table.shape) != 2 or table.dtype != np.float64:
+            raise ValueError(f"table: expected a float64 [G, C] field, got shape {tuple(table.shape)} of {table.dtype}")
+        field, group, G, code, f32 = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
+        if table.shape[1] != field.shape[1]:
+            raise ValueError(f"table: expected a float64 [G, {field.shape[1]}] field, got shape {tuple(table.shape)}")
+        mine = []  # (what this call uploads, freed when it is over)
+        T, Cc = field.shape
+        out = self._result_buffer(out, (T, Cc), True)
+        try:
+            if not isinstance(field, DeviceArray):
+                field = self.to_device(field, field.dtype)
+                mine.append(field)
+            if not isinstance(table, DeviceArray):
+                table = self.to_device(table)
+                mine.append(table)
+            for name, a in (("field", field), ("table", table), ("out", out)):
+                if a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_groupby_apply: `{name}` belongs to another context")
+            check(self.lib.sd_groupby_apply_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, table.vptr, table.ld, out.vptr,
+                                                out.ld))
+        finally:
+            for a in mine:
+                a.free()
+        return out
+
+    def groupby_apply_host(self, field, group, table, op):
+        """host field [T, C], table [G, C] -> host [T, C] through sd_groupby_apply (upload, run, download in one call)"""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        field, group, G, code, f32 = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
+        if isinstance(field, DeviceArray) or table.ndim != 2 or table.shape[1] != field.shape[1]:
+            raise ValueError("groupby_apply_host: expected a host [T, C] field and a host [G, C] table")
+        out = np.empty(field.shape)
+        check(self.lib.sd_groupby_apply(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], ptr(group), G, ptr(table), ptr(out)))
+        return out
+
 
 _default_ctx = None
 

@@ -64,6 +64,26 @@ def _bin_blocks(offsets, max_rows):
     return blocks
 
 
+def resident_source(src, dim):
+    """``src`` when it is an unchunked ``coarse.interp_like(obs)`` with dims (dim, y, x): its fine field can be produced in HBM, block
+    of rows by block of rows (``src._regridder_on(ctx).regrid(src._coarse_stack()[r0:r1], out=block)``); else None.  The rule of every
+    lazy array that walks the time axis of a source (``ResampledGridArray``, the groupby arrays)."""
+    from .regrid import InterpolatedGridArray
+
+    if not isinstance(src, InterpolatedGridArray) or len(src.dims) != 3 or src.dims[0] != dim or src._lead_dims() != src.dims[:1]:
+        return None
+    if src.chunksizes is not None and any(len(src.chunksizes[d]) > 1 for d in src.dims[1:]):
+        return None
+    return src
+
+
+def host_rows(src, dim):
+    """``src`` as a host [T, C] array, ``dim`` first and the other dims flattened in their order; float32 stays float32"""
+    rest = tuple(d for d in src.dims if d != dim)
+    v = _lib.as_field((src.transpose(dim, *rest) if src.dims[0] != dim else src).values)
+    return v.reshape(v.shape[0], -1)
+
+
 class GridResample:
     """``GridArray.resample(time=rule, **kw)``: the bins are made, nothing is reduced yet.  ``mean()`` / ``sum()`` ->
     ``ResampledGridArray``."""
@@ -155,22 +175,10 @@ class ResampledGridArray(DeferredGridArray):
         return tuple(d for d in self.dims if d != self._dim)
 
     def _resident_source(self):
-        """(regridder of the source, its coarse [T, ny, nx] stack) when the source is an unchunked ``coarse.interp_like(obs)`` with
-        dims (time, y, x): its fine field can be produced in HBM"""
-        from .regrid import InterpolatedGridArray
-
-        src = self._source
-        if not isinstance(src, InterpolatedGridArray) or len(src.dims) != 3 or src.dims[0] != self._dim or src._lead_dims() != src.dims[:1]:
-            return None
-        if src.chunksizes is not None and any(len(src.chunksizes[d]) > 1 for d in src.dims[1:]):
-            return None
-        return src
+        return resident_source(self._source, self._dim)
 
     def _host_rows(self):
-        """the source as a host [T, C] array, the other dims flattened in their order; float32 stays float32"""
-        src = self._source.transpose(self._dim, *self._rest_dims()) if self.dims[0] != self._dim else self._source
-        v = _lib.as_field(src.values)
-        return v.reshape(v.shape[0], -1)
+        return host_rows(self._source, self._dim)
 
     def device_field(self, ctx=None):
         """the reduced field as an [M, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest).  The

@@ -251,9 +251,89 @@ def bench_disagg(ctx, args):
     return res
 
 
+def bench_groupby(ctx, args):
+    """groupby_reduce_kernel by month (G = 12) and by day of year (G = 366, mean) and groupby_apply_kernel (SUB of the monthly
+    climatology) on 14 600 daily steps x 100 000 cells, float64 and float32 sources, each timed through ctx.prof() beside sd_memcpy_d2d
+    of the same source bytes and beside resample_kernel ('MS', mean) on the same field in the same run; GB/s by algorithmic bytes
+    (reduce: the source read once + 12 * G * C accumulators + 8 * G * C written; apply: the source + 8 * G * C read, 8 * T * C written);
+    the first 256 cells compared bit for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _groupby_oracle as go
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    _, offsets = time_bins(index, "MS")
+    groups = {"month": (np.asarray(index.month) - 1).astype(np.int32), "dayofyear": (np.asarray(index.dayofyear) - 1).astype(np.int32)}
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(kernel, call, repeats):
+        call()
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            times.append(ctx.prof()[kernel]["ms"])
+        ctx.prof_enable(False)
+        return float(np.median(times)), [min(times), max(times)]
+
+    d64, first = fill(C), fill(256).to_host()
+    spare, monthly = ctx.empty((T, C)), ctx.empty((len(offsets) - 1, C))
+    repeats = max(args.steps, 5)
+    res = {"workload": f"groupby {T} daily steps x {C} cells: mean by month (G=12) and by day of year (G=366), minus the monthly climatology",
+           "repeats": repeats, "bins_per_wave": {"G=12": 1, "G=366": 2}}
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        if dtype == np.float32:
+            d = ctx.empty((T, C), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, d64.vptr, T * C, d.vptr))
+            ctx.synchronize()
+        else:
+            d = d64
+        host = first.astype(dtype)
+        src_bytes = T * C * np.dtype(dtype).itemsize
+        copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+        rs_ms, rs_min_max = timed("resample_kernel", lambda: ctx.resample(d, offsets, "mean", out=monthly), repeats)
+        leg = {"device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6},
+               "resample_kernel_MS_mean": {"kernel_ms": rs_ms, "kernel_ms_min_max": rs_min_max}}
+        clim = None
+        for key, group in groups.items():
+            G = int(group.max()) + 1
+            out = ctx.empty((G, C))
+
+            def reduce():
+                for a in ctx.groupby_reduce(d, group, G, "mean", out=out)[1]:
+                    a.free()
+
+            ms, min_max = timed("groupby_reduce_kernel", reduce, repeats)
+            nbytes = src_bytes + 12 * G * C + 8 * G * C
+            same = bool(np.array_equal(out.cells(0, 256).to_host(), go.reduce(host, group, G, "mean"), equal_nan=True))
+            leg[f"reduce_{key}"] = {"G": G, "kernel_ms": ms, "kernel_ms_min_max": min_max, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                                    "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": same,
+                                    "kernel_over_copy_ms": ms / copy_ms, "kernel_over_resample_ms": ms / rs_ms}
+            if key == "month":
+                clim = out
+            else:
+                out.free()
+        ms, min_max = timed("groupby_apply_kernel", lambda: ctx.groupby_apply(d, groups["month"], clim, "sub", out=spare), repeats)
+        nbytes = src_bytes + 8 * 12 * C + 8 * T * C
+        same = bool(np.array_equal(spare.cells(0, 256).to_host(), go.apply(host, groups["month"], clim.cells(0, 256).to_host(), "sub"), equal_nan=True))
+        leg["apply_sub_month"] = {"G": 12, "kernel_ms": ms, "kernel_ms_min_max": min_max, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                                  "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": same,
+                                  "kernel_over_copy_ms": ms / copy_ms, "kernel_over_resample_ms": ms / rs_ms}
+        clim.free()
+        res[name] = leg
+        if d is not d64:
+            d.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -264,8 +344,9 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg"):
-        line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg}[args.workload](ctx, args))
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby"):
+        line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
+                           "groupby": bench_groupby}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
