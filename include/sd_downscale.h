@@ -114,6 +114,12 @@ extern "C" {
 #define SD_GROUPBY_MUL 2
 #define SD_GROUPBY_DIV 3
 
+/* sd_rolling: statistic of a window of rows */
+#define SD_ROLLING_MEAN 0  /* NaN samples skipped; NaN where fewer than min_periods samples, or none */
+#define SD_ROLLING_SUM 1   /* NaN samples skipped; 0 for a window without a sample under min_periods == 0 */
+#define SD_ROLLING_VAR 2   /* sum of squared deviations from the window's mean / (n - ddof); NaN where n - ddof <= 0 */
+#define SD_ROLLING_STD 3   /* sqrt of SD_ROLLING_VAR */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -484,6 +490,28 @@ int sd_groupby_apply_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f3
 /* host buffers: src [T, C], table [G, C], out [T, C]; upload, run, download */
 int sd_groupby_apply(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int32_t* group, int64_t G,
                      const double* table_host, double* out_host);
+
+/* ---- rolling windows over the time axis: GridArray.rolling(time=w, center=..., min_periods=...).mean() / .sum() / .var() / .std() ----
+ * pandas' fixed integer window per cell.  src is a [T, C] block (cells fastest, rows ld >= C elements apart; float64, or float32 with
+ * src_is_f32 != 0, widened per sample in the kernel).  The window of row t is the rows t - back .. t - back + window - 1 (back =
+ * window - 1: pandas' trailing window; back = window / 2: center=True), clipped to [0, T), or, with wrap != 0, taken modulo T (an
+ * extension: pandas on the series padded from its other end).  The rows t0 .. t0 + n_out - 1 are written to out [n_out, C] float64
+ * (rows ld_out >= C apart): a caller may hand over a block with its halo rows and ask for the interior only.
+ *
+ * A window is evaluated directly, in time order, over its non-NaN samples (n of them): s = ((+0.0 + x_a) + x_b) + ...;
+ * SD_ROLLING_SUM s; SD_ROLLING_MEAN s / n, NaN where n == 0; SD_ROLLING_VAR q / (n - ddof) with q = sum of (x_i - s / n)^2 in the
+ * same order from +0.0, NaN where n - ddof <= 0; SD_ROLLING_STD its square root.  The result is NaN where n < min_periods.  One IEEE
+ * operation per step: a result depends on its own window only, so any cut of the time axis, any layout and any launch geometry give
+ * the same bits.  The work is O(window) per output.
+ *
+ * An unknown op, sizes <= 0, window < 1, back outside [0, window), min_periods outside [0, window], ddof < 0, output rows outside
+ * [0, T), wrap with window > T, a leading dimension below C and a call too large for the grid are SD_ERR_INVALID, refused before
+ * anything is allocated or launched. */
+int sd_rolling_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C, int64_t window, int64_t back,
+                   int64_t min_periods, int64_t ddof, int wrap, int64_t t0, int64_t n_out, double* out_dev, int64_t ld_out);
+/* host buffers: src [T, C], out [T, C]; the whole field in one call: upload, run, download */
+int sd_rolling(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, int64_t window, int64_t back,
+               int64_t min_periods, int64_t ddof, int wrap, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

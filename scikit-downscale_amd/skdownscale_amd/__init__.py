@@ -13,6 +13,7 @@ from .regrid import InterpolatedGridArray, Regridder
 from .resample import GridResample, ResampledGridArray, time_bins
 from .disagg import DisaggregatedGridArray, time_map
 from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, group_labels
+from .rolling import GridRolling, RolledGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -59,5 +60,7 @@ __all__ = [
     "GroupReducedGridArray",
     "GroupAppliedGridArray",
     "group_labels",
+    "GridRolling",
+    "RolledGridArray",
 ]
 __version__ = "0.1.0"

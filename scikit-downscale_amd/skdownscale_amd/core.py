@@ -148,6 +148,26 @@ class GridArray:
 
         return GridGroupBy(self, group, named, name, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def rolling(self, dim=None, center=False, min_periods=None, wrap=False, scratch_bytes=None, **window):
+        """``rolling(time=9, center=True, min_periods=1).mean()`` / ``.sum()`` / ``.var(ddof=1)`` / ``.std(ddof=1)``: pandas' fixed
+        integer window per cell on the GPU (``rolling({"time": 9}, ...)`` is the same).  The window of step t is the steps
+        ``t - (w - 1) .. t``, or ``t - w // 2 .. t - w // 2 + w - 1`` with ``center``, clipped to the array or, with ``wrap=True``, taken
+        around its ends (a circular axis such as the day of the year: pandas on the series padded from its other end).  NaN samples are
+        skipped; fewer than ``min_periods`` (default: the window) samples give NaN.  Each window is evaluated directly in time order:
+        O(window) work per output, and a result that does not depend on how ``scratch_bytes`` (device scratch of one block of time
+        steps, default 1 GiB) cuts the axis.  -> ``GridRolling``: nothing is computed yet."""
+        from .resample import DEFAULT_SCRATCH_BYTES
+        from .rolling import GridRolling
+
+        named = dict(dim or {}) if dim is None or isinstance(dim, dict) else None
+        if named is None:
+            raise ValueError(f"rolling needs {{dim: window}} or dim=window, got {dim!r}")
+        named.update(window)
+        if len(named) != 1:
+            raise ValueError(f"rolling needs exactly one dim=window, got {sorted(named)} (dims of this array: {self.dims})")
+        (d, w), = named.items()
+        return GridRolling(self, d, w, center, min_periods, wrap, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
         """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
         daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and

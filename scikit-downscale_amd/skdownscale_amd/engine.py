@@ -1177,6 +1177,61 @@ class Context:
         check(self.lib.sd_groupby_apply(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], ptr(group), G, ptr(table), ptr(out)))
         return out
 
+    # ---- rolling windows over the time axis (GridArray.rolling) ----
+    @staticmethod
+    def _rolling_args(field, window, op, back, min_periods, ddof):
+        if op not in _lib.ROLLING_OPS:
+            raise NotImplementedError(f"rolling op {op!r}: only {', '.join(repr(k) for k in _lib.ROLLING_OPS)} are implemented")
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        T, Cc = field.shape
+        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_rolling: bad sizes (T={T}, C={Cc})")
+        window = int(window)
+        back = window - 1 if back is None else int(back)
+        min_periods = window if min_periods is None else int(min_periods)
+        return field, window, back, min_periods, int(ddof), _lib.ROLLING_OPS[op], int(field.dtype == np.float32)
+
+    def rolling(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False, t0=0, n_out=None, out=None):
+        """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart) ->
+        [n_out, C] float64 DeviceArray: the rows ``t0 .. t0 + n_out - 1`` (default: all) of the rolling statistic op 'mean' | 'sum' |
+        'var' | 'std' (``ddof`` for the last two).  The window of row t is the rows ``t - back .. t - back + window - 1`` (``back``
+        defaults to ``window - 1``, pandas' trailing window; ``window // 2`` is ``center=True``), clipped to the field or, with
+        ``wrap``, taken modulo T; NaN samples are skipped, fewer than ``min_periods`` (default ``window``) give NaN.  ``out``: a
+        [n_out, C] DeviceArray, possibly a view of a wider or longer one.  O(window) work per output (sd_rolling_dev)."""
+        field, window, back, min_periods, ddof, code, f32 = self._rolling_args(field, window, op, back, min_periods, ddof)
+        T, Cc = field.shape
+        t0 = int(t0)
+        n_out = T - t0 if n_out is None else int(n_out)
+        if n_out < 1:
+            raise ValueError(f"sd_downscale: sd_rolling: the output rows {t0} .. {t0 + n_out - 1} lie outside the {T} rows of the source")
+        mine = None
+        out = self._result_buffer(out, (n_out, Cc), True)
+        try:
+            if not isinstance(field, DeviceArray):
+                field = mine = self.to_device(field, field.dtype)
+            for name, a in (("field", field), ("out", out)):
+                if a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_rolling: `{name}` belongs to another context")
+            check(self.lib.sd_rolling_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, window, back, min_periods, ddof, int(bool(wrap)), t0,
+                                          n_out, out.vptr, out.ld))
+        finally:
+            if mine is not None:
+                mine.free()
+        return out
+
+    def rolling_host(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False):
+        """host [T, C] -> host [T, C] through sd_rolling (upload, run, download in one call)"""
+        field, window, back, min_periods, ddof, code, f32 = self._rolling_args(field, window, op, back, min_periods, ddof)
+        if isinstance(field, DeviceArray):
+            raise ValueError("rolling_host: expected a host array")
+        out = np.empty(field.shape)
+        check(self.lib.sd_rolling(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], window, back, min_periods, ddof,
+                                  int(bool(wrap)), ptr(out)))
+        return out
+
 
 _default_ctx = None
 

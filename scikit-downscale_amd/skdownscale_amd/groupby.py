@@ -7,7 +7,8 @@ returns, ``GroupReducedGridArray`` is what its ``mean()`` / ``sum()`` return and
 ``gb + other``, ``gb * other`` and ``gb / other`` return: the source and the group ids, computed when the field is asked for -- on the
 host through ``values``, or as a ``DeviceArray`` through ``device_field``.  The source is walked in blocks of time steps: a block of
 ``coarse.interp_like(obs)`` is regridded into device scratch, a block of a host array is uploaded into it (float32 as float32), and a
-``ResampledGridArray`` is reduced in HBM by its own ``device_field``; none of them crosses PCIe as a fine float64 field.
+``ResampledGridArray`` is reduced in HBM by its own ``device_field`` (a lazy ``RolledGridArray`` likewise); none of them crosses PCIe as a
+fine float64 field.
 
 Groups recur -- every year has a January --, so the reduction carries its sums from block to block; the samples of a (group, cell)
 are added in time order whatever the blocks, so the result does not depend on where they are cut.
@@ -54,16 +55,42 @@ def _time_blocks(T, max_rows):
     return [(r0, min(T, r0 + max_rows)) for r0 in range(0, T, max_rows)]
 
 
-def _walk_source(source, dim, ctx, scratch_bytes, visit):
+def _halo_blocks(T, max_rows, halo):
+    """[0, T) in consecutive runs [r0, r1) with the rows [b0, b1) = [r0 - before, r1 + after) clipped to [0, T) that a window reaching
+    ``halo = (before, after)`` rows around each of its rows touches: ``(r0, r1, b0, b1)`` with at most ``max_rows`` rows in [b0, b1).
+    None where ``max_rows`` has no room for one row beside its halo."""
+    before, after = halo
+    if max_rows >= T:
+        return [(0, T, 0, T)]
+    step = max_rows - before - after
+    if step < 1:
+        return None
+    return [(r0, min(T, r0 + step), max(0, r0 - before), min(T, r0 + step + after)) for r0 in range(0, T, step)]
+
+
+def _lazy_dim(source, also=()):
+    """the dim along which a not yet computed lazy array gives its field as [rows of that dim, cells of the other dims in their order]
+    through ``device_field``; None for any other array.  ``also``: classes taken beside ``ResampledGridArray`` / ``RolledGridArray``"""
+    from .rolling import RolledGridArray
+
+    if not isinstance(source, (ResampledGridArray, RolledGridArray) + tuple(also)) or source.computed:
+        return None
+    return source._gdim if isinstance(source, GroupReducedGridArray) else source._dim
+
+
+def _walk_source(source, dim, ctx, scratch_bytes, visit, halo=None, also_lazy=()):
     """``visit(r0, r1, block)`` for consecutive blocks of time steps of ``source``: ``block`` is the [r1 - r0, C] DeviceArray of the rows
-    r0 .. r1 - 1 (C = cells of the other dims in their order, the last fastest), valid during the visit.  A ``ResampledGridArray`` is
-    one block, reduced in HBM; an unchunked ``coarse.interp_like(obs)`` is regridded, and any other array uploaded, in blocks of at
-    most ``scratch_bytes`` of device scratch."""
+    r0 .. r1 - 1 (C = cells of the other dims in their order, the last fastest), valid during the visit.  A lazy ``ResampledGridArray``
+    or ``RolledGridArray`` (and those of ``also_lazy``) is one block, computed in HBM; an unchunked ``coarse.interp_like(obs)`` is
+    regridded, and any other array uploaded, in blocks of at most ``scratch_bytes`` of device scratch.
+
+    With ``halo = (before, after)`` a block also holds up to ``before`` rows in front of r0 and ``after`` rows behind r1 - 1, clipped to
+    the array: ``visit(r0, r1, block, b0)`` with ``block`` the rows b0 .. of the source, through r1 - 1 + after."""
     T = source.sizes[dim]
-    if isinstance(source, ResampledGridArray) and not source.computed and source._dim == dim:
+    if _lazy_dim(source, also_lazy) == dim:
         field = source.device_field(ctx)
         try:
-            visit(0, T, field)
+            visit(0, T, field) if halo is None else visit(0, T, field, 0)
         finally:
             field.free()
         return
@@ -78,15 +105,22 @@ def _walk_source(source, dim, ctx, scratch_bytes, visit):
     if min(T, C) < 1:
         raise ValueError(f"nothing to group: the array has sizes {source.sizes}")
     max_rows = min(T, max(1, int(scratch_bytes) // (C * dtype.itemsize)))
-    scratch = ctx.empty((max_rows, C), dtype)
+    if halo is None:
+        blocks = [(r0, r1, r0, r1) for r0, r1 in _time_blocks(T, max_rows)]
+    else:
+        blocks = _halo_blocks(T, max_rows, halo)
+        if blocks is None:
+            raise ValueError(f"scratch_bytes={int(scratch_bytes)} holds {max_rows} steps of {C} cells: too few for one step and the "
+                             f"{halo[0]} + {halo[1]} steps of its window around it; raise scratch_bytes")
+    scratch = ctx.empty((max(b1 - b0 for _, _, b0, b1 in blocks), C), dtype)
     try:
-        for r0, r1 in _time_blocks(T, max_rows):
-            block = scratch.rows(0, r1 - r0)
+        for r0, r1, b0, b1 in blocks:
+            block = scratch.rows(0, b1 - b0)
             if resident is not None:
-                rg.regrid(rows[r0:r1], out=block)
+                rg.regrid(rows[b0:b1], out=block)
             else:
-                block.copy_from_host(rows[r0:r1])
-            visit(r0, r1, block)
+                block.copy_from_host(rows[b0:b1])
+            visit(r0, r1, block) if halo is None else visit(r0, r1, block, b0)
     finally:
         scratch.free()
 
@@ -308,11 +342,14 @@ class GroupAppliedGridArray(DeferredGridArray):
         return self._group
 
     def _table(self, ctx):
-        """other as a [G', C] float64 DeviceArray in this array's cell order: a lazy reduction in that order is computed in HBM, any
-        other array goes up once"""
+        """other as a [G', C] float64 DeviceArray in this array's cell order: a lazy reduction in that order, or a lazy rolling
+        statistic of one, is computed in HBM, any other array goes up once"""
         order = (self._gdim,) + self._rest
         o = self._other
-        if isinstance(o, GroupReducedGridArray) and tuple(o.dims) == order and not o.computed:
+        from .rolling import RolledGridArray
+
+        lazy = isinstance(o, (GroupReducedGridArray, RolledGridArray)) and _lazy_dim(o, (GroupReducedGridArray,)) == self._gdim
+        if lazy and tuple(o.dims) == order:
             return o.device_field(ctx)
         v = np.ascontiguousarray((o if tuple(o.dims) == order else o.transpose(*order)).values, dtype=np.float64)
         return ctx.to_device(v.reshape(v.shape[0], -1))

@@ -331,9 +331,75 @@ def bench_groupby(ctx, args):
     return res
 
 
+def bench_rolling(ctx, args):
+    """rolling_kernel on 14 600 daily steps x 100 000 cells, float64 and float32 sources: centred mean at w = 9 and w = 31, centred std at
+    w = 31 (staged in LDS) and a centred mean at w = 91 (too long for the LDS budget: rolling_unstaged_kernel), each the median of 7
+    HIP-event times through ctx.prof() beside sd_memcpy_d2d of the same source bytes and beside groupby_apply_kernel (SUB of the monthly
+    climatology: the same traffic, source read once and T * C doubles written) on the same field in the same run; GB/s by algorithmic
+    bytes (the source read once + 8 * T * C written); the first 256 cells compared bit for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _rolling_oracle as ro
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    month = (np.asarray(index.month) - 1).astype(np.int32)
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(kernel, call, repeats):
+        call()
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            times.append(ctx.prof()[kernel]["ms"])
+        ctx.prof_enable(False)
+        return float(np.median(times)), [min(times), max(times)]
+
+    d64, first = fill(C), fill(256).to_host()
+    spare = ctx.empty((T, C))
+    repeats = max(args.steps, 7)
+    cases = (("mean_w9", 9, "mean", "rolling_kernel"), ("mean_w31", 31, "mean", "rolling_kernel"), ("std_w31", 31, "std", "rolling_kernel"),
+             ("mean_w91_unstaged", 91, "mean", "rolling_unstaged_kernel"))
+    res = {"workload": f"rolling {T} daily steps x {C} cells, centred windows: mean w=9, mean w=31, std w=31 (staged), mean w=91 (unstaged)",
+           "repeats": repeats}
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        if dtype == np.float32:
+            d = ctx.empty((T, C), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, d64.vptr, T * C, d.vptr))
+            ctx.synchronize()
+        else:
+            d = d64
+        host = first.astype(dtype)
+        src_bytes = T * C * np.dtype(dtype).itemsize
+        nbytes = src_bytes + 8 * T * C
+        copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+        clim, acc = ctx.groupby_reduce(d, month, 12, "mean")
+        for a in acc:
+            a.free()
+        ap_ms, ap_min_max = timed("groupby_apply_kernel", lambda: ctx.groupby_apply(d, month, clim, "sub", out=spare), repeats)
+        clim.free()
+        leg = {"device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6},
+               "groupby_apply_kernel_sub_month": {"kernel_ms": ap_ms, "kernel_ms_min_max": ap_min_max, "GBps": (nbytes + 8 * 12 * C) / ap_ms / 1e6}}
+        for key, w, op, kernel in cases:
+            back = w // 2
+            ms, min_max = timed(kernel, lambda: ctx.rolling(d, w, op, back, 1, out=spare), repeats)
+            same = bool(np.array_equal(spare.cells(0, 256).to_host(), ro.finish(ro.moments(host, w, back), op, 1, 1), equal_nan=True))
+            leg[key] = {"window": w, "op": op, "kernel": kernel, "kernel_ms": ms, "kernel_ms_min_max": min_max, "algorithmic_bytes": nbytes,
+                        "GBps": nbytes / ms / 1e6, "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": same,
+                        "kernel_over_copy_ms": ms / copy_ms, "kernel_over_apply_ms": ms / ap_ms}
+        res[name] = leg
+        if d is not d64:
+            d.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -344,9 +410,9 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
-                           "groupby": bench_groupby}[args.workload](ctx, args))
+                           "groupby": bench_groupby, "rolling": bench_rolling}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
