@@ -132,6 +132,7 @@ typedef struct sd_zscore_state sd_zscore_state;
 typedef struct sd_grouped_state sd_grouped_state;
 typedef struct sd_arrm_state sd_arrm_state;
 typedef struct sd_regrid sd_regrid;
+typedef struct sd_remap sd_remap;
 typedef struct sd_comm sd_comm;
 #define SD_COMM_ID_BYTES 128 /* RCCL's ncclUniqueId */
 
@@ -422,6 +423,34 @@ int sd_regrid_apply_dev(sd_ctx* ctx, const sd_regrid* rg, const void* src_dev, i
                         int64_t ld_out);
 /* host buffers: src [T, ny, nx], out [T, Ny * Nx] */
 int sd_regrid_apply(sd_ctx* ctx, const sd_regrid* rg, const void* src_host, int src_is_f32, int64_t T, double* out_host);
+
+/* ---- conservative remapping: GridArray.remap_like (fine to coarse, first order, area overlap) -----------------
+ * A [T, ny, nx] field (rows of a step contiguous, steps ld >= ny * nx elements apart) on a rectilinear grid is averaged onto the
+ * cells of an [Ny, Nx] rectilinear grid; the result is a [T, C] float64 field, C = Ny * Nx, cells fastest, rows ld_out >= C apart.
+ * Each dimension is given by its cell bounds (src_yb [ny + 1], src_xb [nx + 1], dst_yb [Ny + 1], dst_xb [Nx + 1]), strictly
+ * ascending or descending as stored, in the units whose differences are the weights (the caller transforms latitudes: no sin here).
+ * Per dimension the overlap of source cell k with target cell j is w = min(sb_hi, db_hi) - max(sb_lo, db_lo) on the ascending-ordered
+ * bounds; only overlaps > 0 count, they form one contiguous run of source cells per target cell, and full[j] is their running sum
+ * from +0.0 in stored order (at most n_src + n_dst - 1 entries per dimension; never a per-cell table).  Per step and target (j, i),
+ * every product rounded on its own and every sum a running sum from +0.0 in stored order:
+ *   cn[x] = sum over the rows y of run j of wy[y] * (v[t, y, x] is NaN ? 0 : v),  cd[x] = sum of wy[y] * (v is NaN ? 0 : 1)
+ *   num = sum over the columns x of run i of wx[x] * cn[x],                        den = sum of wx[x] * cd[x]
+ *   out = num / den  if den > 0 and den >= min_valid * (full_y[j] * full_x[i]) * (1 - 2^-30),  else NaN
+ * min_valid in [0, 1] is the valid share of the covered area a target cell needs (0: any valid sample; the 2^-30 slack lets a fully
+ * covered, fully valid cell pass at 1).  A target cell outside the source hull is NaN; a partly covered one is the mean over its
+ * covered part.  inf follows IEEE arithmetic.  Longitudes do not wrap.  The result does not depend on the launch geometry or on how
+ * the time axis is cut.  src: float64, or float32 with src_is_f32 != 0 (widened in the kernel: the values are those of the widened
+ * source).  NaN in the bounds, bounds that are not strictly monotonic, a dimension without a cell, ld < ny * nx, ld_out < C,
+ * min_valid outside [0, 1] and a grid too large for 32-bit row, column and table indices are SD_ERR_INVALID.
+ * sd_remap_create builds and uploads the two tables; a sd_remap serves any number of calls. */
+int sd_remap_create(sd_ctx* ctx, int64_t ny, int64_t nx, const double* src_yb, const double* src_xb, int64_t Ny, int64_t Nx,
+                    const double* dst_yb, const double* dst_xb, sd_remap** out);
+int sd_remap_destroy(sd_remap* rm);
+int sd_remap_info(const sd_remap* rm, int64_t* ny, int64_t* nx, int64_t* Ny, int64_t* Nx, int64_t* y_entries, int64_t* x_entries);
+int sd_remap_apply_dev(sd_ctx* ctx, const sd_remap* rm, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, double min_valid,
+                       double* out_dev, int64_t ld_out);
+/* host buffers: src [T, ny, nx], out [T, Ny * Nx]; upload, run, download */
+int sd_remap_apply(sd_ctx* ctx, const sd_remap* rm, const void* src_host, int src_is_f32, int64_t T, double min_valid, double* out_host);
 
 /* ---- resampling of the time axis: GridArray.resample(time=rule).mean() / .sum() -----------------------------
  * A [T, C] field (cells fastest, rows ld >= C elements apart) is reduced over runs of consecutive rows into an [M, C] float64 field

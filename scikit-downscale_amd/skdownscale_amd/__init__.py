@@ -10,6 +10,7 @@ from .gard import AnalogGridModel, AnalogRegression, PureAnalog, PureRegression,
 from .groupers import DAY_GROUPER, MONTH_GROUPER, PaddedDOYGrouper
 from .grouping import GroupedGridModel, GroupedRegressor
 from .regrid import InterpolatedGridArray, Regridder
+from .remap import ConservativeRemapper, RemappedGridArray, cell_bounds
 from .resample import GridResample, ResampledGridArray, time_bins
 from .disagg import DisaggregatedGridArray, time_map
 from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, group_labels
@@ -51,6 +52,9 @@ __all__ = [
     "arrm_breakpoints",
     "Regridder",
     "InterpolatedGridArray",
+    "ConservativeRemapper",
+    "RemappedGridArray",
+    "cell_bounds",
     "ResampledGridArray",
     "GridResample",
     "time_bins",

@@ -133,6 +133,11 @@ SIGNATURES = {
     "sd_regrid_info": [_p, C.POINTER(_int), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "sd_regrid_apply_dev": [_p, _p, _p, _int, _i64, _p, _i64],
     "sd_regrid_apply": [_p, _p, _p, _int, _i64, _p],
+    "sd_remap_create": [_p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, C.POINTER(_p)],
+    "sd_remap_destroy": [_p],
+    "sd_remap_info": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "sd_remap_apply_dev": [_p, _p, _p, _int, _i64, _i64, _dbl, _p, _i64],
+    "sd_remap_apply": [_p, _p, _p, _int, _i64, _dbl, _p],
     "sd_resample_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64],
     "sd_resample": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p],
     "sd_disagg_dev": [_p, _int, _p, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _i64],

@@ -119,6 +119,27 @@ class GridArray:
         interp_dims(self, target)
         return InterpolatedGridArray(self, target, method)
 
+    def remap_like(self, other, weights="area", latitude="auto", min_valid=0.5, src_bounds=None, dst_bounds=None, scratch_bytes=None):
+        """First-order conservative (area-overlap) remapping onto the coarser grid of ``other`` over exactly the two spatial dims both
+        arrays name: the aggregation of fine observations to a GCM's grid (step 1 of BCSD, Wood et al. 2004), where ``interp_like``
+        would sample a few nodes and alias.  Every target cell is the overlap-weighted mean of the non-NaN source cells it covers,
+        NaN where they carry less than ``min_valid`` of the covered weight (0: any valid sample suffices) or where the cell lies
+        outside the source; a partly covered cell is the mean over its covered part.  ``weights='area'`` measures the latitude dim
+        (``latitude='auto'``: the one named ``lat`` / ``latitude``; or a dim name, or None) in sin(lat), ``'plain'`` uses coordinate
+        units on both dims.  Cell bounds are the midpoints between centres, the ends extrapolated by half a spacing, unless
+        ``src_bounds`` / ``dst_bounds`` ``{dim: n + 1 bounds}`` give them.  Longitudes do not wrap.  ``time`` and ``variable`` pass
+        through.  ``scratch_bytes``: device scratch of one block of fine time steps (default 1 GiB); float32 goes up as float32.
+        -> a lazy ``RemappedGridArray`` (float64)."""
+        from .regrid import interp_dims
+        from .remap import RemappedGridArray
+
+        dims = interp_dims(self, other.dims)
+        missing = [d for d in dims if d not in other.coords]
+        if missing:
+            raise ValueError(f"`other` has no coordinate for dim {missing[0]!r}")
+        return RemappedGridArray(self, {d: other.coords[d] for d in dims}, weights, latitude, min_valid, src_bounds, dst_bounds,
+                                 scratch_bytes=scratch_bytes)
+
     def resample(self, indexer=None, scratch_bytes=None, **kwargs):
         """``resample(time='MS').mean()`` / ``.sum()``: pandas' ``DataFrame.resample(rule, **kw)`` bins of the dim's coordinate, reduced
         per cell on the GPU (``xarray``'s ``da.resample(time=rule)`` for these two reductions).  Exactly one dim is named, as a keyword

@@ -293,6 +293,61 @@ class RegridState(_State):
         return src, int(src.dtype == np.float32)
 
 
+class RemapState(_State):
+    """Separable area-overlap tables of one (source grid, target grid) on the device (sd_remap_create)."""
+
+    def info(self):
+        v = [C.c_int64() for _ in range(6)]
+        check(self.ctx.lib.sd_remap_info(self.vptr, *[C.byref(x) for x in v]))
+        return dict(zip(("ny", "nx", "Ny", "Nx", "y_entries", "x_entries"), (x.value for x in v)))
+
+    def apply(self, field, min_valid=0.5, out=None):
+        """field: a float32 / float64 host array [T, ny, nx] or [T, ny * nx] (any other dtype is taken as float64) or a DeviceArray
+        [T, ny * nx] (rows ``ld`` apart) -> [T, Ny * Nx] float64 DeviceArray, cells fastest (``out``: a [T, C] DeviceArray, possibly a
+        view of a wider or longer one).  float32 goes to the device as float32 and is widened in the kernel."""
+        i = self.info()
+        field, f32, min_valid = self._args(field, i, min_valid)
+        T = field.shape[0]
+        mine = None
+        if not isinstance(field, DeviceArray):
+            field = mine = self.ctx.to_device(field, field.dtype)
+        try:
+            out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
+            for name, a in (("field", field), ("out", out)):
+                if a.ctx is not self.ctx:
+                    raise ValueError(f"sd_downscale: sd_remap: `{name}` belongs to another context")
+            check(self.ctx.lib.sd_remap_apply_dev(self.ctx.handle, self.vptr, field.vptr, f32, field.ld, T, min_valid, out.vptr, out.ld))
+        finally:
+            if mine is not None:
+                mine.free()
+        return out
+
+    def apply_host(self, field, min_valid=0.5):
+        """host [T, ny, nx] -> host [T, Ny * Nx] through sd_remap_apply (upload, run, download in one call)"""
+        i = self.info()
+        if isinstance(field, DeviceArray):
+            raise ValueError("apply_host: expected a host array")
+        field, f32, min_valid = self._args(field, i, min_valid)
+        out = np.empty((field.shape[0], i["Ny"] * i["Nx"]))
+        check(self.ctx.lib.sd_remap_apply(self.ctx.handle, self.vptr, ptr(field), f32, field.shape[0], min_valid, ptr(out)))
+        return out
+
+    @staticmethod
+    def _args(field, i, min_valid):
+        cells = i["ny"] * i["nx"]
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+            if field.ndim == 3 and field.shape[1:] == (i["ny"], i["nx"]):
+                field = field.reshape(field.shape[0], cells)
+        if len(field.shape) != 2 or field.shape[1] != cells or field.shape[0] < 1 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, {i['ny']}, {i['nx']}] or [T, {cells}] field, got shape "
+                             f"{tuple(field.shape)} of {field.dtype}")
+        min_valid = float(min_valid)
+        if not 0.0 <= min_valid <= 1.0:
+            raise ValueError(f"min_valid={min_valid!r}: expected a share of the covered area in [0, 1]")
+        return field, int(field.dtype == np.float32), min_valid
+
+
 class Context:
     """One GPU + one HIP stream.  Calls on a context are serialised."""
 
@@ -954,6 +1009,30 @@ class Context:
         check(self.lib.sd_regrid_create(self.handle, _lib.REGRID_METHODS[method], len(sy), len(sx), ptr(sy), ptr(sx), len(dy), len(dx),
                                         ptr(dy), ptr(dx), C.byref(h)))
         return RegridState(self, h.value, self.lib.sd_regrid_destroy)
+
+    # ---- conservative remapping (GridArray.remap_like) ----
+    def remap_create(self, src_yb, src_xb, dst_yb, dst_xb):
+        """Area-overlap tables that take a [T, len(src_yb) - 1, len(src_xb) - 1] field onto the grid whose cell bounds are
+        (dst_yb, dst_xb); every bounds array is strictly ascending or descending, in the units whose differences are the weights
+        -> RemapState"""
+        b = {}
+        for name, a in (("src_yb", src_yb), ("src_xb", src_xb), ("dst_yb", dst_yb), ("dst_xb", dst_xb)):
+            a = np.asarray(a)
+            if a.ndim != 1 or len(a) < 2:
+                raise ValueError(f"{name}: expected the n + 1 bounds of n >= 1 cells, got shape {a.shape}")
+            b[name] = _lib.as_f64(a)
+        h = C.c_void_p()
+        check(self.lib.sd_remap_create(self.handle, len(b["src_yb"]) - 1, len(b["src_xb"]) - 1, ptr(b["src_yb"]), ptr(b["src_xb"]),
+                                       len(b["dst_yb"]) - 1, len(b["dst_xb"]) - 1, ptr(b["dst_yb"]), ptr(b["dst_xb"]), C.byref(h)))
+        return RemapState(self, h.value, self.lib.sd_remap_destroy)
+
+    def remap_host(self, field, src_yb, src_xb, dst_yb, dst_xb, min_valid=0.5):
+        """host [T, ny, nx] -> host [T, Ny * Nx]: tables, upload, run, download (sd_remap_create + sd_remap_apply)"""
+        state = self.remap_create(src_yb, src_xb, dst_yb, dst_xb)
+        try:
+            return state.apply_host(field, min_valid)
+        finally:
+            state.close()
 
     # ---- resampling of the time axis (GridArray.resample) ----
     @staticmethod

@@ -82,7 +82,8 @@ def _walk_source(source, dim, ctx, scratch_bytes, visit, halo=None, also_lazy=()
     """``visit(r0, r1, block)`` for consecutive blocks of time steps of ``source``: ``block`` is the [r1 - r0, C] DeviceArray of the rows
     r0 .. r1 - 1 (C = cells of the other dims in their order, the last fastest), valid during the visit.  A lazy ``ResampledGridArray``
     or ``RolledGridArray`` (and those of ``also_lazy``) is one block, computed in HBM; an unchunked ``coarse.interp_like(obs)`` is
-    regridded, and any other array uploaded, in blocks of at most ``scratch_bytes`` of device scratch.
+    regridded, an unchunked ``fine.remap_like(coarse)`` over a host array uploaded and remapped, and any other array uploaded, in blocks
+    of at most ``scratch_bytes`` of device scratch.
 
     With ``halo = (before, after)`` a block also holds up to ``before`` rows in front of r0 and ``after`` rows behind r1 - 1, clipped to
     the array: ``visit(r0, r1, block, b0)`` with ``block`` the rows b0 .. of the source, through r1 - 1 + after."""

@@ -67,10 +67,16 @@ def _bin_blocks(offsets, max_rows):
 def resident_source(src, dim):
     """``src`` when it is an unchunked ``coarse.interp_like(obs)`` with dims (dim, y, x): its fine field can be produced in HBM, block
     of rows by block of rows (``src._regridder_on(ctx).regrid(src._coarse_stack()[r0:r1], out=block)``); else None.  The rule of every
-    lazy array that walks the time axis of a source (``ResampledGridArray``, the groupby arrays)."""
+    lazy array that walks the time axis of a source (``ResampledGridArray``, the groupby arrays).  Likewise ``src`` when it is a not
+    yet computed ``fine.remap_like(coarse)`` with those dims over a host array: a block of fine rows is uploaded and remapped into
+    the block."""
     from .regrid import InterpolatedGridArray
+    from .remap import RemappedGridArray
 
-    if not isinstance(src, InterpolatedGridArray) or len(src.dims) != 3 or src.dims[0] != dim or src._lead_dims() != src.dims[:1]:
+    if isinstance(src, RemappedGridArray) and (src.computed or not src._host_source()):
+        return None
+    if (not isinstance(src, (InterpolatedGridArray, RemappedGridArray)) or len(src.dims) != 3 or src.dims[0] != dim
+            or src._lead_dims() != src.dims[:1]):
         return None
     if src.chunksizes is not None and any(len(src.chunksizes[d]) > 1 for d in src.dims[1:]):
         return None

@@ -397,9 +397,70 @@ def bench_rolling(ctx, args):
     return res
 
 
+def bench_remap(ctx, args):
+    """remap_kernel alone (ctx.prof(): an event pair around the launch): 14 600 daily steps of a 250 x 400 fine field onto 16 x 25
+    coarse cells by area overlap (latitude in sin(lat); 250 / 16 is not an integer, so target rows share source rows), float64 and
+    float32 sources, beside sd_memcpy_d2d of the same source bytes and beside resample_kernel ('MS', mean) on the same field in the
+    same run.  GB/s by algorithmic bytes (the source read once + 8 * T * Ny * Nx written); the first two and the last time step
+    compared bit for bit with the oracle.  -> one result per source type"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _remap_oracle as mo
+    from skdownscale_amd.resample import time_bins
+
+    T, (ny, nx), (Ny, Nx) = args.times, (250, 400), (16, 25)
+    C = ny * nx
+    index = synth.daily_calendar(T)
+    _, offsets = time_bins(index, "MS")
+    tab = synth.tas_tables(index)["y_obs"]
+    d64 = ctx.synth_fill(ctx.empty((T, C)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+    syb, sxb = np.sin(np.deg2rad(np.linspace(30.0, 50.0, ny + 1))), np.linspace(-120.0, -100.0, nx + 1)
+    dyb, dxb = np.sin(np.deg2rad(np.linspace(30.0, 50.0, Ny + 1))), np.linspace(-120.0, -100.0, Nx + 1)
+    state = ctx.remap_create(syb, sxb, dyb, dxb)
+    spare, monthly, out = ctx.empty((T, C)), ctx.empty((len(offsets) - 1, C)), ctx.empty((T, Ny * Nx))
+    repeats = max(args.steps, 5)
+    picks = [0, 1, T - 1]
+
+    def timed(kernel, call):
+        call()
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            times.append(ctx.prof()[kernel]["ms"])
+        ctx.prof_enable(False)
+        return float(np.median(times)), [min(times), max(times)]
+
+    results = []
+    for name, dtype in (("f64", np.float64), ("f32", np.float32)):
+        if dtype == np.float32:
+            d = ctx.empty((T, C), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, d64.vptr, T * C, d.vptr))
+            ctx.synchronize()
+        else:
+            d = d64
+        src_bytes = T * C * np.dtype(dtype).itemsize
+        copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+        rs_ms, rs_min_max = timed("resample_kernel", lambda: ctx.resample(d, offsets, "mean", out=monthly))
+        ms, min_max = timed("remap_kernel", lambda: state.apply(d, 0.5, out=out))
+        host = np.stack([d.rows(t, t + 1).to_host()[0] for t in picks]).reshape(len(picks), ny, nx)
+        got = np.stack([out.rows(t, t + 1).to_host()[0] for t in picks])
+        same = bool(np.array_equal(got, mo.remap(host, syb, sxb, dyb, dxb, 0.5).reshape(len(picks), -1), equal_nan=True))
+        nbytes = src_bytes + 8 * T * Ny * Nx
+        results.append({"workload": f"remap {T} daily steps of {ny}x{nx} -> {Ny}x{Nx} by area overlap, min_valid=0.5, {name} source", "repeats": repeats,
+                        "source": name, "kernel_ms": ms, "kernel_ms_min_max": min_max, "algorithmic_bytes": nbytes, "read_GBps": src_bytes / ms / 1e6,
+                        "GBps": nbytes / ms / 1e6, "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_steps_0_1_last": same,
+                        "device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6},
+                        "resample_kernel_MS_mean": {"kernel_ms": rs_ms, "kernel_ms_min_max": rs_min_max, "read_GBps": src_bytes / rs_ms / 1e6},
+                        "read_rate_over_copy": copy_ms / ms, "read_rate_over_resample": rs_ms / ms})
+        if d is not d64:
+            d.free()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -410,6 +471,14 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
+    if args.workload == "remap":  # one JSON line per source type
+        for res in bench_remap(ctx, args):
+            line = json.dumps(res)
+            print(line)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
+        return
     if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
                            "groupby": bench_groupby, "rolling": bench_rolling}[args.workload](ctx, args))
