@@ -8,6 +8,8 @@
 //   straight  REP back-to-back copies of the sort (REP x 11 KB of straight-line code: what the 50 KB fused kernel looks like to
 //             the instruction cache, which two CUs share)
 // Prints ns per sort per SIMD (= per-SIMD throughput) and ns per sort per wave (= latency a wave sees).
+// A/B of the issue order of the merge levels 4 .. 6 (sd_wsort.h): build once plain (half-batches), once with -DSD_WSORT_SERIAL (stage by
+// stage) and once with -DSD_WSORT_PREFETCH; profiles/wsort_pipe/microbench_wsort_occ.log.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>

@@ -1,5 +1,6 @@
 // Correctness + throughput check of the register wave sort (csrc/sd_wsort.h) on random keys.
 //   hipcc -O3 --offload-arch=gfx950 csrc/microbench/wsort_test.hip -o /tmp/wsort_test && /tmp/wsort_test
+// (-DSD_WSORT_SERIAL / -DSD_WSORT_PREFETCH: the other issue orders of the merge levels 4 .. 6, see sd_wsort.h)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

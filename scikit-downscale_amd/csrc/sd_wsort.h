@@ -17,10 +17,24 @@
 //   * the local merger sorts cyclic-bitonic sequences: even lengths are half-cleaned and split; the odd lengths 3 and 5
 //     (K = 12, 24; K = 20) end in 3-sorters (v_min3 / v_med3 / v_max3_u32), other odd lengths in a full sorter.
 //
+//   * schedule of the levels 4..6, whose stages lane ^ 4, 16, 31, 63 go through the LDS pipe (a round trip of a hundred cycles and
+//     more against none for a DPP move): in the stages after the first every key register is a dependency chain of its own, so a
+//     level runs as two half-batches of K/2 keys (LevelSched below).  One half issues its ds_swizzle requests and the other half
+//     then runs its own DPP moves and v_med3 until it has requests of its own in flight; only then are the first half's results
+//     consumed, behind one counted s_waitcnt lgkmcnt per half-batch.  The comparators and their order per register are those of
+//     the stage-by-stage form, so the result is bit-identical; -DSD_WSORT_SERIAL keeps that form for A/B runs
+//     (microbench/wsort_occ.hip, wsort_test.hip), and K = 24 always uses it (registers).  Not the default, -DSD_WSORT_PREFETCH: the
+//     first stage of the levels 5 and 6 reads registers the local merger of the level before has finished sub-block by sub-block
+//     (K = 20: 5|5|5|5), so its requests can go out under the merging of the other sub-blocks -- at K more live registers, which
+//     bcsd_fd_kernel does not have.  tests/wsort_sched_check.cpp runs a host model of the op lists; profiles/wsort_pipe/ has
+//     the measurements (-3.6 % per sort with two resident waves per SIMD, -0.8 % on the BCSD headline).
+//
 // K = 20: 202 + 6 * 80 + 21 * 20 * 2 = ~1 520 32-bit instructions per 1 280 keys, against ~2 800 mostly double-rate instructions and 410 LDS instructions of the f64 merge sort of
 // sd_wave.h.  tools/dev/nets.py checks the networks (0-1 principle), tools/dev/sim_wave_bitonic.py the lane scheme.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <utility>
 
 namespace sdws {
 
@@ -102,6 +116,139 @@ struct BitonicNet {
                 batcher_into(c, len, base);
             }
         }
+    }
+};
+
+
+// ---- issue order of one merge level (levels 4 .. 6), as a list of operations on the key registers k[0..K) and the partner
+// temporaries t[0..2K): the kernels execute the list as straight-line code, the host check (tests/wsort_sched_check.cpp) runs it
+// on a model of the 64 lanes.
+//   kOpFetch      t[b] = k[a] of lane ^ c
+//   kOpFetchNext  the same for the first stage of the NEXT level; executed only when that level runs
+//   kOpMed        k[a] = med3(k[a], t[b], lanes with bit c set keep the maximum)
+//   kOpNet        operation a of BitonicNet<K>
+//   kOpFence      the instruction scheduler moves nothing across
+//   kOpWait       s_waitcnt lgkmcnt(a): at most a requests to the LDS pipe still out
+constexpr unsigned char kOpFetch = 0, kOpFetchNext = 1, kOpMed = 2, kOpNet = 3, kOpFence = 4, kOpWait = 5;
+constexpr int kMaxLgkm = 15;  // the counter has four bits
+struct SchedOp {
+    unsigned char kind, a, b, c;
+};
+constexpr int kMaxSched = 768;
+// partners fetched through the LDS pipe (ds_swizzle / ds_bpermute) instead of a DPP move
+constexpr bool via_lds(int x) { return x == 4 || x == 16 || x == 31 || x == 63; }
+
+// A/B: -DSD_WSORT_PREFETCH chains the levels 4 -> 5 -> 6 through PRE / NEXT below.  Not the default: up to K more temporaries are
+// live across a merger, and bcsd_fd_kernel<20> then spills (128 VGPRs, 14 to scratch).
+#ifdef SD_WSORT_PREFETCH
+constexpr bool kPrefetch = true;
+#else
+constexpr bool kPrefetch = false;
+#endif
+
+// Level L (runs of M = 2^(L-1) lanes).  Stage 0 pairs element i with element K-1-i of lane ^ (2M-1) and writes its partners to
+// t[K + i]; the stages h = M/2 .. 1 pair element i with element i of lane ^ h through t[i].
+//   PRE   the fetches of stage 0 were issued by the level before (its NEXT)
+//   NEXT  issue the fetches of the next level's stage 0 inside the local merger, each register once no later operation of the
+//         merger touches it
+// The halves A = [0, K/2) and B = [K/2, K) each walk stage by stage; a half that has just issued fetches through the LDS pipe
+// hands over to the other one, which runs until it has issued such fetches itself (or is done).  Every med3 of stage 0 comes after
+// all fetches of stage 0: it overwrites a register the partner lane reads.
+template <int K, int L, bool PRE, bool NEXT>
+struct LevelSched {
+    int n = 0;
+    SchedOp op[kMaxSched] = {};
+    constexpr void put(unsigned char kind, int a, int b, int c) {
+        op[n].kind = kind;
+        op[n].a = (unsigned char)a;
+        op[n].b = (unsigned char)b;
+        op[n].c = (unsigned char)c;
+        ++n;
+    }
+    constexpr void fence() {
+        if (n > 0 && op[n - 1].kind != kOpFence) put(kOpFence, 0, 0, 0);
+    }
+    BitonicNet<K> net{};
+    // the merger's last operation on register r
+    constexpr int last_use(int r) const {
+        int last = -1;
+        for (int c = 0; c < net.c.n; ++c)
+            if (net.c.a[c] == r || net.c.b[c] == r || (net.c.c[c] != kNone && net.c.c[c] == r)) last = c;
+        return last;
+    }
+    constexpr LevelSched() {
+        constexpr int M = 1 << (L - 1), H = K / 2;
+        int xs[6] = {}, bits[6] = {}, S = 0;
+        xs[S] = 2 * M - 1;
+        bits[S] = L - 1;
+        ++S;
+        for (int h = 16, b = 4; h >= 1; h >>= 1, --b)
+            if (M >= 2 * h) {
+                xs[S] = h;
+                bits[S] = b;
+                ++S;
+            }
+        // sequence numbers of the requests to the LDS pipe, which answers in order: a group of med3 that reads answers up to
+        // number q waits for lgkmcnt(issued - 1 - q) once, and the compiler's own per-use waits behind it fall away
+        int seq[2 * K] = {}, issued = 0;
+        for (int i = 0; i < 2 * K; ++i) seq[i] = -1;
+        // the half that goes first consumes the other half's registers: after a prefetch those of A (final first in the merger)
+        int h = PRE ? 1 : 0;
+        if (PRE) {
+            for (int c = 0; c < net.c.n; ++c)
+                for (int r = 0; r < K; ++r)
+                    if (last_use(r) == c) seq[K + r] = issued++;
+        } else {
+            for (int j = 0; j < K; ++j) {
+                const int i = (j + H) % K;  // B's registers first: A consumes them
+                put(kOpFetch, i, K + i, xs[0]);
+                if (via_lds(xs[0])) seq[K + i] = issued++;
+            }
+        }
+        int st[2] = {0, 0};  // per half: the stage whose fetches are issued and whose med3 are due
+        while (st[0] < S || st[1] < S) {
+            if (st[h] >= S) {
+                h = 1 - h;
+                continue;
+            }
+            const int lo = h ? H : 0, hi = h ? K : H, s = st[h];
+            if (via_lds(xs[s])) {
+                int q = -1;
+                for (int i = lo; i < hi; ++i) q = seq[s == 0 ? K + (K - 1 - i) : i] > q ? seq[s == 0 ? K + (K - 1 - i) : i] : q;
+                fence();
+                if (issued - 1 - q <= kMaxLgkm) {
+                    put(kOpWait, issued - 1 - q, 0, 0);
+                    fence();  // or the med3 below are scheduled in front of the wait and get waits of their own
+                }
+            }
+            for (int i = lo; i < hi; ++i) put(kOpMed, i, s == 0 ? K + (K - 1 - i) : i, bits[s]);
+            ++st[h];
+            if (st[h] < S) {
+                const int x = xs[st[h]];
+                if (via_lds(x)) fence();
+                for (int i = lo; i < hi; ++i) {
+                    put(kOpFetch, i, i, x);
+                    if (via_lds(x)) seq[i] = issued++;
+                }
+                if (via_lds(x)) {
+                    fence();
+                    h = 1 - h;
+                }
+            }
+        }
+        fence();
+        for (int c = 0; c < net.c.n; ++c) {
+            put(kOpNet, c, 0, 0);
+            if (!NEXT) continue;
+            bool any = false;
+            for (int r = 0; r < K; ++r)
+                if (last_use(r) == c) {
+                    put(kOpFetchNext, r, K + r, 4 * M - 1);
+                    any = true;
+                }
+            if (any) fence();
+        }
+        fence();
     }
 };
 
@@ -202,6 +349,60 @@ __device__ __forceinline__ void cross_stage(unsigned (&k)[K], int lane, int addr
     for (int i = 0; i < K; ++i) k[i] = med3(k[i], t[REV ? K - 1 - i : i], sel);
 }
 
+// One level in the issue order of LevelSched.  t: the partner temporaries, kept by the caller because a level's NEXT fetches are
+// consumed by the level after it; `next` (wave-uniform): that level runs.  The compiler places the s_waitcnt lgkmcnt itself (the
+// LDS pipe returns in order, so they are counted); the fences keep the requests and their consumers where the list puts them.
+template <int K, int L, bool PRE, bool NEXT>
+struct LevelTables {
+    static constexpr LevelSched<K, L, PRE, NEXT> s{};
+    static constexpr BitonicNet<K> bnet{};
+};
+
+template <int K, int L, bool PRE, bool NEXT, int O>
+__device__ __forceinline__ void sched_step(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next) {
+    using T = LevelTables<K, L, PRE, NEXT>;
+    constexpr int kind = T::s.op[O].kind, a = T::s.op[O].a, b = T::s.op[O].b, c = T::s.op[O].c;
+    if constexpr (kind == kOpFetch) {
+        t[b] = lane_xor<c>(k[a], addr63);
+    } else if constexpr (kind == kOpFetchNext) {
+        if (next) t[b] = lane_xor<c>(k[a], addr63);
+    } else if constexpr (kind == kOpMed) {
+        k[a] = med3(k[a], t[b], (unsigned)(-((lane >> c) & 1)));
+    } else if constexpr (kind == kOpNet) {
+        constexpr int ra = T::bnet.c.a[a], rb = T::bnet.c.b[a], rc = T::bnet.c.c[a];
+        if constexpr (rc == kNone) {
+            const unsigned lo = umin(k[ra], k[rb]);
+            const unsigned hi = umax(k[ra], k[rb]);
+            k[ra] = lo;
+            k[rb] = hi;
+        } else {
+            // see apply_net
+            const unsigned x = k[ra], y = k[rb], z = k[rc];
+            unsigned lo, mid, hi;
+            asm("v_min3_u32 %0, %3, %4, %5\n\tv_med3_u32 %1, %3, %4, %5\n\tv_max3_u32 %2, %3, %4, %5"
+                : "=&v"(lo), "=&v"(mid), "=&v"(hi)
+                : "v"(x), "v"(y), "v"(z));
+            k[ra] = lo;
+            k[rb] = mid;
+            k[rc] = hi;
+        }
+    } else if constexpr (kind == kOpWait) {
+        __builtin_amdgcn_s_waitcnt(0xC07F | (a << 8));  // lgkmcnt(a); vmcnt and expcnt at their maxima: no wait
+    } else {
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int K, int L, bool PRE, bool NEXT, int... O>
+__device__ __forceinline__ void sched_steps(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next, std::integer_sequence<int, O...>) {
+    (sched_step<K, L, PRE, NEXT, O>(k, t, lane, addr63, next), ...);
+}
+
+template <int K, int L, bool PRE, bool NEXT>
+__device__ __forceinline__ void merge_level_piped(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next) {
+    sched_steps<K, L, PRE, NEXT>(k, t, lane, addr63, next, std::make_integer_sequence<int, LevelTables<K, L, PRE, NEXT>::s.n>{});
+}
+
 template <int K, int L>
 __device__ __forceinline__ void merge_level(unsigned (&k)[K], int lane, int addr63) {
     constexpr int M = 1 << (L - 1);
@@ -226,9 +427,30 @@ __device__ __forceinline__ void wave_sort(unsigned (&k)[K], int lane, int lanes_
     if (lanes_used > 1) merge_level<K, 1>(k, lane, addr63);
     if (lanes_used > 2) merge_level<K, 2>(k, lane, addr63);
     if (lanes_used > 4) merge_level<K, 3>(k, lane, addr63);
+#ifndef SD_WSORT_SERIAL
+    // the levels with stages on the LDS pipe, in the issue order of LevelSched.  No "s_nop 1" between them: the stage behind a
+    // merger reads through the LDS pipe there; the one fence at the end is for a DPP read by the caller.  K = 24 stays stage by
+    // stage: bcsd_fx_kernel<24>, which spills already, spills more with the fences in its way.
+    if constexpr (K > 20) {
+        if (lanes_used > 8) merge_level<K, 4>(k, lane, addr63);
+        if (lanes_used > 16) merge_level<K, 5>(k, lane, addr63);
+        if (lanes_used > 32) merge_level<K, 6>(k, lane, addr63);
+    } else if (lanes_used > 8) {
+        unsigned t[2 * K];
+        const bool l5 = lanes_used > 16, l6 = lanes_used > 32;
+        merge_level_piped<K, 4, false, kPrefetch>(k, t, lane, addr63, l5);
+        if (l5) {
+            merge_level_piped<K, 5, kPrefetch, kPrefetch>(k, t, lane, addr63, l6);
+            if (l6) merge_level_piped<K, 6, kPrefetch, false>(k, t, lane, addr63, false);
+        }
+        dpp_fence<K>(k);
+    }
+#else
+    // A/B: stage by stage over all K keys
     if (lanes_used > 8) merge_level<K, 4>(k, lane, addr63);
     if (lanes_used > 16) merge_level<K, 5>(k, lane, addr63);
     if (lanes_used > 32) merge_level<K, 6>(k, lane, addr63);
+#endif
 }
 #endif  // __HIPCC__
 
