@@ -120,6 +120,14 @@ extern "C" {
 #define SD_ROLLING_VAR 2   /* sum of squared deviations from the window's mean / (n - ddof); NaN where n - ddof <= 0 */
 #define SD_ROLLING_STD 3   /* sqrt of SD_ROLLING_VAR */
 
+/* sd_quantile: NumPy's estimation methods of np.nanquantile (h = (n - 1) * q over the n sorted non-NaN samples v) */
+#define SD_QUANTILE_LINEAR 0    /* v[floor(h)] and its successor interpolated at h - floor(h) (NumPy's _lerp) */
+#define SD_QUANTILE_LOWER 1     /* v[floor(h)] */
+#define SD_QUANTILE_HIGHER 2    /* v[ceil(h)] */
+#define SD_QUANTILE_NEAREST 3   /* v[rint(h)], half to even */
+#define SD_QUANTILE_MIDPOINT 4  /* v[h] where h is whole, else the interpolation at 0.5 */
+#define SD_QUANTILE_MEDIAN 5    /* np.nanmedian: the middle sample, or (v[n/2 - 1] + v[n/2]) / 2; q and Q are not read, Q counts as 1 */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -541,6 +549,32 @@ int sd_rolling_dev(sd_ctx* ctx, int op, const void* src_dev, int src_is_f32, int
 /* host buffers: src [T, C], out [T, C]; the whole field in one call: upload, run, download */
 int sd_rolling(sd_ctx* ctx, int op, const void* src_host, int src_is_f32, int64_t T, int64_t C, int64_t window, int64_t back,
                int64_t min_periods, int64_t ddof, int wrap, double* out_host);
+
+/* ---- order statistics over the time axis: GridArray.quantile / .median (np.nanquantile / np.nanmedian per cell and group) --------
+ * src is a [T, C] field (cells fastest, rows ld >= C elements apart; float64, or float32 with src_is_f32 != 0, widened per sample:
+ * exact, so the result is that of the widened field).  group: host int32 [T] with every id in [0, G), or NULL: one group (G is then
+ * not read and counts as 1).  q: host double [Q], every entry in [0, 1].  out [Q * G, C] float64 (rows ld_out >= C apart): row
+ * q * G + g is quantile q of group g.
+ *
+ * Per (group, cell): v = the samples without NaN, ascending, n of them.  n == 0 gives NaN; with skipna == 0 any NaN in the group gives
+ * NaN.  Otherwise h = (double)(n - 1) * q, lo = floor(h), g = h - lo, hi = min(lo + 1, n - 1), a = v[lo], b = v[hi], d = b - a and
+ * SD_QUANTILE_LINEAR g >= 0.5 ? b - d * (1 - g) : a + d * g; LOWER v[lo]; HIGHER v[ceil(h)]; NEAREST v[rint(h)] (half to even);
+ * MIDPOINT v[lo] where h is whole, else b - d * 0.5; MEDIAN v[n / 2] for odd n, (v[n / 2 - 1] + v[n / 2]) / 2 for even n.  These
+ * are the operations of NumPy 2's np.nanquantile(method=...) / np.nanmedian / np.quantile, one IEEE operation each: the result
+ * equals NumPy's bit for bit for finite samples and depends neither on the order of a group's rows, nor on the layout, nor on the
+ * launch geometry.  +-inf samples are ordinary values of the sort; the interpolation then follows IEEE arithmetic (inf - inf is NaN,
+ * as in NumPy).  A group id that never occurs gives NaN.
+ *
+ * Groups of up to 1 344 rows are sorted one wave per (group, cell) on chip; longer ones, up to 19 456 rows, go through sorted runs in
+ * 8 * C * (sum of the groups' lengths, each rounded up to whole runs) bytes of device scratch (SD_ERR_NOMEM where that fails);
+ * beyond that the call is SD_ERR_UNSUPPORTED.  An unknown method, sizes <= 0, G <= 0, Q <= 0, a q outside [0, 1] (NaN included:
+ * "Quantiles must be in the range [0, 1]"), a leading dimension below C, a group id outside [0, G), a call too large for the grid,
+ * ld >= 2^29 and T >= 2^31 are SD_ERR_INVALID, refused before anything is allocated or launched. */
+int sd_quantile_dev(sd_ctx* ctx, int method, int skipna, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C,
+                    const int32_t* group_or_null, int64_t G, const double* q, int64_t Q, double* out_dev, int64_t ld_out);
+/* host buffers: src [T, C], out [Q * G, C]; upload, run, download */
+int sd_quantile(sd_ctx* ctx, int method, int skipna, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int32_t* group_or_null,
+                int64_t G, const double* q, int64_t Q, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

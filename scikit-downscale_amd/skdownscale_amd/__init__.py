@@ -15,6 +15,7 @@ from .resample import GridResample, ResampledGridArray, time_bins
 from .disagg import DisaggregatedGridArray, time_map
 from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, group_labels
 from .rolling import GridRolling, RolledGridArray
+from .order_stats import TimeQuantileGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -66,5 +67,6 @@ __all__ = [
     "group_labels",
     "GridRolling",
     "RolledGridArray",
+    "TimeQuantileGridArray",
 ]
 __version__ = "0.1.0"

@@ -29,6 +29,7 @@ DISAGG_OPS = {"shift": 0, "scale_mean": 1, "scale_sum": 2}  # SD_DISAGG_*
 GROUPBY_REDUCE_OPS = {"mean": 0, "sum": 1}  # SD_GROUPBY_MEAN / _SUM
 GROUPBY_APPLY_OPS = {"sub": 0, "add": 1, "mul": 2, "div": 3}  # SD_GROUPBY_SUB .. _DIV
 ROLLING_OPS = {"mean": 0, "sum": 1, "var": 2, "std": 3}  # SD_ROLLING_*
+QUANTILE_METHODS = {"linear": 0, "lower": 1, "higher": 2, "nearest": 3, "midpoint": 4, "median": 5}  # SD_QUANTILE_*
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -148,6 +149,8 @@ SIGNATURES = {
     "sd_groupby_apply": [_p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _p],
     "sd_rolling_dev": [_p, _int, _p, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _i64, _p, _i64],
     "sd_rolling": [_p, _int, _p, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p],
+    "sd_quantile_dev": [_p, _int, _int, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64],
+    "sd_quantile": [_p, _int, _int, _p, _int, _i64, _i64, _p, _i64, _p, _i64, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

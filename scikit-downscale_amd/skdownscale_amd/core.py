@@ -189,6 +189,31 @@ class GridArray:
         (d, w), = named.items()
         return GridRolling(self, d, w, center, min_periods, wrap, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def quantile(self, q, dim="time", by=None, method="linear", skipna=True, name="group", scratch_bytes=None):
+        """``quantile(0.9, "time", by="time.dayofyear")``: NumPy's ``np.nanquantile(x, q, method=...)`` per cell over ``dim`` on the GPU
+        (``skipna=False``: ``np.quantile``, NaN where a NaN is among the samples), bit for bit for finite samples; ``method`` 'linear'
+        | 'lower' | 'higher' | 'nearest' | 'midpoint'; every ``q`` in [0, 1].  ``by``: None for the whole axis, or what ``groupby``
+        takes -- ``"<dim>.<field>"`` (``time.month``, ``time.dayofyear``, ``time.season``: the group dim is named after the field), one
+        label per step or a callable (the group dim is named ``name``); the groups are the sorted unique labels present.  A scalar
+        ``q`` gives the source's dims with ``dim`` dropped, or replaced in place by the group dim; an array ``q`` adds a leading
+        ``"quantile"`` dim (xarray's grouped spelling puts it last: ``transpose`` is there).  The whole [T, C] source is held in HBM
+        (``T * C * itemsize`` bytes; groups of more than 1 344 steps take as much scratch again, more than 19 456 are refused).
+        -> a lazy ``TimeQuantileGridArray`` (float64)."""
+        from .order_stats import TimeQuantileGridArray
+        from .resample import DEFAULT_SCRATCH_BYTES
+
+        return TimeQuantileGridArray(self, dim, q, by, method, skipna, name,
+                                     scratch_bytes=DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
+    def median(self, dim="time", by=None, skipna=True, name="group", scratch_bytes=None):
+        """``np.nanmedian`` per cell over ``dim`` on the GPU (``skipna=False``: ``np.median``), per group with ``by`` as for
+        ``quantile``.  -> a lazy ``TimeQuantileGridArray`` (float64)."""
+        from .order_stats import TimeQuantileGridArray
+        from .resample import DEFAULT_SCRATCH_BYTES
+
+        return TimeQuantileGridArray(self, dim, 0.5, by, "median", skipna, name,
+                                     scratch_bytes=DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
         """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
         daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and

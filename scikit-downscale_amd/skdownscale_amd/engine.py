@@ -1256,6 +1256,65 @@ class Context:
         check(self.lib.sd_groupby_apply(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], ptr(group), G, ptr(table), ptr(out)))
         return out
 
+    # ---- order statistics over the time axis (GridArray.quantile / .median) ----
+    @staticmethod
+    def _quantile_args(field, q, group, G, method):
+        if method not in _lib.QUANTILE_METHODS:
+            raise ValueError(f"quantile method {method!r}: expected one of {', '.join(repr(k) for k in _lib.QUANTILE_METHODS)}")
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        T, Cc = field.shape
+        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
+            raise ValueError(f"sd_downscale: sd_quantile: bad sizes (T={T}, C={Cc})")
+        if group is None:
+            G = 1
+        else:
+            group = np.ascontiguousarray(group, dtype=np.int32)
+            if group.shape != (T,):
+                raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+            G = int(group.max()) + 1 if G is None else int(G)
+        q = np.ascontiguousarray([0.5] if method == "median" else np.atleast_1d(q), dtype=np.float64)
+        if q.ndim != 1 or G < 1 or len(q) < 1:
+            raise ValueError(f"sd_downscale: sd_quantile: bad sizes (G={G}, Q={q.size if q.ndim == 1 else q.shape})")
+        return field, q, group, G, _lib.QUANTILE_METHODS[method], int(field.dtype == np.float32)
+
+    def quantile(self, field, q, group=None, G=None, method="linear", skipna=True, out=None):
+        """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); q: one
+        quantile or [Q] of them in [0, 1]; group: host int32 [T] with every id in [0, G) (``G`` defaults to the largest id + 1), or None
+        for one group -> [Q * G, C] float64 DeviceArray whose row ``q * G + g`` is np.nanquantile(method=...) of group g per cell
+        (``skipna=False``: np.quantile, NaN where the group holds one); method 'linear' | 'lower' | 'higher' | 'nearest' | 'midpoint',
+        or 'median' (np.nanmedian; q is not read, Q = 1).  ``out``: a [Q * G, C] DeviceArray, possibly a view of a wider or longer
+        one.  Groups of more than 19 456 rows are refused (sd_quantile_dev)."""
+        field, q, group, G, code, f32 = self._quantile_args(field, q, group, G, method)
+        T, Cc = field.shape
+        mine = None
+        out = self._result_buffer(out, (len(q) * G, Cc), True)
+        try:
+            if not isinstance(field, DeviceArray):
+                field = mine = self.to_device(field, field.dtype)
+            for name, a in (("field", field), ("out", out)):
+                if a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_quantile: `{name}` belongs to another context")
+            check(self.lib.sd_quantile_dev(self.handle, code, int(bool(skipna)), field.vptr, f32, field.ld, T, Cc, None if group is None else ptr(group),
+                                           G, ptr(q), len(q), out.vptr, out.ld))
+        finally:
+            if mine is not None:
+                mine.free()
+        return out
+
+    def quantile_host(self, field, q, group=None, G=None, method="linear", skipna=True):
+        """host [T, C] -> host [Q * G, C] through sd_quantile (upload, run, download in one call)"""
+        field, q, group, G, code, f32 = self._quantile_args(field, q, group, G, method)
+        if isinstance(field, DeviceArray):
+            raise ValueError("quantile_host: expected a host array")
+        T, Cc = field.shape
+        out = np.empty((len(q) * G, Cc))
+        check(self.lib.sd_quantile(self.handle, code, int(bool(skipna)), ptr(field), f32, T, Cc, None if group is None else ptr(group), G, ptr(q),
+                                   len(q), ptr(out)))
+        return out
+
     # ---- rolling windows over the time axis (GridArray.rolling) ----
     @staticmethod
     def _rolling_args(field, window, op, back, min_periods, ddof):

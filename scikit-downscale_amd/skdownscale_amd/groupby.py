@@ -71,8 +71,11 @@ def _halo_blocks(T, max_rows, halo):
 def _lazy_dim(source, also=()):
     """the dim along which a not yet computed lazy array gives its field as [rows of that dim, cells of the other dims in their order]
     through ``device_field``; None for any other array.  ``also``: classes taken beside ``ResampledGridArray`` / ``RolledGridArray``"""
+    from .order_stats import TimeQuantileGridArray
     from .rolling import RolledGridArray
 
+    if isinstance(source, TimeQuantileGridArray):  # (a [G, C] table where a lazy GroupReducedGridArray is taken)
+        return source._row_dim() if GroupReducedGridArray in also and not source.computed else None
     if not isinstance(source, (ResampledGridArray, RolledGridArray) + tuple(also)) or source.computed:
         return None
     return source._gdim if isinstance(source, GroupReducedGridArray) else source._dim
@@ -343,13 +346,14 @@ class GroupAppliedGridArray(DeferredGridArray):
         return self._group
 
     def _table(self, ctx):
-        """other as a [G', C] float64 DeviceArray in this array's cell order: a lazy reduction in that order, or a lazy rolling
-        statistic of one, is computed in HBM, any other array goes up once"""
+        """other as a [G', C] float64 DeviceArray in this array's cell order: a lazy reduction or a lazy grouped quantile in that order,
+        or a lazy rolling statistic of one, is computed in HBM, any other array goes up once"""
         order = (self._gdim,) + self._rest
         o = self._other
+        from .order_stats import TimeQuantileGridArray
         from .rolling import RolledGridArray
 
-        lazy = isinstance(o, (GroupReducedGridArray, RolledGridArray)) and _lazy_dim(o, (GroupReducedGridArray,)) == self._gdim
+        lazy = isinstance(o, (GroupReducedGridArray, RolledGridArray, TimeQuantileGridArray)) and _lazy_dim(o, (GroupReducedGridArray,)) == self._gdim
         if lazy and tuple(o.dims) == order:
             return o.device_field(ctx)
         v = np.ascontiguousarray((o if tuple(o.dims) == order else o.transpose(*order)).values, dtype=np.float64)

@@ -397,6 +397,72 @@ def bench_rolling(ctx, args):
     return res
 
 
+def bench_quantile(ctx, args):
+    """the quantile kernels on 14 600 daily steps x 100 000 cells float64: by month (G = 12) with q = [0.05, 0.5, 0.95] -- the segment path
+    at its widest width -- and the whole axis with q = 0.5 -- the series path --, each kernel timed through ctx.prof() beside
+    sd_memcpy_d2d of the same source bytes, beside groupby_reduce_kernel (mean by month) and beside the kernels of a BcsdPrecipitation
+    fit of the same field (sd_bcsd_fit_dev, SD_BCSD_PR: the same twelve sorts per cell) in the same run; GB/s by algorithmic bytes (8 * T
+    * C read + 8 * Q * G * C written); the first 256 cells compared bit for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _quantile_oracle as qo
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    month = (np.asarray(index.month) - 1).astype(np.int32)
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(call, repeats):
+        """per kernel: (median ms, [min, max]) of ``repeats`` profiled calls after one warm-up"""
+        call()
+        ctx.prof_enable(True)
+        seen = {}
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            for name, v in ctx.prof().items():
+                seen.setdefault(name, []).append(v["ms"])
+        ctx.prof_enable(False)
+        return {name: {"kernel_ms": float(np.median(v)), "kernel_ms_min_max": [min(v), max(v)]} for name, v in seen.items()}
+
+    d, first = fill(C), fill(256).to_host()
+    spare = ctx.empty((T, C))
+    repeats = max(args.steps, 5)
+    src_bytes = 8 * T * C
+    copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+    spare.free()
+    res = {"workload": f"quantile {T} daily steps x {C} cells float64: q = [0.05, 0.5, 0.95] by month (G=12), and q = 0.5 of the whole axis",
+           "repeats": repeats, "device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6}}
+    mean = ctx.empty((12, C))
+
+    def reduce():
+        for a in ctx.groupby_reduce(d, month, 12, "mean", out=mean)[1]:
+            a.free()
+
+    res["groupby_reduce_kernel_month_mean"] = timed(reduce, repeats)["groupby_reduce_kernel"]
+    mean.free()
+
+    def fit():
+        ctx.bcsd_fit(_lib.BCSD_PR, None, d, month, 12, True).close()
+
+    kernels = timed(fit, repeats)
+    res["bcsd_pr_fit"] = {"kernels": kernels, "kernel_ms": sum(k["kernel_ms"] for k in kernels.values())}
+    for name, q, group, G in (("by_month", [0.05, 0.5, 0.95], month, 12), ("whole_axis", [0.5], None, 1)):
+        out = ctx.empty((len(q) * G, C))
+        kernels = timed(lambda: ctx.quantile(d, q, group, G, out=out), repeats)
+        ms = sum(k["kernel_ms"] for k in kernels.values())
+        nbytes = src_bytes + 8 * len(q) * G * C
+        same = qo.same(out.cells(0, 256).to_host(), qo.quantile_field(first, q, group, G))
+        res[name] = {"G": G, "q": q, "kernels": kernels, "kernel_ms": ms, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                     "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": bool(same),
+                     "kernel_over_copy_ms": ms / copy_ms, "kernel_over_groupby_reduce_ms": ms / res["groupby_reduce_kernel_month_mean"]["kernel_ms"],
+                     "kernel_over_bcsd_pr_fit_ms": ms / res["bcsd_pr_fit"]["kernel_ms"]}
+        out.free()
+    return res
+
+
 def bench_remap(ctx, args):
     """remap_kernel alone (ctx.prof(): an event pair around the launch): 14 600 daily steps of a 250 x 400 fine field onto 16 x 25
     coarse cells by area overlap (latitude in sin(lat); 250 / 16 is not an integer, so target rows share source rows), float64 and
@@ -460,7 +526,7 @@ def bench_remap(ctx, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -479,9 +545,9 @@ def main():
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
         return
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
-                           "groupby": bench_groupby, "rolling": bench_rolling}[args.workload](ctx, args))
+                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
