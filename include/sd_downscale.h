@@ -128,6 +128,19 @@ extern "C" {
 #define SD_QUANTILE_MIDPOINT 4  /* v[h] where h is whole, else the interpolation at 0.5 */
 #define SD_QUANTILE_MEDIAN 5    /* np.nanmedian: the middle sample, or (v[n/2 - 1] + v[n/2]) / 2; q and Q are not read, Q counts as 1 */
 
+/* sd_spells: the comparison of a sample x with its threshold t (one IEEE comparison of doubles) */
+#define SD_SPELL_GT 0  /* x > t */
+#define SD_SPELL_GE 1  /* x >= t */
+#define SD_SPELL_LT 2  /* x < t */
+#define SD_SPELL_LE 3  /* x <= t */
+/* sd_spells: statistics of a bin, from its state (valid, hits, run, longest, days, spells) */
+#define SD_SPELL_VALID 0          /* steps where neither the sample nor the threshold is NaN */
+#define SD_SPELL_COUNT 1          /* hits */
+#define SD_SPELL_FRACTION 2       /* (double)hits / (double)valid; NaN for a bin without a valid step */
+#define SD_SPELL_LONGEST_SPELL 3  /* the longest run of consecutive hits */
+#define SD_SPELL_SPELL_DAYS 4     /* steps inside runs of at least min_length hits */
+#define SD_SPELL_SPELL_COUNT 5    /* runs of at least min_length hits */
+
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
 
@@ -575,6 +588,40 @@ int sd_quantile_dev(sd_ctx* ctx, int method, int skipna, const void* src_dev, in
 /* host buffers: src [T, C], out [Q * G, C]; upload, run, download */
 int sd_quantile(sd_ctx* ctx, int method, int skipna, const void* src_host, int src_is_f32, int64_t T, int64_t C, const int32_t* group_or_null,
                 int64_t G, const double* q, int64_t Q, double* out_host);
+
+/* ---- threshold and spell indices per period: GridArray.where(op, threshold).resample(time=rule).count() / .longest_spell() ... ----
+ * src is a [T, C] field (cells fastest, rows ld >= C elements apart; float64, or float32 with src_is_f32 != 0).  The bins are those of
+ * sd_resample: offsets, a host array of M + 1 entries that starts at 0, never decreases and ends at T.  The threshold of row r and
+ * cell c is the scalar `threshold` (table NULL; ld_t, group and G are not read), or table[group[r] * ld_t + c] of a [G, C] float64
+ * device table (rows ld_t >= C apart; `threshold` is not read); group: host int32 [T] with every id in [0, G), or NULL with G == 1:
+ * row 0 for every row, a per-cell threshold.
+ *
+ * The rule, per cell over the steps of one bin in time order.  x is the sample widened to double, t the threshold as double.  A step
+ * is valid when neither x nor t is NaN.  A step is a hit when it is valid and x (op) t holds: one IEEE comparison, +-inf are ordinary
+ * values.  An invalid step is not a hit and ends a spell.  Spells are cut at the bin's ends: a bin is evaluated by itself (climdex's
+ * spells.can.span.years = FALSE).  The state (valid, hits, run, longest, days, spells), all int32 and all zero at the bin's start, is
+ * updated per step for the minimum spell length L = min_length >= 1:
+ *     valid += is_valid;  hits += hit;  run = hit ? run + 1 : 0;  longest = max(longest, run)
+ *     if (run == L) { days += L; spells += 1; } else if (run > L) days += 1;
+ * out holds nstat float64 fields [M, C] (rows ld_out >= C apart, the fields stride_out >= M * ld_out elements apart): field s is the
+ * statistic stats[s] (SD_SPELL_VALID .. SD_SPELL_SPELL_COUNT; a host array of nstat codes, 1 <= nstat <= 6), all from one pass over
+ * src.  SD_SPELL_FRACTION is one division, NaN for a bin without a valid step; every other statistic of such a bin -- empty or
+ * invalid throughout -- is 0.  All values are integers or one division of integers: the result is the same bit for bit whatever the
+ * layout, the leading dimensions or the launch geometry.
+ *
+ * Deviation from NumPy 2: a float32 sample is compared after widening, against a double threshold.  NumPy compares a float32 array
+ * with a Python float in float32: np.float32(0.1) > 0.1 is False there and True here.
+ *
+ * An unknown op or statistic code, nstat outside 1 .. 6, min_length < 1, sizes <= 0, T >= 2^31 (the counts are int32), a leading
+ * dimension below C, stride_out < M * ld_out, G < 1, a NULL group with G > 1, a group id outside [0, G) and a table of bins that
+ * breaks the rules above are SD_ERR_INVALID, refused before anything is allocated or launched. */
+int sd_spells_dev(sd_ctx* ctx, const void* src_dev, int src_is_f32, int64_t ld, int64_t T, int64_t C, int op, double threshold,
+                  const double* table_dev_or_null, int64_t ld_t, const int32_t* group_or_null, int64_t G, const int64_t* offsets, int64_t M,
+                  int64_t min_length, const int* stats, int nstat, double* out_dev, int64_t ld_out, int64_t stride_out);
+/* host buffers: src [T, C], table [G, C] or NULL, out [nstat * M, C]; upload, run, download */
+int sd_spells(sd_ctx* ctx, const void* src_host, int src_is_f32, int64_t T, int64_t C, int op, double threshold,
+              const double* table_host_or_null, const int32_t* group_or_null, int64_t G, const int64_t* offsets, int64_t M, int64_t min_length,
+              const int* stats, int nstat, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

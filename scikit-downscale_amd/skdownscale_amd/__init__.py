@@ -16,6 +16,7 @@ from .disagg import DisaggregatedGridArray, time_map
 from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, group_labels
 from .rolling import GridRolling, RolledGridArray
 from .order_stats import TimeQuantileGridArray
+from .spells import GridCondition, SpellGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -68,5 +69,7 @@ __all__ = [
     "GridRolling",
     "RolledGridArray",
     "TimeQuantileGridArray",
+    "GridCondition",
+    "SpellGridArray",
 ]
 __version__ = "0.1.0"

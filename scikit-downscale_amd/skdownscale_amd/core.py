@@ -214,6 +214,26 @@ class GridArray:
         return TimeQuantileGridArray(self, dim, 0.5, by, "median", skipna, name,
                                      scratch_bytes=DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def where(self, op, threshold, dim="time", by=None, name="group", scratch_bytes=None):
+        """``where("<", 1.0).resample(time="YS").longest_spell()``: threshold and spell indices per period and cell on the GPU (frost
+        days, R1mm, CDD / CWD, WSDI, TX90p).  ``op``: '>' | '>=' | '<' | '<='.  ``threshold``: a number (``by`` must be None); an array
+        or ``GridArray`` over the other dims, one value per cell (``by`` None); or, with ``by`` as for ``quantile`` -- ``"<dim>.<field>"``,
+        one label per step or a callable (the group dim is then named ``name``) --, a ``[G, *rest]`` array with one field per sorted
+        label or a ``GridArray`` carrying the group dim, its rows matched by label as ``gb - other`` matches them (a lazy grouped mean,
+        scalar-``q`` quantile or ``rolling`` of one stays in HBM).  A step is valid when neither the sample nor its threshold is NaN
+        and a hit when it is valid and ``sample op threshold`` holds as doubles (a float32 sample is widened first: NumPy 2 compares
+        with a Python float in float32, so ``np.float32(0.1) > 0.1`` is False there and True here); an invalid step ends a spell.
+        -> ``GridCondition``: nothing is computed yet.  Its ``resample(time=rule, **pandas_kw)`` cuts the axis into pandas' bins, each
+        evaluated by itself (spells do not span bins); without it the whole axis is one bin, the dim is dropped and the whole field is
+        held in HBM (``T * C * itemsize`` bytes).  ``valid()``, ``count()``, ``fraction()`` (NaN for a bin without a valid step),
+        ``longest_spell()``, ``spell_days(min_length)``, ``spell_count(min_length)`` give a lazy ``SpellGridArray`` (float64, exact);
+        ``indices(names, min_length=1)`` several of them behind a leading ``"index"`` dim from one pass over the field.
+        ``scratch_bytes``: device scratch of one block of whole bins (default 1 GiB; a block is at least one bin)."""
+        from .resample import DEFAULT_SCRATCH_BYTES
+        from .spells import GridCondition
+
+        return GridCondition(self, op, threshold, dim, by, name, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
         """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
         daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and

@@ -1077,6 +1077,96 @@ class Context:
         check(self.lib.sd_resample(self.handle, code, ptr(field), f32, T, Cc, ptr(offsets), M, ptr(out)))
         return out
 
+    # ---- threshold and spell indices per bin of the time axis (GridArray.where) ----
+    @staticmethod
+    def _spells_args(field, op, threshold, offsets, stats, min_length, group):
+        if op not in _lib.SPELL_OPS:
+            raise ValueError(f"where op {op!r}: expected one of {', '.join(repr(k) for k in _lib.SPELL_OPS)}")
+        stats = [stats] if isinstance(stats, str) else list(stats)
+        for s in stats:
+            if s not in _lib.SPELL_STATS:
+                raise ValueError(f"spell statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SPELL_STATS)}")
+        if not 1 <= len(stats) <= len(_lib.SPELL_STATS):
+            raise ValueError(f"sd_downscale: sd_spells: nstat = {len(stats)}, expected 1 to {len(_lib.SPELL_STATS)} statistics")
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        T, Cc = field.shape
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
+        M = len(offsets) - 1
+        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_spells: bad sizes (T={T}, C={Cc}, M={M})")
+        table = None
+        if isinstance(threshold, DeviceArray) or np.ndim(threshold) > 0:
+            table = threshold if isinstance(threshold, DeviceArray) else np.ascontiguousarray(threshold, dtype=np.float64)
+            if len(table.shape) != 2 or table.dtype != np.float64 or table.shape[1] != Cc or table.shape[0] < 1:
+                raise ValueError(f"threshold: expected a number or a float64 [G, {Cc}] table, got shape {tuple(table.shape)} of {table.dtype}")
+            threshold = 0.0
+            if group is not None:
+                group = np.ascontiguousarray(group, dtype=np.int32)
+                if group.shape != (T,):
+                    raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+        elif group is not None:
+            raise ValueError("group: a scalar threshold takes no group ids")
+        codes = np.ascontiguousarray([_lib.SPELL_STATS[s] for s in stats], dtype=np.intc)
+        return field, _lib.SPELL_OPS[op], float(threshold), table, group, offsets, codes, int(min_length), int(field.dtype == np.float32)
+
+    def spells(self, field, op, threshold, offsets, stats, min_length=1, group=None, out=None, plane_rows=None):
+        """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); op
+        '>' | '>=' | '<' | '<='; threshold: a number, or a [G, C] float64 table (host array or DeviceArray) whose row ``group[r]``
+        (host int32 [T]; None with G == 1: a per-cell threshold) holds the thresholds of row r; offsets: host int64 [M + 1], bin m =
+        rows offsets[m] .. offsets[m + 1] - 1; stats: one name or a list of 'valid' | 'count' | 'fraction' | 'longest_spell' |
+        'spell_days' | 'spell_count' -> [nstat * M, C] float64 DeviceArray, row ``s * M + m`` the statistic s of bin m, all from one
+        pass over the field (sd_spells_dev; the rule is in include/sd_downscale.h).  ``out``: that DeviceArray, possibly a view of a
+        wider one.  With ``plane_rows`` ``out`` is instead the [M, C] view of this call's bins inside the first of nstat planes of
+        ``plane_rows`` rows each of a longer DeviceArray (how a caller fills the bins block by block)."""
+        field, code, thr, table, group, offsets, codes, L, f32 = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
+        T, Cc = field.shape
+        M, nstat = len(offsets) - 1, len(codes)
+        if plane_rows is None:
+            out = self._result_buffer(out, (nstat * M, Cc), True)
+            stride = M * out.ld
+        else:
+            out = self._result_buffer(out, (M, Cc), True)
+            base = out.base
+            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
+            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
+                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
+            stride = int(plane_rows) * out.ld
+        mine = []  # (what this call uploads, freed when it is over)
+        try:
+            if not isinstance(field, DeviceArray):
+                field = self.to_device(field, field.dtype)
+                mine.append(field)
+            if table is not None and not isinstance(table, DeviceArray):
+                table = self.to_device(table)
+                mine.append(table)
+            for name, a in (("field", field), ("threshold", table), ("out", out)):
+                if a is not None and a.ctx is not self:
+                    raise ValueError(f"sd_downscale: sd_spells: `{name}` belongs to another context")
+            check(self.lib.sd_spells_dev(self.handle, field.vptr, f32, field.ld, T, Cc, code, thr, None if table is None else table.vptr,
+                                         0 if table is None else table.ld, None if group is None else ptr(group),
+                                         1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), nstat, out.vptr, out.ld, stride))
+        finally:
+            for a in mine:
+                a.free()
+        return out
+
+    def spells_host(self, field, op, threshold, offsets, stats, min_length=1, group=None):
+        """host [T, C] -> host [nstat * M, C] through sd_spells (upload, run, download in one call)"""
+        field, code, thr, table, group, offsets, codes, L, f32 = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
+        if isinstance(field, DeviceArray) or isinstance(table, DeviceArray):
+            raise ValueError("spells_host: expected host arrays")
+        T, Cc = field.shape
+        M = len(offsets) - 1
+        out = np.empty((len(codes) * M, Cc))
+        check(self.lib.sd_spells(self.handle, ptr(field), f32, T, Cc, code, thr, ptr(table), None if group is None else ptr(group),
+                                 1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), len(codes), ptr(out)))
+        return out
+
     # ---- temporal disaggregation (GridArray.disaggregate) ----
     @staticmethod
     def _disagg_args(target, obs, src_row, offsets, op, climo, group):

@@ -36,16 +36,23 @@ def check_quantiles(q):
     return np.atleast_1d(arr).copy(), arr.ndim == 0
 
 
-def _whole_field(source, dim, ctx, block_bytes):
-    """``source`` as one [T, C] DeviceArray the caller frees (C = cells of the other dims in their order, the last fastest)"""
+def lazy_whole_source(source, dim):
+    """whether ``source`` is a not yet computed lazy array that gives its whole field as [steps of ``dim``, C] through its own
+    ``device_field``: a ``resample`` / ``groupby`` / ``rolling`` result, a ``GroupApplied`` anomaly, ``disaggregate``, or a
+    ``remap_like`` of such a field"""
     from .disagg import DisaggregatedGridArray
     from .groupby import GroupAppliedGridArray, GroupReducedGridArray, _lazy_dim
     from .remap import RemappedGridArray
 
     if _lazy_dim(source, (GroupReducedGridArray, GroupAppliedGridArray, DisaggregatedGridArray)) == dim:
-        return source.device_field(ctx)
-    if (isinstance(source, RemappedGridArray) and not source.computed and not source._host_source() and len(source.dims) == 3
-            and source.dims[0] == dim and source._lead_dims() == source.dims[:1]):
+        return True
+    return (isinstance(source, RemappedGridArray) and not source.computed and not source._host_source() and len(source.dims) == 3
+            and source.dims[0] == dim and source._lead_dims() == source.dims[:1])
+
+
+def _whole_field(source, dim, ctx, block_bytes):
+    """``source`` as one [T, C] DeviceArray the caller frees (C = cells of the other dims in their order, the last fastest)"""
+    if lazy_whole_source(source, dim):
         return source.device_field(ctx)
     T = source.sizes[dim]
     resident = resident_source(source, dim)

@@ -524,9 +524,81 @@ def bench_remap(ctx, args):
     return results
 
 
+def bench_spells(ctx, args):
+    """spells_kernel on 14 600 daily steps x 100 000 cells float64 with 'YS' bins: a scalar threshold with one statistic, and a [366, C]
+    day-of-year table (the day-of-year means of the field) with three statistics (fraction, spell_days at min_length 6, count), each
+    timed through ctx.prof() -- median and [min, max] of 7 profiled calls after a warm-up -- beside sd_memcpy_d2d of the same source
+    bytes, resample_kernel (mean over the same bins) and groupby_apply_kernel (minus the same table) in the same run; GB/s by algorithmic bytes (8 * T * C read, + 8 * T * C
+    of table rows for the table case, + 8 * nstat * M * C written) and, for the table case, by distinct bytes too (the table once, 8 * 366 * C:
+    each of its rows is read again in every year, which the caches can serve); the first 256 cells compared bit for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _spells_oracle as sp
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    labels, offsets = time_bins(index, "YS")
+    M = len(labels)
+    doy = (np.asarray(index.dayofyear) - 1).astype(np.int32)
+    tab = synth.tas_tables(index)["y_obs"]
+
+    def fill(cells):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(call, kernel, repeats):
+        call()
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            times.append(ctx.prof()[kernel]["ms"])
+        ctx.prof_enable(False)
+        return {"kernel_ms": float(np.median(times)), "kernel_ms_min_max": [min(times), max(times)]}
+
+    d, first = fill(C), fill(256).to_host()
+    repeats = 7
+    src_bytes = 8 * T * C
+    spare = ctx.empty((T, C))
+    copy_ms, copy_min_max = device_copy_ms(ctx, spare, d, src_bytes, repeats)
+    spare.free()
+    res = {"workload": f"spells {T} daily steps -> {M} 'YS' bins x {C} cells float64: scalar threshold, 1 statistic; [366, C] day-of-year table, 3 statistics",
+           "repeats": repeats, "device_copy": {"ms": copy_ms, "ms_min_max": copy_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6}}
+    mean = ctx.empty((M, C))
+    res["resample_kernel_mean"] = timed(lambda: ctx.resample(d, offsets, "mean", out=mean), "resample_kernel", repeats)
+    res["resample_kernel_mean"]["algorithmic_bytes"] = src_bytes + 8 * M * C
+    mean.free()
+    clim, acc = ctx.groupby_reduce(d, doy, 366, "mean")
+    for a in acc:
+        a.free()
+    anom = ctx.empty((T, C))  # the yardstick of the table case: groupby_apply_kernel reads the same source and table rows (and writes 8 * T * C)
+    res["groupby_apply_kernel_sub_doy"] = timed(lambda: ctx.groupby_apply(d, doy, clim, "sub", out=anom), "groupby_apply_kernel", repeats)
+    res["groupby_apply_kernel_sub_doy"]["algorithmic_bytes"] = 3 * src_bytes + 8 * 366 * C
+    anom.free()
+    threshold = float(np.nanmean(first))
+    cases = (("scalar_1_statistic", ">", threshold, None, ["longest_spell"], 1, 0, 0),
+             ("doy_table_3_statistics", ">", clim, doy, ["fraction", "spell_days", "count"], 6, 8 * T * C, 8 * 366 * C))
+    for name, op, thr, group, stats, L, table_bytes, table_distinct in cases:
+        out = ctx.empty((len(stats) * M, C))
+        r = timed(lambda: ctx.spells(d, op, thr, offsets, stats, L, group, out=out), "spells_kernel", repeats)
+        ms = r["kernel_ms"]
+        nbytes = src_bytes + table_bytes + 8 * len(stats) * M * C
+        host_thr = thr if group is None else thr.cells(0, 256).to_host()
+        got, want = out.cells(0, 256).to_host(), sp.spells(first, offsets, op, host_thr, stats, L, group)
+        distinct = src_bytes + table_distinct + 8 * len(stats) * M * C
+        r.update({"op": op, "statistics": stats, "min_length": L, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                  "distinct_bytes": distinct, "GBps_of_distinct_bytes": distinct / ms / 1e6,
+                  "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": bool(np.array_equal(got, want, equal_nan=True)),
+                  "kernel_over_copy_ms": ms / copy_ms, "kernel_over_resample_ms": ms / res["resample_kernel_mean"]["kernel_ms"],
+                  "kernel_over_groupby_apply_ms": ms / res["groupby_apply_kernel_sub_doy"]["kernel_ms"]})
+        res[name] = r
+        out.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -545,9 +617,9 @@ def main():
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
         return
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
-                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile}[args.workload](ctx, args))
+                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
