@@ -370,6 +370,7 @@ struct DevPtr {
 };
 struct DevGroupTable {  // borrowed from the context's group-table cache (valid until the next upload_group_table calls evict it)
     DevPtr order, off;
+    DevPtr rtab;  // request row tables of the LDS-DMA kernel (cached tables only; nullptr: none)
     int nmax = 0;
     std::vector<int64_t> host_off;
     sd_scratch own_order, own_off;  // explicit tables (upload_explicit_table) are owned by the call
@@ -417,6 +418,7 @@ int upload_group_table(sd_ctx* ctx, const int32_t* gid, int64_t T, int G, DevGro
             SD_HIP(hipStreamSynchronize(ctx->stream));
             (void)hipFree(ctx->gt_cache[lru].order);
             (void)hipFree(ctx->gt_cache[lru].off);
+            (void)hipFree(ctx->gt_cache[lru].rtab);
             ctx->gt_cache.erase(ctx->gt_cache.begin() + (long)lru);
         }
         sd_gt_cache_entry e;
@@ -430,15 +432,35 @@ int upload_group_table(sd_ctx* ctx, const int32_t* gid, int64_t T, int G, DevGro
             (void)hipFree(e.order);
             SD_HIP(rc);
         }
+        // The request row tables of the LDS-DMA kernel (sd_bcsd_plan.h: build_row_tables) live and die with the entry: they depend
+        // on the order table alone.  Built for every group of a length that kernel is launched on; none of them: no tables.
+        std::vector<int32_t> rtab;
+        if (G <= 64)
+            for (int g = 0; g < G; ++g) {
+                const int n = (int)(gt.off[g + 1] - gt.off[g]);
+                if (!sdfx::tmj::tab_len_ok(n)) continue;
+                if (rtab.empty()) rtab.assign((size_t)G * sdfx::tmj::kTabInts, 0);
+                sdfx::tmj::build_row_tables(gt.order.data() + gt.off[g], n, rtab.data() + (size_t)g * sdfx::tmj::kTabInts);
+            }
+        if (!rtab.empty()) {
+            rc = hipMalloc((void**)&e.rtab, sizeof(int32_t) * rtab.size());
+            if (rc != hipSuccess) {
+                (void)hipFree(e.order);
+                (void)hipFree(e.off);
+                SD_HIP(rc);
+            }
+        }
         ctx->gt_cache.push_back(std::move(e));
         hit = &ctx->gt_cache.back();
         SD_HIP(hipMemcpyAsync(hit->order, gt.order.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, ctx->stream));
         SD_HIP(hipMemcpyAsync(hit->off, off32.data(), sizeof(int32_t) * (G + 1), hipMemcpyHostToDevice, ctx->stream));
+        if (hit->rtab) SD_HIP(hipMemcpyAsync(hit->rtab, rtab.data(), sizeof(int32_t) * rtab.size(), hipMemcpyHostToDevice, ctx->stream));
         SD_HIP(hipStreamSynchronize(ctx->stream));  // host vectors go out of scope
     }
     hit->last_use = ++ctx->gt_clock;
     d->order.p = hit->order;
     d->off.p = hit->off;
+    d->rtab.p = hit->rtab;
     d->nmax = hit->nmax;
     d->host_off = hit->host_off;
     return SD_OK;
@@ -900,9 +922,9 @@ sdrs::Params call_params(const BcsdPlan& plan, int kind, int G, int return_anoms
     p.C = C; p.Tf = Tf; p.ntiles = (C + 7) / 8;
     p.n_endpoints = n_endpoints > 0 ? n_endpoints : 10;  // quantile.py:426
     p.X = X; p.y = y; p.ld = ld;
-    if (gf) { p.ord_f = (const int32_t*)gf->order.p; p.off_f = (const int32_t*)gf->off.p; }
+    if (gf) { p.ord_f = (const int32_t*)gf->order.p; p.off_f = (const int32_t*)gf->off.p; p.rtab_f = (const int32_t*)gf->rtab.p; }
     p.Xp = Xp; p.ld_p = ld_p; p.out = out; p.ld_out = ld_out; p.status_p = status_p;
-    if (gp) { p.ord_p = (const int32_t*)gp->order.p; p.off_p = (const int32_t*)gp->off.p; }
+    if (gp) { p.ord_p = (const int32_t*)gp->order.p; p.off_p = (const int32_t*)gp->off.p; p.rtab_p = (const int32_t*)gp->rtab.p; }
     if (plan.fused)
         if (const char* e = sd_dev_env("SD_FZ_ABLATE")) p.dev_flags = atoi(e);
     return p;

@@ -858,21 +858,8 @@ namespace tmj {
 // ds_read_b64 and ds_read2_b64 alike; the tails likewise ((nl + t) + 8 s2 = nl + l mod 32).  (Rows in time order with the
 // chunks skewed by 16 B -- the first version -- put lanes 16 chunks apart on the same banks: 3-way conflicts, and the column
 // phases ran at half the speed of the old cell-major rows.)  A sample's tag = its position 16 chunk + slot (11 bits).
-// (kChunkStride, kBlock, lanes_of, chunks_of: sd_bcsd_plan.h)
-__device__ __forceinline__ int tail_chunk(int l) { return (l & 7) + 8 * (l >> 5); }
-__device__ __forceinline__ int tail_slot(int l) { return (l >> 3) & 3; }
-// row of the segment that slot S of chunk Q holds (n - 1 where the slot holds none)
-__device__ __forceinline__ int row_of_slot(int Q, int S, int nl, int n) {
-    int r;
-    if (Q < nl) {
-        r = kBlock * Q + S;
-    } else {
-        const int t = Q - nl;
-        const int l = (t & 7) + 8 * (S & 3) + 32 * (t >> 3);
-        r = l < nl ? kBlock * l + 16 + (S >> 2) : n - 1;
-    }
-    return r < n ? r : n - 1;
-}
+// (kChunkStride, kBlock, lanes_of, chunks_of, tail_chunk, tail_slot, row_of_slot -- the row of the segment that slot S of chunk Q
+// holds -- and the row tables: sd_bcsd_plan.h)
 __device__ __forceinline__ unsigned tag_off(unsigned tag) { return (tag << 6) + ((tag >> 4) << 3); }  // position -> byte offset (cell 0)
 
 template <int NREG>
@@ -895,6 +882,21 @@ __device__ __forceinline__ RowIdx<NREG> rows_of_chunks(const int32_t* __restrict
 template <int NREG>
 __device__ __forceinline__ RowIdx<NREG> rows_of_wave(const int32_t* __restrict__ ord, int n, int q0, int wave, int lane) {
     return rows_of_chunks<NREG>(ord, n, q0 + wave, kW, lane);
+}
+// The same registers from a group's row table (sd_bcsd_plan.h: build_row_tables): register j, lane <- tab[FIRST + 64 j + lane], one
+// contiguous line per register and no arithmetic beyond the lane offset.  LAST: the last entry the list may name (entries behind
+// it belong to requests nobody makes: they read entry LAST).
+//   rows_of_wave<N>(ord, n, 8 k0, wave)      = rows_of_table<N, 16 k0, kTabWave - 1>(W + kTabWave wave)
+//   rows_of_chunks<N>(ord, n, qb, 1)         = rows_of_table<N, 0, ...>(P + 16 qb)
+template <int NREG, int FIRST, int LAST>
+__device__ __forceinline__ RowIdx<NREG> rows_of_table(const int32_t* __restrict__ tab, int lane) {
+    RowIdx<NREG> t;
+#pragma unroll
+    for (int j = 0; j < NREG; ++j) {
+        const int e = FIRST + 64 * j + lane;
+        t.v[j] = tab[FIRST + 64 * j + 63 > LAST ? (e < LAST ? e : LAST) : e];
+    }
+    return t;
 }
 // The indices are "used" here, so the compiler's wait for their loads sits here -- ahead of the requests -- and not between
 // them, where it would count only its own loads and drain the DMA queue with them.
@@ -1108,7 +1110,10 @@ inline bool fd_geometry_ok(int rs, size_t lds) {
     const int nch = rs / 16;
     return rs % 16 == 0 && nch >= kU2Chunks && nch <= kFdMaxChunks && lds >= kHeadDoubles * sizeof(double) + (size_t)nch * tmj::kChunkStride;
 }
-template <int K, bool RAG>
+// TAB: the request rows (rp, ry_late, ry_early, ro: the same ten registers, named at the same places) come from the row tables of
+// the launch's group tables (Params::rtab_f / rtab_p) instead of ~20 vector instructions and a dependent gather each; a launch
+// without tables (explicit group tables, SD_FD_NOTAB of the development library) takes the instantiation that derives them.
+template <int K, bool RAG, bool TAB>
 __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     ParamsPtr p = (ParamsPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1148,6 +1153,8 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     const int m = p->off_f[g + 1] - begf;  // == the predict segment's length (groups of equal length)
     const int begp = p->off_p[g];
     if (m == 0) return;
+    const int32_t* const tab_f = TAB ? p->rtab_f + (int64_t)g * tmj::kTabInts : nullptr;  // [P | W] of the group, fit order
+    const int32_t* const tab_p = TAB ? p->rtab_p + (int64_t)g * tmj::kTabInts : nullptr;  // predict order
     const int nl = RAG ? tmj::lanes_of(m) : m / K;  // lanes with data
     const int nch = tmj::chunks_of(m);
     constexpr int nlate = kU2Chunks;  // chunks under the u2 area: the late half of y (nch > nlate: fd_geometry_ok)
@@ -1165,7 +1172,9 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     tmj::RowIdx<2> ry_early;
     {
         SD_LANE();
-        tmj::RowIdx<3> rp = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, lane);  // (in one batch with the rows of the x_hist tile)
+        tmj::RowIdx<3> rp;  // (in one batch with the rows of the x_hist tile)
+        if constexpr (TAB) rp = tmj::rows_of_table<3, 0, tmj::kTabWave - 1>(tab_p + tmj::kTabP + tmj::kTabWave * wave, lane);
+        else rp = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, lane);
         TileRegs<NR> xh;
         int tf[NR];
         rows_load<NR, !RAG>(p->ord_f + begf, m, tf);
@@ -1276,8 +1285,13 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         SDT(3);  // rolling mean
         // the rows of the y requests (the loads return under the key generation): the late chunks are those under the u2 region
         // of the wave's column -- col, not wave: a tile shifted back over its predecessor rotates the columns
-        ry_late = tmj::rows_of_chunks<2>(p->ord_f + begf, m, kU2CellChunks * col, 1, lane);
-        ry_early = tmj::rows_of_wave<2>(p->ord_f + begf, m, nlate, wave, lane);
+        if constexpr (TAB) {
+            ry_late = tmj::rows_of_table<2, 0, tmj::kTabP - 1>(tab_f + 16 * kU2CellChunks * col, lane);
+            ry_early = tmj::rows_of_table<2, 16 * (nlate / kW), tmj::kTabWave - 1>(tab_f + tmj::kTabP + tmj::kTabWave * wave, lane);
+        } else {
+            ry_late = tmj::rows_of_chunks<2>(p->ord_f + begf, m, kU2CellChunks * col, 1, lane);
+            ry_early = tmj::rows_of_wave<2>(p->ord_f + begf, m, nlate, wave, lane);
+        }
         SDPH("u_keys");
         unsigned u2[K];
         {
@@ -1415,7 +1429,9 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
     SDPH("store");
     SDT(13);  // scatter, shift restored
     redo_flag[wave] = redo_y ? 2 : 0;  // (bit 1: no barrier lies between the readers of the first vote and this write; bit 0 stays 0)
-    tmj::RowIdx<3> ro = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, tid_now() % kWave);  // (named ahead of the last barrier)
+    tmj::RowIdx<3> ro;  // (named ahead of the last barrier)
+    if constexpr (TAB) ro = tmj::rows_of_table<3, 0, tmj::kTabWave - 1>(tab_p + tmj::kTabP + tmj::kTabWave * wave, tid_now() % kWave);
+    else ro = tmj::rows_of_wave<3>(p->ord_p + begp, m, 0, wave, tid_now() % kWave);
     __syncthreads();
     tmj::rows_ready(ro);
     SDT(14);  // last barrier
@@ -2045,7 +2061,10 @@ int run_k(sd_ctx* ctx, const BcsdLaunch& L, const Params& p) {
             if constexpr (K == tmj::kBlock) {
                 if (!fd_geometry_ok(L.rs, L.lds))
                     return sd_set_error(SD_ERR_INVALID, "bcsd_fd_kernel: rs = %d, %zu bytes of LDS do not hold its u2 area", L.rs, (size_t)L.lds);
-                return launch_rec(ctx, L, p, L.kernel == BcsdKernel::FdWhole ? &bcsd_fd_kernel<K, false> : &bcsd_fd_kernel<K, true>);
+                // (a record with row tables on group tables that carry none -- explicit tables -- derives the rows in the kernel)
+                if (L.row_tables && p.rtab_f != nullptr && p.rtab_p != nullptr)
+                    return launch_rec(ctx, L, p, L.kernel == BcsdKernel::FdWhole ? &bcsd_fd_kernel<K, false, true> : &bcsd_fd_kernel<K, true, true>);
+                return launch_rec(ctx, L, p, L.kernel == BcsdKernel::FdWhole ? &bcsd_fd_kernel<K, false, false> : &bcsd_fd_kernel<K, true, false>);
             }
             break;
         default: break;

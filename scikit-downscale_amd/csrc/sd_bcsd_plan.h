@@ -76,6 +76,49 @@ constexpr int kChunkStride = 1024 + 8;
 constexpr int kBlock = 20;  // rows per lane (the kernel's K)
 constexpr int lanes_of(int n) { return (n + kBlock - 1) / kBlock; }
 constexpr int chunks_of(int n) { return lanes_of(n) + 16; }  // n: more than 32 lanes of 20
+// Lane l works on rows 20 l .. 20 l + 19: chunk l holds the first 16 of them (slot i = row 20 l + i), its tail of four sits in chunk
+// nl + tail_chunk(l) at the slots tail_slot(l) + 4 e (nl = lanes_of(n); the layout and its bank arithmetic: sd_bcsd_fx.hip)
+constexpr int tail_chunk(int l) { return (l & 7) + 8 * (l >> 5); }
+constexpr int tail_slot(int l) { return (l >> 3) & 3; }
+// row of the segment that slot S of chunk Q holds (n - 1 where the slot holds none, chunks past the tile included)
+__attribute__((always_inline)) constexpr int row_of_slot(int Q, int S, int nl, int n) {
+    int r = 0;
+    if (Q < nl) {
+        r = kBlock * Q + S;
+    } else {
+        const int t = Q - nl;
+        const int l = (t & 7) + 8 * (S & 3) + 32 * (t >> 3);
+        r = l < nl ? kBlock * l + 16 + (S >> 2) : n - 1;
+    }
+    return r < n ? r : n - 1;
+}
+
+// Request row tables of one group: the time index behind every (chunk, slot) of the tile is a function of the group's order table
+// alone -- the same for every tile, step and call on that calendar --, so it is tabulated once per cached group table
+// (sd_bcsd.hip: upload_group_table) instead of derived by every (tile, month) item:
+//   P[16 Q + S]         = ord[row_of_slot(Q, S, nl, n)], Q = 0 .. kTabChunks - 1: every chunk three row registers of a wave name
+//                         (8 waves x 12 requests); the late y requests of column `col` read P at 16 * 5 col + 64 j + lane
+//   W[wave][j][lane]    = P[16 (wave + 8 (4 j + lane / 16)) + lane % 16]: the chunks wave + 8 k dealt round the waves, in the order
+//                         a wave's registers hold them (register j, lane) -- one contiguous 256-byte line per register
+// One group's table is [P | W]; a table set holds one per group of the order table (groups no LDS-DMA launch serves stay zero).
+constexpr int kTabChunks = 96;
+constexpr int kTabP = 16 * kTabChunks;               // entries of P
+constexpr int kTabWave = 3 * 64;                     // entries of W per wave
+constexpr int kTabW = sdw::kW * kTabWave;            // entries of W
+constexpr int kTabInts = kTabP + kTabW;              // 3 072 entries, 12 KB per group
+static_assert(sdw::kW - 1 + sdw::kW * (kTabWave / 16 - 1) == kTabChunks - 1, "W names the chunks of P, all of them");
+// the segment lengths the LDS-DMA kernel is launched on (bcsd_plan_detail::plan_fx: `fits`)
+constexpr bool tab_len_ok(int n) { return n > 32 * kBlock && n <= 64 * kBlock; }
+inline void build_row_tables(const int32_t* ord, int n, int32_t* tab) {
+    const int nl = lanes_of(n);
+    for (int Q = 0; Q < kTabChunks; ++Q)
+        for (int S = 0; S < 16; ++S) tab[16 * Q + S] = ord[row_of_slot(Q, S, nl, n)];
+    int32_t* W = tab + kTabP;
+    for (int wave = 0; wave < sdw::kW; ++wave)
+        for (int j = 0; j < 3; ++j)
+            for (int lane = 0; lane < 64; ++lane)
+                W[wave * kTabWave + 64 * j + lane] = tab[16 * (wave + sdw::kW * (4 * j + lane / 16)) + lane % 16];
+}
 }  // namespace tmj
 
 // LDS of a workgroup of the LDS-DMA kernel: [head: kHeadDoubles][tile: chunks_of(nmax) x 1 032 B]; the u2 area (8 cells x RSU
@@ -140,6 +183,7 @@ struct BcsdDevSwitches {
     bool no_dma = false;       // SD_FX_NODMA: the register-tile kernel instead of the LDS-DMA one
     bool no_full = false;      // SD_FX_NOFULL: no whole-lane (FULL) launches
     bool no_compact = false;   // SD_FX_NOCOMPACT: no compacting precipitation kernel
+    bool no_tab = false;       // SD_FD_NOTAB: the LDS-DMA kernel derives its request rows itself (no row tables)
 };
 
 struct BcsdCall {
@@ -191,6 +235,7 @@ struct BcsdLaunch {
     int64_t grid_x, grid_y;
     int block;
     const char* name;          // profiler name
+    bool row_tables = false;   // LDS-DMA kernel: the request rows come from the group tables' row tables (tmj::build_row_tables)
 };
 
 struct BcsdPlan {
@@ -298,7 +343,9 @@ inline bool plan_fx(const BcsdCall& c, BcsdPlan* pl, int nmax, const std::vector
         return nmn > 640 && nch <= 80 && late <= 40 && nch - late <= 40 && 2 * sdfx::fd_lds_bytes(n) <= c.lds_max;
     };
     const auto fd = [&](unsigned long long mask, int s, BcsdKernel k, const char* name) {
-        return add_tiled(c, pl, k, 20, true, mask, sdfx::fd_u2_stride(nmx[s]), 0, 0, sdfx::fd_lds_bytes(nmx[s]), name);
+        if (!add_tiled(c, pl, k, 20, true, mask, sdfx::fd_u2_stride(nmx[s]), 0, 0, sdfx::fd_lds_bytes(nmx[s]), name)) return false;
+        pl->launches.back().row_tables = !c.dev.no_tab;  // (`fits` admits the lengths of tmj::tab_len_ok only)
+        return true;
     };
     const bool fd_full = dma && full != 0ull && fits(full, 0), fd_rest = dma && rest != 0ull && fits(rest, 1);
     if (full == 0ull && !fd_rest) return general(0ull);

@@ -51,6 +51,9 @@ struct Params {
     double* y_trend;       // state [C][G][2]: slope, intercept of the fitted segment's line
     int n_endpoints;  // points of the OLS tail lines (quantile.py:426, 537-541); 0 is taken as the default 10 (sd_bcsd.hip: call_params)
     int dev_flags;  // development library only (SD_FZ_ABLATE): phases skipped to time the rest; results are then wrong
+    // request row tables of the LDS-DMA kernel, [G][tmj::kTabInts] next to ord_f / ord_p (sd_bcsd_plan.h: build_row_tables); nullptr
+    // where the group table has none (explicit tables, or no group of a length that kernel serves)
+    const int32_t* rtab_f; const int32_t* rtab_p;
 };
 
 }  // namespace sdrs

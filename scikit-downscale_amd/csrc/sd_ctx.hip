@@ -25,6 +25,7 @@ void sd_gt_cache_clear(sd_ctx* ctx) {
     for (auto& e : ctx->gt_cache) {
         if (e.order) (void)hipFree(e.order);
         if (e.off) (void)hipFree(e.off);
+        if (e.rtab) (void)hipFree(e.rtab);
     }
     ctx->gt_cache.clear();
 }

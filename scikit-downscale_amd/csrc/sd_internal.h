@@ -39,6 +39,7 @@ static inline BcsdDevSwitches sd_bcsd_dev_switches() {
     d.no_fused = on("SD_BCSD_FUSED", "0");
     d.no_rs_split = on("SD_RS_SPLIT", "0");
     d.no_dma = on("SD_FX_NODMA", "");
+    d.no_tab = on("SD_FD_NOTAB", "");
     d.no_full = on("SD_FX_NOFULL", "");
     d.no_compact = on("SD_FX_NOCOMPACT", "");
     return d;
@@ -95,6 +96,7 @@ struct sd_gt_cache_entry {
     int G = 0;
     int32_t* order = nullptr;  // device [T]
     int32_t* off = nullptr;    // device [G+1]
+    int32_t* rtab = nullptr;   // device [G][sdfx::tmj::kTabInts]: request row tables of the LDS-DMA kernel (nullptr: no group takes it)
     int nmax = 0;
     std::vector<int64_t> host_off;
     uint64_t last_use = 0;
