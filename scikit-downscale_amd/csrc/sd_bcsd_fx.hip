@@ -59,10 +59,8 @@ using sdrs::Params;
 
 typedef const Params __attribute__((address_space(4)))* ParamsPtr;
 
-constexpr unsigned kTagBits = 11, kTagMask = 2047u;
-constexpr unsigned kQD = (1u << 21) - 2048u;  // data keys use q <= kQD; pads q = kQD + 1 + slot
-
-// (kFront, Lay<K> -- the slot of a sample in its row -- and row_slots: sd_bcsd_plan.h)
+// (kTagBits, kTagMask, kQD -- keys = (q << 11) | tag, data keys q <= kQD, pads q = kQD + 1 + slot --, kFront, Lay<K> -- the slot of
+// a sample in its row -- and row_slots: sd_bcsd_plan.h)
 
 __device__ __forceinline__ unsigned lds_u32(unsigned a) { return *reinterpret_cast<__attribute__((address_space(3))) unsigned*>((uintptr_t)a); }
 
@@ -265,7 +263,9 @@ __device__ __forceinline__ void store_tile_sw(double* __restrict__ dst, int64_t 
 // column sums of one group's rows for the 8 cells of the tile from issued tile registers, as far as one wave gets: the wave's
 // partial sums go to scratch[wave][cell]; the caller adds the 8 partials of its cell behind its next barrier (sd_wave.h's
 // tile_reduce_mean does the same with two barriers of its own)
-template <int RPT, bool FULL = false>
+// SUMTEST (bcsd_fd_kernel): the thread's two sums are tested instead of every value -- a non-finite addend makes its sum non-finite
+// (inf - inf = NaN) --, and only a non-finite sum, that of finite values that overflow included, takes the per-value tests.
+template <int RPT, bool FULL = false, bool SUMTEST = false>
 __device__ __forceinline__ void tile_reduce_partials(const TileRegs<RPT>& t, int nrows, int64_t c0, int64_t C, double* scratch,
                                                      int32_t* status, int wave, int lane, int* bad_cell) {
     const int tid = tid_now();
@@ -276,8 +276,10 @@ __device__ __forceinline__ void tile_reduce_partials(const TileRegs<RPT>& t, int
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
         // (rows past the segment were loaded from row 0 of the segment: testing them too flags nothing new)
-        bad0 |= nonfinite64(t.v0[k]);
-        bad1 |= nonfinite64(t.v1[k]);
+        if (!SUMTEST) {
+            bad0 |= nonfinite64(t.v0[k]);
+            bad1 |= nonfinite64(t.v1[k]);
+        }
         if (FULL && k + 1 < RPT) {
             s0 += t.v0[k];
             s1 += t.v1[k];
@@ -285,6 +287,14 @@ __device__ __forceinline__ void tile_reduce_partials(const TileRegs<RPT>& t, int
             const bool in = rr + k * kRowsPerPass < nrows;
             s0 += in ? t.v0[k] : 0.0;
             s1 += in ? t.v1[k] : 0.0;
+        }
+    }
+    if (SUMTEST && (nonfinite64(s0) || nonfinite64(s1))) {
+        // (row 0 of the segment, which stands in for the rows past it, is some thread's first row: in its sum)
+#pragma unroll
+        for (int k = 0; k < RPT; ++k) {
+            bad0 |= nonfinite64(t.v0[k]);
+            bad1 |= nonfinite64(t.v1[k]);
         }
     }
     if (bad0 && c < C) atomicOr(&status[c], SDI_NONFINITE);
@@ -860,7 +870,17 @@ namespace tmj {
 // phases ran at half the speed of the old cell-major rows.)  A sample's tag = its position 16 chunk + slot (11 bits).
 // (kChunkStride, kBlock, lanes_of, chunks_of, tail_chunk, tail_slot, row_of_slot -- the row of the segment that slot S of chunk Q
 // holds -- and the row tables: sd_bcsd_plan.h)
-__device__ __forceinline__ unsigned tag_off(unsigned tag) { return (tag << 6) + ((tag >> 4) << 3); }  // position -> byte offset (cell 0)
+__device__ __forceinline__ unsigned tag_off(unsigned tag) { return tag_off_ref(tag); }  // position -> byte offset (cell 0)
+// LDS address of the position a key names in the column at colb: colb + key_off(key) (sd_bcsd_plan.h) in four instructions --
+// v_bfe_u32 (chunk), v_mad_u32_u24 (chunk * 1 032 + colb), v_and_b32 (slot), v_lshl_add_u32.  The last one is written out: the
+// compiler turns (key & 15) << 6 into (key << 6) & 0x3c0 and then needs five.  (Its result feeds a DS address: no hazard the
+// compiler would have to see.)
+__device__ __forceinline__ unsigned key_addr(unsigned colb, unsigned key, unsigned stride = (unsigned)kChunkStride) {
+    const unsigned base = bfe(key, 4, kTagBits - 4) * stride + colb, slot = key & 15u;
+    unsigned a;
+    asm("v_lshl_add_u32 %0, %1, 6, %2" : "=v"(a) : "v"(slot), "v"(base));
+    return a;
+}
 
 template <int NREG>
 struct RowIdx {
@@ -978,6 +998,26 @@ __device__ __forceinline__ Tags tags_of(int lane, int nl) {
     return Tags{16u * (unsigned)lane, 16u * (unsigned)(nl + tail_chunk(lane)) + (unsigned)tail_slot(lane)};
 }
 
+// The pad keys (pad_key: sd_bcsd_plan.h) replace the data keys of the positions past the segment.  Whole-lane segments: those are
+// the lanes past the data, two to four of the 64 -- one block under their exec mask (K adds) instead of an add and a select per key
+// in every lane; the empty inline assembly keeps the compiler from turning the block back into selects.  RAG: the last data lane
+// ends inside its block, one compare and select per sample as before.
+template <int K, bool RAG>
+__device__ __forceinline__ void pad_keys(int m, int lane, unsigned (&key)[K]) {
+    static_assert(K == kBlock, "pad_key counts in lanes of kBlock samples");
+    unsigned pad0 = pad_key(lane, 0);
+    if constexpr (RAG) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) key[i] = K * lane + i < m ? key[i] : pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
+    } else {
+        if (K * lane >= m) {
+            asm volatile("" : "+v"(pad0));
+#pragma unroll
+            for (int i = 0; i < K; ++i) key[i] = pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
+        }
+    }
+}
+
 // keys + second-level keys of the shifted series: t = (v - lo) * sc + 1 in [1, kQD - 1]; t + 2^21 has the exponent of 2^21, so its
 // mantissa is t in units of 2^-31: 21 bits of q above 31 further bits.  Monotone in v (fma, add: correctly rounded).
 // key = (q << 11) | sample index; u2 = the low mantissa word (bit 31 = the lowest bit of q: equal wherever q is).
@@ -990,20 +1030,14 @@ template <int K, bool RAG, class GetU>
 __device__ __forceinline__ void keys_u2(const GetU& u_of, double lo, double hi, int m, int lane, const Tags& tg, unsigned (&key)[K], unsigned (&u2)[K]) {
     const double sc = (double)(kQD - 2u) / (hi - lo);  // +inf when every sample is equal: t = NaN everywhere, all keys and u2 tie
     const double off = -lo * sc + 1.0;
-    const unsigned tag0 = (unsigned)(K * lane);
-    const unsigned pad0 = ((kQD + 1u + tag0) << kTagBits) | tag0;
-    const bool lane_in = K * lane < m;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         const double t = __builtin_fma(u_of(i), sc, off) + 2097152.0;
         const unsigned w0 = (unsigned)__double2loint(t), w1 = (unsigned)__double2hiint(t);
-        unsigned q = __builtin_amdgcn_alignbit(w1, w0, 31) & 0x1fffffu;
-        q = q < kQD ? q : kQD;
-        const unsigned dk = (q << kTagBits) | tg.of(i);
-        const unsigned pk = pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
-        key[i] = (RAG ? K * lane + i < m : lane_in) ? dk : pk;
+        key[i] = key_u2(w0, w1, tg.of(i));  // (sd_bcsd_plan.h: alignbit, min, tag add, bfi)
         u2[i] = w0;
     }
+    pad_keys<K, RAG>(m, lane, key);
 }
 // keys of the observations (the cvt path of keys_from_range) with position tags.  The extremes need no mask: the slots of a
 // ragged last lane past the segment hold copies of its last row, lanes past the segment lane 0's block.
@@ -1019,17 +1053,13 @@ __device__ __forceinline__ void keys_pos(const double (&v)[K], int m, int lane, 
     hi = wave_max_f64(hi);
     const double sc = (double)kQD / (hi - lo);
     const double off = -lo * sc;
-    const unsigned tag0 = (unsigned)(K * lane);
-    const unsigned pad0 = ((kQD + 1u + tag0) << kTagBits) | tag0;
-    const bool lane_in = K * lane < m;
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         unsigned q = (unsigned)__builtin_fma(v[i], sc, off);
         q = q < kQD ? q : kQD;
-        const unsigned dk = (q << kTagBits) | tg.of(i);
-        const unsigned pk = pad0 + (unsigned)i * ((1u << kTagBits) + 1u);
-        key[i] = (RAG ? K * lane + i < m : lane_in) ? dk : pk;
+        key[i] = (q << kTagBits) | tg.of(i);
     }
+    pad_keys<K, RAG>(m, lane, key);
 }
 
 // exact order inside runs of equal q (see fix_equal_q): the values behind two tags are fetched and compared by `cmp`
@@ -1095,6 +1125,13 @@ __device__ __forceinline__ int fix_equal_q_by(unsigned (&k)[K], int lane, const 
 // Per-sample predicates where a position past m would change a result: the rolling window and its count (the last two lanes),
 // the extremes of u, the pad keys, the y climatology sum, the scatter and the stores; the other lanes compute the same values
 // as the whole-lane instantiation.  The x_hist rows are predicated like the general kernel's (segments below full_min_len).
+// route of the cross-lane stages of the two sorts (sd_wsort.h: via_lds); -DSD_FD_ROUTE=1 .. 3 builds the other policies for A/B runs.
+// Policy 0 (DPP wherever it exists) is the fastest here: +0.13, +0.28 and +0.43 ms per step for the policies 1, 2 and 3
+// (profiles/fd_valu/README.md)
+#ifndef SD_FD_ROUTE
+#define SD_FD_ROUTE 0
+#endif
+constexpr int kFdRoute = SD_FD_ROUTE;
 constexpr int kU2CellChunks = 5;                                 // whole chunks per cell of the u2 area
 constexpr int kU2CellBytes = kU2CellChunks * tmj::kChunkStride;  // 5 160 B
 constexpr int kU2Chunks = kW * kU2CellChunks;                    // 40: the u2 area = the late half of y
@@ -1197,7 +1234,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
                 xh.v1[k] = v.y;
             }
         }
-        if (!(abl & 4)) tile_reduce_partials<NR, !RAG>(xh, m, c0, p->C, scratch, p->status_fit, wave, lane, bad_cell);
+        if (!(abl & 4)) tile_reduce_partials<NR, !RAG, true>(xh, m, c0, p->C, scratch, p->status_fit, wave, lane, bad_cell);
         SDT(1);  // x_hist summed, x_fut requested
         tmj::dma_wait_all();
     }
@@ -1319,7 +1356,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         wave_fence();
         SDT(4);  // u2 stored, keys
         SDPH("u_sort");
-        if (!(abl & 1)) sdws::wave_sort<K>(ku, lane, (m + K - 1) / K);
+        if (!(abl & 1)) sdws::wave_sort<K, kFdRoute>(ku, lane, (m + K - 1) / K);
         SDT(5);  // sort of u
         SDPH("u_fix");
         const auto cmp_u2 = [ub](unsigned ta, unsigned tb, bool* gt, bool* eq) {
@@ -1378,9 +1415,13 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
             bool bad = false;
             const int rl = m - K * bl;
 #pragma unroll
-            for (int i = 0; i < K; ++i) {
-                s += !RAG || i < rl ? v[i] : 0.0;  // (RAG: the sum of the general kernel)
-                bad |= nonfinite64(v[i]);
+            for (int i = 0; i < K; ++i) s += !RAG || i < rl ? v[i] : 0.0;  // (RAG: the sum of the general kernel)
+            // One test of the sum instead of one per observation: a non-finite addend makes the sum non-finite (inf - inf = NaN).
+            // A non-finite sum -- finite observations whose sum overflows land here too -- takes the per-value tests, which decide.
+            // (RAG: the slots past the segment hold copies of its last row, which the sum includes.)
+            if (nonfinite64(s)) {
+#pragma unroll
+                for (int i = 0; i < K; ++i) bad |= nonfinite64(v[i]);
             }
             s = has ? s : 0.0;
             yc = wave_sum_f64(s) / (double)m;  // bcsd.py:223
@@ -1389,7 +1430,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         }
         SDT(10);  // y_climo, keys
         SDPH("y_sort");
-        if (!(abl & 2)) sdws::wave_sort<K>(ky, lane, (m + K - 1) / K);
+        if (!(abl & 2)) sdws::wave_sort<K, kFdRoute>(ky, lane, (m + K - 1) / K);
         SDT(11);  // sort of y
         SDPH("y_fix");
         const auto cmp_y = [colb](unsigned ta, unsigned tb, bool* gt, bool* eq) {
@@ -1400,9 +1441,10 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
         if (!(abl & 8)) redo_y = (tmj::fix_equal_q_by<K>(ky, lane, cmp_y) & kUnsorted) != 0 && cell_live;  // tied observations are interchangeable
         SDPH("y_gather");
         {
-            const unsigned tm = has ? kTagMask : 0u;  // (pad keys carry tags of no sample: those lanes read position 0)
+            // (pad keys carry tags of no sample: the lanes past the data take a chunk stride of 0 and read some slot of chunk 0)
+            const unsigned stride = has ? (unsigned)tmj::kChunkStride : 0u;
 #pragma unroll
-            for (int i = 0; i < K; ++i) t[i] = lds_f64(colb + tmj::tag_off(ky[i] & tm));
+            for (int i = 0; i < K; ++i) t[i] = lds_f64(tmj::key_addr(colb, ky[i], stride));
         }
         SDT(12);  // fix-up of y, sorted observations gathered
         // ---- identity map (equal group lengths): rank r of u takes the r-th smallest observation; scatter to the time slots ----
@@ -1413,7 +1455,7 @@ __global__ void __launch_bounds__(kThreads, 4) bcsd_fd_kernel(const Params) {
             // those values go to the lane's own slots past the segment, which the stores skip)
             const tmj::Tags tg = tmj::tags_of(lane, nl);
 #pragma unroll
-            for (int i = 0; i < K; ++i) lds_store_f64(colb + tmj::tag_off(!RAG || K * lane + i < m ? ku[i] & kTagMask : tg.of(i)), t[i]);
+            for (int i = 0; i < K; ++i) lds_store_f64(tmj::key_addr(colb, !RAG || K * lane + i < m ? ku[i] : tg.of(i)), t[i]);
         }
         wave_fence();
         SDPH("restore");

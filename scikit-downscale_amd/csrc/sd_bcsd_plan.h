@@ -27,6 +27,10 @@ namespace sdfx {
 
 constexpr int kFront = 4;
 
+// sort keys of the fused kernels: (q << kTagBits) | tag, q the quantised value, tag the sample's position in its row or tile
+constexpr unsigned kTagBits = 11, kTagMask = 2047u;
+constexpr unsigned kQD = (1u << 21) - 2048u;  // data keys use q <= kQD; pads q = kQD + 1 + slot
+
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
 
 // LDS row layout of the register-tile kernels: sample j of the segment sits in slot 4 + j + j / (K * P), P = 64 / gcd(2K, 64)
@@ -92,6 +96,35 @@ __attribute__((always_inline)) constexpr int row_of_slot(int Q, int S, int nl, i
     }
     return r < n ? r : n - 1;
 }
+
+// ---- integer formulas of the kernel's keys and tag addresses, as the kernel evaluates them (`_ref`: the forms they replaced,
+// kept for tests/fd_keys_check.cpp, which runs both) -----------------------------------------------------------------------------
+// v_alignbit_b32 / v_bfe_u32 / v_bfi_b32
+constexpr uint32_t alignbit(uint32_t hi, uint32_t lo, unsigned s) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> s); }
+constexpr uint32_t bfe(uint32_t v, unsigned off, unsigned width) { return (v >> off) & ((1u << width) - 1u); }
+constexpr uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) { return (mask & a) | (~mask & b); }
+// key of a sample of the shifted series from the two words (w1: high) of t + 2^21, t = the quantised value in [1, kQD - 1]: the
+// mantissa is t in units of 2^-31, q = its bits 51 .. 31, clamped to kQD (NaN: 2^20), above the tag.
+constexpr uint32_t key_u2_ref(uint32_t w0, uint32_t w1, uint32_t tag) {
+    uint32_t q = alignbit(w1, w0, 31) & 0x1fffffu;
+    q = q < kQD ? q : kQD;
+    return (q << kTagBits) | tag;
+}
+// The same in four instructions: alignbit by 20 leaves q in bits 31 .. 11 (the exponent falls off the top) over 11 fraction bits;
+// clamped with the fraction bits all ones, the q field is min(q, kQD); the tag (< 2^11) then replaces the fraction bits.
+constexpr uint32_t key_u2(uint32_t w0, uint32_t w1, uint32_t tag) {
+    const uint32_t a = alignbit(w1, w0, 32 - 1 - kTagBits), top = (kQD << kTagBits) | kTagMask;
+    return bfi(kTagMask, tag, a < top ? a : top);
+}
+// pad key i of lane `lane` (a lane past the data): q = kQD + 1 + K lane + i above the tag K lane + i
+constexpr uint32_t pad_key(int lane, int i) {
+    const uint32_t tag0 = (uint32_t)(kBlock * lane);
+    return (((kQD + 1u + tag0) << kTagBits) | tag0) + (uint32_t)i * ((1u << kTagBits) + 1u);
+}
+// byte offset (cell 0) of position `tag` = 16 chunk + slot of the tile: chunk * kChunkStride + 64 slot
+constexpr uint32_t tag_off_ref(uint32_t tag) { return (tag << 6) + ((tag >> 4) << 3); }
+// The same straight from a key (no `& kTagMask` first): the chunk is a bit field of the key, the slot a masked shift.
+constexpr uint32_t key_off(uint32_t key) { return bfe(key, 4, kTagBits - 4) * (uint32_t)kChunkStride + ((key << 6) & 0x3c0u); }
 
 // Request row tables of one group: the time index behind every (chunk, slot) of the tile is a function of the group's order table
 // alone -- the same for every tile, step and call on that calendar --, so it is tabulated once per cached group table

@@ -13,7 +13,9 @@
 //     8, 15; ds_swizzle -- the LDS crossbar, no LDS memory -- for lane ^ 4, 16, 31; ds_bpermute for lane ^ 63) and
 //     v_med3_u32(own, partner, sel) with sel = 0 in the lanes that keep the minimum and 0xffffffff in those that keep
 //     the maximum: median(a, b, 0) = min(a, b), median(a, b, ~0) = max(a, b).  No lane-dependent sign conventions, no
-//     divergence; all keys stay in true ascending order.
+//     divergence; all keys stay in true ascending order.  Which route a stage takes is one function, via_lds(policy, L, x):
+//     the policies 1 .. 3 move DPP stages of the levels 4 .. 6 to the LDS pipe (one vector instruction per key less each);
+//     measured inside bcsd_fd_kernel every step of them is slower (profiles/fd_valu/README.md), so every kernel uses policy 0.
 //   * the local merger sorts cyclic-bitonic sequences: even lengths are half-cleaned and split; the odd lengths 3 and 5
 //     (K = 12, 24; K = 20) end in 3-sorters (v_min3 / v_med3 / v_max3_u32), other odd lengths in a full sorter.
 //
@@ -135,8 +137,25 @@ struct SchedOp {
     unsigned char kind, a, b, c;
 };
 constexpr int kMaxSched = 768;
-// partners fetched through the LDS pipe (ds_swizzle / ds_bpermute) instead of a DPP move
-constexpr bool via_lds(int x) { return x == 4 || x == 16 || x == 31 || x == 63; }
+// Route of a cross-lane stage: the partner lane ^ x of merge level L comes through the LDS pipe (ds_swizzle / ds_bpermute: no
+// vector instruction) or by a DPP move (one vector instruction per key).  lane ^ 4, 16, 31, 63 have no DPP form.  The others have
+// both, and saturated the two cost the same (profiles/r06/microbench_permlane_swap.log), so which is cheaper depends on how busy
+// the kernel keeps either pipe: a policy moves stages of the levels 4 .. 6 -- where LevelSched hides the round trip behind the
+// other half-batch -- to the LDS pipe.  The levels 1 .. 3 hide nothing and stay DPP under every policy.
+//   0  DPP wherever it exists
+//   1  + lane ^ 15 in level 4 and lane ^ 8 in the levels 5 and 6     (-60 vector instructions per sort at K = 20)
+//   2  + lane ^ 2 in the levels 4 .. 6                                (-120)
+//   3  + lane ^ 1 in the levels 4 .. 6                                (-180)
+// LevelSched and lane_xor both read this one function.  A kernel names its policy in wave_sort<K, POLICY>; the default is 0.
+constexpr int kRoutePolicies = 4;
+constexpr bool via_lds(int policy, int L, int x) {
+    if (x == 4 || x == 16 || x == 31 || x == 63) return true;
+    if (L < 4) return false;
+    if (policy >= 1 && ((L == 4 && x == 15) || (L >= 5 && x == 8))) return true;
+    if (policy >= 2 && x == 2) return true;
+    if (policy >= 3 && x == 1) return true;
+    return false;
+}
 
 // A/B: -DSD_WSORT_PREFETCH chains the levels 4 -> 5 -> 6 through PRE / NEXT below.  Not the default: up to K more temporaries are
 // live across a merger, and bcsd_fd_kernel<20> then spills (128 VGPRs, 14 to scratch).
@@ -154,8 +173,9 @@ constexpr bool kPrefetch = false;
 // The halves A = [0, K/2) and B = [K/2, K) each walk stage by stage; a half that has just issued fetches through the LDS pipe
 // hands over to the other one, which runs until it has issued such fetches itself (or is done).  Every med3 of stage 0 comes after
 // all fetches of stage 0: it overwrites a register the partner lane reads.
-template <int K, int L, bool PRE, bool NEXT>
+template <int K, int L, bool PRE, bool NEXT, int POLICY = 0>
 struct LevelSched {
+    static constexpr bool via_lds(int x) { return sdws::via_lds(POLICY, L, x); }
     int n = 0;
     SchedOp op[kMaxSched] = {};
     constexpr void put(unsigned char kind, int a, int b, int c) {
@@ -258,28 +278,20 @@ __device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b 
 // median of three; the compiler matches max(min(a, b), min(max(a, b), c)) to v_med3_u32
 __device__ __forceinline__ unsigned med3(unsigned a, unsigned b, unsigned c) { return umax(umin(a, b), umin(umax(a, b), c)); }
 
-// the value lane (l ^ X) holds in v
-template <int X>
+// the value lane (l ^ X) holds in v; LDS: through the LDS pipe (via_lds of the stage's level and policy)
+template <int X, bool LDS>
 __device__ __forceinline__ unsigned lane_xor(unsigned v, int addr63) {
-#ifdef SD_WSORT_SWZ
-    // A/B: partners below lane ^ 32 through the LDS crossbar instead of DPP moves (one vector instruction per key and stage less,
-    // one LDS-pipe instruction more); SD_WSORT_SWZ is a bit mask over X
-    if constexpr (X < 32 && ((SD_WSORT_SWZ >> (X == 1 ? 0 : X == 2 ? 1 : X == 3 ? 2 : X == 7 ? 3 : X == 8 ? 4 : X == 15 ? 5 : 6)) & 1))
-        return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (X << 10) | 0x1F);
-    else
-#endif
-    if constexpr (X == 1) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
+    static_assert(LDS || !via_lds(0, 6, X), "lane ^ 4, 16, 31, 63 have no DPP form");
+    if constexpr (X == 63) return (unsigned)__builtin_amdgcn_ds_bpermute(addr63, (int)v);
+    else if constexpr (LDS) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (X << 10) | 0x1F);  // and 0x1f, xor X (X < 32)
+    else if constexpr (X == 1) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
     else if constexpr (X == 2) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
     else if constexpr (X == 3) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x1B, 0xF, 0xF, true);   // quad_perm [3,2,1,0]
     else if constexpr (X == 7) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);  // row_half_mirror
     else if constexpr (X == 15) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true);  // row_mirror
-    else if constexpr (X == 8) return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, true);   // row_ror:8
-    else if constexpr (X == 4) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);               // and 0x1f, xor 4
-    else if constexpr (X == 16) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);              // and 0x1f, xor 16
-    else if constexpr (X == 31) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, 0x7C1F);              // and 0x1f, xor 31
     else {
-        static_assert(X == 63, "unsupported lane permutation");
-        return (unsigned)__builtin_amdgcn_ds_bpermute(addr63, (int)v);
+        static_assert(X == 8, "unsupported lane permutation");
+        return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, true);   // row_ror:8
     }
 }
 
@@ -344,7 +356,7 @@ __device__ __forceinline__ void cross_stage(unsigned (&k)[K], int lane, int addr
     const unsigned sel = (unsigned)(-((lane >> BIT) & 1));
     unsigned t[K];
 #pragma unroll
-    for (int i = 0; i < K; ++i) t[i] = lane_xor<X>(k[i], addr63);
+    for (int i = 0; i < K; ++i) t[i] = lane_xor<X, via_lds(0, BIT + 1, X)>(k[i], addr63);  // (stage by stage: nothing hides a round trip)
 #pragma unroll
     for (int i = 0; i < K; ++i) k[i] = med3(k[i], t[REV ? K - 1 - i : i], sel);
 }
@@ -352,20 +364,20 @@ __device__ __forceinline__ void cross_stage(unsigned (&k)[K], int lane, int addr
 // One level in the issue order of LevelSched.  t: the partner temporaries, kept by the caller because a level's NEXT fetches are
 // consumed by the level after it; `next` (wave-uniform): that level runs.  The compiler places the s_waitcnt lgkmcnt itself (the
 // LDS pipe returns in order, so they are counted); the fences keep the requests and their consumers where the list puts them.
-template <int K, int L, bool PRE, bool NEXT>
+template <int K, int L, bool PRE, bool NEXT, int POLICY>
 struct LevelTables {
-    static constexpr LevelSched<K, L, PRE, NEXT> s{};
+    static constexpr LevelSched<K, L, PRE, NEXT, POLICY> s{};
     static constexpr BitonicNet<K> bnet{};
 };
 
-template <int K, int L, bool PRE, bool NEXT, int O>
+template <int K, int L, bool PRE, bool NEXT, int POLICY, int O>
 __device__ __forceinline__ void sched_step(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next) {
-    using T = LevelTables<K, L, PRE, NEXT>;
+    using T = LevelTables<K, L, PRE, NEXT, POLICY>;
     constexpr int kind = T::s.op[O].kind, a = T::s.op[O].a, b = T::s.op[O].b, c = T::s.op[O].c;
     if constexpr (kind == kOpFetch) {
-        t[b] = lane_xor<c>(k[a], addr63);
+        t[b] = lane_xor<c, via_lds(POLICY, L, c)>(k[a], addr63);
     } else if constexpr (kind == kOpFetchNext) {
-        if (next) t[b] = lane_xor<c>(k[a], addr63);
+        if (next) t[b] = lane_xor<c, via_lds(POLICY, L + 1, c)>(k[a], addr63);
     } else if constexpr (kind == kOpMed) {
         k[a] = med3(k[a], t[b], (unsigned)(-((lane >> c) & 1)));
     } else if constexpr (kind == kOpNet) {
@@ -393,14 +405,14 @@ __device__ __forceinline__ void sched_step(unsigned (&k)[K], unsigned (&t)[2 * K
     }
 }
 
-template <int K, int L, bool PRE, bool NEXT, int... O>
+template <int K, int L, bool PRE, bool NEXT, int POLICY, int... O>
 __device__ __forceinline__ void sched_steps(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next, std::integer_sequence<int, O...>) {
-    (sched_step<K, L, PRE, NEXT, O>(k, t, lane, addr63, next), ...);
+    (sched_step<K, L, PRE, NEXT, POLICY, O>(k, t, lane, addr63, next), ...);
 }
 
-template <int K, int L, bool PRE, bool NEXT>
+template <int K, int L, bool PRE, bool NEXT, int POLICY>
 __device__ __forceinline__ void merge_level_piped(unsigned (&k)[K], unsigned (&t)[2 * K], int lane, int addr63, bool next) {
-    sched_steps<K, L, PRE, NEXT>(k, t, lane, addr63, next, std::make_integer_sequence<int, LevelTables<K, L, PRE, NEXT>::s.n>{});
+    sched_steps<K, L, PRE, NEXT, POLICY>(k, t, lane, addr63, next, std::make_integer_sequence<int, LevelTables<K, L, PRE, NEXT, POLICY>::s.n>{});
 }
 
 template <int K, int L>
@@ -419,8 +431,10 @@ __device__ __forceinline__ void merge_level(unsigned (&k)[K], int lane, int addr
 
 // Sorts the wave's 64 * K keys; `lanes_used` (wave-uniform) = number of leading lanes that hold data: lanes beyond
 // must hold keys >= every key of the lanes in use (pads), and merge levels that could only move pads are skipped.
-template <int K>
+// POLICY: route of the cross-lane stages of the levels 4 .. 6 (via_lds)
+template <int K, int POLICY = 0>
 __device__ __forceinline__ void wave_sort(unsigned (&k)[K], int lane, int lanes_used = 64) {
+    static_assert(POLICY >= 0 && POLICY < kRoutePolicies, "route policy");
     constexpr SortNet<K> snet{};
     const int addr63 = (lane ^ 63) << 2;
     apply_net<K>(k, snet);
@@ -438,10 +452,10 @@ __device__ __forceinline__ void wave_sort(unsigned (&k)[K], int lane, int lanes_
     } else if (lanes_used > 8) {
         unsigned t[2 * K];
         const bool l5 = lanes_used > 16, l6 = lanes_used > 32;
-        merge_level_piped<K, 4, false, kPrefetch>(k, t, lane, addr63, l5);
+        merge_level_piped<K, 4, false, kPrefetch, POLICY>(k, t, lane, addr63, l5);
         if (l5) {
-            merge_level_piped<K, 5, kPrefetch, kPrefetch>(k, t, lane, addr63, l6);
-            if (l6) merge_level_piped<K, 6, kPrefetch, false>(k, t, lane, addr63, false);
+            merge_level_piped<K, 5, kPrefetch, kPrefetch, POLICY>(k, t, lane, addr63, l6);
+            if (l6) merge_level_piped<K, 6, kPrefetch, false, POLICY>(k, t, lane, addr63, false);
         }
         dpp_fence<K>(k);
     }
