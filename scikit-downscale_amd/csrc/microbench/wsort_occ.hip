@@ -10,6 +10,8 @@
 // Prints ns per sort per SIMD (= per-SIMD throughput) and ns per sort per wave (= latency a wave sees).
 // A/B of the issue order of the merge levels 4 .. 6 (sd_wsort.h): build once plain (half-batches), once with -DSD_WSORT_SERIAL (stage by
 // stage) and once with -DSD_WSORT_PREFETCH; profiles/wsort_pipe/microbench_wsort_occ.log.
+// A/B of the K = 20 tables: plain (the searched networks of sd_wsort_nets20.h) against -DSD_WSORT_NETS20_OFF (Batcher sorter,
+// half-cleaner merger); profiles/wsort_nets/microbench_wsort_occ.log.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
