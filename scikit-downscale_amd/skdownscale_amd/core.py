@@ -330,10 +330,35 @@ class LazyGridArray(GridArray):
 class DeferredGridArray(GridArray):
     """A float64 field that is computed when it is asked for, the base of what ``interp_like``, ``resample`` and ``disaggregate``
     return.  A subclass sets ``dims``, ``coords`` and ``name`` and gives ``sizes`` and ``_compute_values()``; ``values`` keeps what that
-    returned.  ``isel`` and ``transpose`` work on the computed field unless the subclass can stay lazy."""
+    returned.  ``isel`` and ``transpose`` work on the computed field unless the subclass can stay lazy.
+
+    What a lazy array says of itself as the *source* of another one (``timesource`` reads it): ``_kind`` names the class, ``_row_dim()``
+    and ``_block_producer()`` say how its field comes into HBM without crossing the host."""
 
     _full = None
     _ctx = None
+    _kind = None
+
+    def _row_dim(self):
+        """the dim along which ``device_field`` gives the field as [rows of that dim, cells of the other dims in their order]; None
+        where it does not"""
+        return None
+
+    def _block_producer(self, ctx, dim):
+        """a ``timesource.RowProducer`` where the field can be produced in HBM as [rows of ``dim``, cells], rows [r0, r1) at a time;
+        else None"""
+        return None
+
+    def _field_order(self):
+        """the dims of ``device_field``, the trailing ones flattened into its cells"""
+        raise NotImplementedError
+
+    def _compute_values(self):
+        field = self.device_field()
+        try:
+            return self._in_dims(field.to_host(), self._field_order())
+        finally:
+            field.free()
 
     @property
     def shape(self):

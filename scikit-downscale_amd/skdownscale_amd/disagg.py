@@ -21,7 +21,8 @@ import pandas as pd
 
 from . import _lib
 from .core import DeferredGridArray, GridArray
-from .resample import DEFAULT_SCRATCH_BYTES, ResampledGridArray, _bin_blocks
+from .resample import DEFAULT_SCRATCH_BYTES
+from .timesource import _bin_blocks, takes_whole
 
 KINDS = ("shift", "scale")
 
@@ -120,6 +121,8 @@ class DisaggregatedGridArray(DeferredGridArray):
     """A monthly ``GridArray`` turned into daily weather: same dims, ``dim`` at the number of days of the labelled months with the
     daily coordinate."""
 
+    _kind = "disagg"
+
     def __init__(self, monthly, daily_obs, dim="time", kind="shift", stat=None, years=None, seed=0, climatology=None, ctx=None,
                  scratch_bytes=DEFAULT_SCRATCH_BYTES):
         self._op = disagg_op(kind, stat)
@@ -182,73 +185,52 @@ class DisaggregatedGridArray(DeferredGridArray):
         """the monthly field as an [M, C] float64 DeviceArray: a resampled field in this order is reduced in HBM, any other goes up once"""
         order = (self._dim,) + self._rest
         m = self._monthly
-        if isinstance(m, ResampledGridArray) and tuple(m.dims) == order and not m.computed:
+        if takes_whole(m, "target", self._dim) and tuple(m.dims) == order:
             return m.device_field(ctx)
         v = _lib.as_f64((m if tuple(m.dims) == order else m.transpose(*order)).values)
         return ctx.to_device(v.reshape(v.shape[0], -1))
 
-    def _walk(self, ctx, block_out, done):
-        """blocks of whole months of at most ``scratch_bytes`` of output: ``block_out(r0, r1)`` names the [r1 - r0, C] DeviceArray
-        that takes the rows, ``done(r0, r1, block)`` is called when they are there.  A month is always made within one block by the
-        same lane: the result does not depend on the block size."""
-        off, M = self._offsets, len(self._offsets) - 1
+    def _row_dim(self):
+        return self._dim
+
+    def _make(self, ctx, to_host):
+        """the daily field, made in blocks of whole months of at most ``scratch_bytes`` of output: as a [Tout, C] DeviceArray, or with
+        ``to_host`` through one block of device scratch as a host array.  A month is always made within one block by the same lane:
+        the result does not depend on the block size."""
+        off, M, Tout = self._offsets, len(self._offsets) - 1, len(self._time)
         obs = self._obs_rows()
         C = obs.shape[1]
         if C < 1:
             raise ValueError(f"nothing to disaggregate: the array has sizes {self._monthly.sizes}")
-        d_obs = ctx.to_device(obs, obs.dtype)
-        target = self._target(ctx)
-        assert target.shape == (M, C), (target.shape, M, C)
-        climo = None if self._climo is None else ctx.to_device(self._climo)
+        blocks = [(a, b, int(off[a]), int(off[b])) for a, b in _bin_blocks(off, max(1, self._scratch_bytes // (C * 8)))]
+        d_obs = target = climo = out = None
+        kept = False
         try:
-            for a, b in _bin_blocks(off, max(1, self._scratch_bytes // (C * 8))):
-                r0, r1 = int(off[a]), int(off[b])
-                block = block_out(r0, r1, C)
+            d_obs = ctx.to_device(obs, obs.dtype)
+            target = self._target(ctx)
+            assert target.shape == (M, C), (target.shape, M, C)
+            climo = None if self._climo is None else ctx.to_device(self._climo)
+            out = ctx.empty((max(r1 - r0 for _, _, r0, r1 in blocks) if to_host else Tout, C))
+            host = np.empty((Tout, C)) if to_host else None
+            for a, b, r0, r1 in blocks:
+                block = out.rows(0, r1 - r0) if to_host else out.rows(r0, r1)
                 ctx.disaggregate(target.rows(a, b), d_obs, self._src_row[r0:r1], off[a:b + 1] - r0, self._op, climo,
                                  None if climo is None else self._group[a:b], out=block)
-                done(r0, r1, block)
+                if to_host:
+                    host[r0:r1] = block.to_host()
+            kept = not to_host
+            return host if to_host else out
         finally:
-            for d in (d_obs, target, climo):
+            for d in (d_obs, target, climo, None if kept else out):
                 if d is not None:
                     d.free()
 
-    def _largest_block(self, C):
-        off = self._offsets
-        return max(int(off[b] - off[a]) for a, b in _bin_blocks(off, max(1, self._scratch_bytes // (C * 8))))
-
     def device_field(self, ctx=None):
         """the daily field as a [Tout, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest)"""
-        ctx = self._context(ctx)
-        out = []
-
-        def block_out(r0, r1, C):
-            if not out:
-                out.append(ctx.empty((len(self._time), C)))
-            return out[0].rows(r0, r1)
-
-        self._walk(ctx, block_out, lambda r0, r1, block: None)
-        return out[0]
+        return self._make(self._context(ctx), False)
 
     def _compute_values(self):
-        ctx = self._context()
-        Tout = len(self._time)
-        state = {}
-
-        def block_out(r0, r1, C):
-            if not state:
-                state["scratch"] = ctx.empty((self._largest_block(C), C))
-                state["host"] = np.empty((Tout, C))
-            return state["scratch"].rows(0, r1 - r0)
-
-        def done(r0, r1, block):
-            state["host"][r0:r1] = block.to_host()
-
-        try:
-            self._walk(ctx, block_out, done)
-        finally:
-            if state:
-                state["scratch"].free()
-        return self._in_dims(state["host"], (self._dim,) + self._rest)
+        return self._in_dims(self._make(self._context(), True), (self._dim,) + self._rest)
 
     def __repr__(self):
         return (f"<DisaggregatedGridArray {self.sizes} {self._op} of {self._monthly.sizes} on {self._obs.sizes} "

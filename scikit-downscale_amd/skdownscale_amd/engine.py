@@ -1,6 +1,7 @@
 """Thin object layer over the C ABI: contexts, HBM-resident fields and fitted-state handles."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -1034,15 +1035,45 @@ class Context:
         finally:
             state.close()
 
+    # ---- what the wrappers of the time-axis kernels share ----
+    @staticmethod
+    def _time_field(field, name="field", rows="T"):
+        """a [T, C] field as the time-axis kernels take it: a DeviceArray, or a host array as float32 / float64"""
+        if not isinstance(field, DeviceArray):
+            field = _lib.as_field(field)
+        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{name}: expected a float32 or float64 [{rows}, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        return field
+
+    @contextlib.contextmanager
+    def _uploads(self):
+        """``up(a, dtype)``: ``a`` on the device -- a DeviceArray (or None) as it is, a host array uploaded for the length of the
+        ``with`` block and freed when it ends"""
+        mine = []
+
+        def up(a, dtype=np.float64):
+            if a is None or isinstance(a, DeviceArray):
+                return a
+            mine.append(self.to_device(a, dtype))
+            return mine[-1]
+
+        try:
+            yield up
+        finally:
+            for a in mine:
+                a.free()
+
+    def _same_context(self, who, **arrays):
+        for name, a in arrays.items():
+            if a is not None and a.ctx is not self:
+                raise ValueError(f"sd_downscale: {who}: `{name}` belongs to another context")
+
     # ---- resampling of the time axis (GridArray.resample) ----
     @staticmethod
     def _resample_args(field, offsets, op):
         if op not in _lib.RESAMPLE_OPS:
             raise NotImplementedError(f"resample reduction {op!r}: only 'mean' and 'sum' are implemented")
-        if not isinstance(field, DeviceArray):
-            field = _lib.as_field(field)
-        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
-            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        field = Context._time_field(field)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if offsets.ndim != 1 or len(offsets) < 1:
             raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
@@ -1053,17 +1084,15 @@ class Context:
         offsets: host int64 [M + 1], bin m = rows offsets[m] .. offsets[m + 1] - 1 -> [M, C] float64 DeviceArray (``out``: a [M, C]
         DeviceArray, possibly a view of a wider or longer one).  op 'mean' | 'sum', NaN samples skipped (sd_resample_dev)."""
         field, offsets, code, f32 = self._resample_args(field, offsets, op)
-        if not isinstance(field, DeviceArray):
-            field = self.to_device(field, field.dtype)
         T, Cc = field.shape
         M = len(offsets) - 1
         if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
             raise ValueError(f"sd_downscale: sd_resample: bad sizes (T={T}, C={Cc}, M={M})")
         out = self._result_buffer(out, (M, Cc), True)
-        for name, a in (("field", field), ("out", out)):
-            if a.ctx is not self:
-                raise ValueError(f"sd_downscale: sd_resample: `{name}` belongs to another context")
-        check(self.lib.sd_resample_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(offsets), M, out.vptr, out.ld))
+        with self._uploads() as up:
+            field = up(field, field.dtype)
+            self._same_context("sd_resample", field=field, out=out)
+            check(self.lib.sd_resample_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(offsets), M, out.vptr, out.ld))
         return out
 
     def resample_host(self, field, offsets, op="mean"):
@@ -1088,10 +1117,7 @@ class Context:
                 raise ValueError(f"spell statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SPELL_STATS)}")
         if not 1 <= len(stats) <= len(_lib.SPELL_STATS):
             raise ValueError(f"sd_downscale: sd_spells: nstat = {len(stats)}, expected 1 to {len(_lib.SPELL_STATS)} statistics")
-        if not isinstance(field, DeviceArray):
-            field = _lib.as_field(field)
-        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
-            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        field = Context._time_field(field)
         T, Cc = field.shape
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if offsets.ndim != 1 or len(offsets) < 1:
@@ -1136,23 +1162,12 @@ class Context:
             if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
                 raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
             stride = int(plane_rows) * out.ld
-        mine = []  # (what this call uploads, freed when it is over)
-        try:
-            if not isinstance(field, DeviceArray):
-                field = self.to_device(field, field.dtype)
-                mine.append(field)
-            if table is not None and not isinstance(table, DeviceArray):
-                table = self.to_device(table)
-                mine.append(table)
-            for name, a in (("field", field), ("threshold", table), ("out", out)):
-                if a is not None and a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_spells: `{name}` belongs to another context")
+        with self._uploads() as up:
+            field, table = up(field, field.dtype), up(table)
+            self._same_context("sd_spells", field=field, threshold=table, out=out)
             check(self.lib.sd_spells_dev(self.handle, field.vptr, f32, field.ld, T, Cc, code, thr, None if table is None else table.vptr,
                                          0 if table is None else table.ld, None if group is None else ptr(group),
                                          1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), nstat, out.vptr, out.ld, stride))
-        finally:
-            for a in mine:
-                a.free()
         return out
 
     def spells_host(self, field, op, threshold, offsets, stats, min_length=1, group=None):
@@ -1172,10 +1187,7 @@ class Context:
     def _disagg_args(target, obs, src_row, offsets, op, climo, group):
         if op not in _lib.DISAGG_OPS:
             raise NotImplementedError(f"disaggregation op {op!r}: only 'shift', 'scale_mean' and 'scale_sum' are implemented")
-        if not isinstance(obs, DeviceArray):
-            obs = _lib.as_field(obs)
-        if len(obs.shape) != 2 or obs.dtype not in (np.float32, np.float64):
-            raise ValueError(f"obs: expected a float32 or float64 [To, C] field, got shape {tuple(obs.shape)} of {obs.dtype}")
+        obs = Context._time_field(obs, "obs", "To")
         fields = {"target": target, "climo": climo}
         for name, a in fields.items():
             if a is None:
@@ -1205,31 +1217,17 @@ class Context:
         - 1; climo [G, C] float64 with group: host int32 [M] when the target is an anomaly -> [Tout, C] float64 DeviceArray (``out``:
         a [Tout, C] DeviceArray, possibly a view of a wider or longer one).  op 'shift' | 'scale_mean' | 'scale_sum' (sd_disagg_dev)."""
         target, obs, src_row, offsets, code, f32, climo, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
-        mine = []  # (what this call uploads, freed when it is over)
-
-        def resident(a, dtype):
-            if isinstance(a, DeviceArray):
-                return a
-            mine.append(self.to_device(a, dtype))
-            return mine[-1]
-
         To, Cc = obs.shape
         M, Tout = target.shape[0], len(src_row)
         if min(To, Cc, Tout, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
             raise ValueError(f"sd_downscale: sd_disagg: bad sizes (To={To}, C={Cc}, Tout={Tout}, M={M})")
         out = self._result_buffer(out, (Tout, Cc), True)
-        try:
-            target, obs = resident(target, np.float64), resident(obs, obs.dtype)
-            climo = None if climo is None else resident(climo, np.float64)
-            for name, a in (("target", target), ("obs", obs), ("climo", climo), ("out", out)):
-                if a is not None and a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_disagg: `{name}` belongs to another context")
+        with self._uploads() as up:
+            target, obs, climo = up(target), up(obs, obs.dtype), up(climo)
+            self._same_context("sd_disagg", target=target, obs=obs, climo=climo, out=out)
             check(self.lib.sd_disagg_dev(self.handle, code, target.vptr, target.ld, obs.vptr, f32, obs.ld, To, Cc, ptr(src_row), Tout, ptr(offsets),
                                          M, None if climo is None else climo.vptr, 0 if climo is None else climo.ld,
                                          0 if climo is None else climo.shape[0], None if group is None else ptr(group), out.vptr, out.ld))
-        finally:
-            for a in mine:
-                a.free()
         return out
 
     def disaggregate_host(self, target, obs, src_row, offsets, op="shift", climo=None, group=None):
@@ -1250,10 +1248,7 @@ class Context:
     def _groupby_args(who, field, group, G, op, ops):
         if op not in ops:
             raise NotImplementedError(f"{who} op {op!r}: only {', '.join(repr(k) for k in ops)} are implemented")
-        if not isinstance(field, DeviceArray):
-            field = _lib.as_field(field)
-        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
-            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        field = Context._time_field(field)
         group = np.ascontiguousarray(group, dtype=np.int32)
         if group.shape != (field.shape[0],):
             raise ValueError(f"group: expected one group id per row ({field.shape[0]}), got shape {group.shape}")
@@ -1272,9 +1267,6 @@ class Context:
         of op 'mean' | 'sum' over everything added so far (``out``: a [G, C] DeviceArray, possibly a view of a wider or longer one),
         else None; NaN samples skipped (sd_groupby_reduce_dev).  Any cut of the rows into calls gives the bits of one call."""
         field, group, G, code, f32 = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
-        mine = None
-        if not isinstance(field, DeviceArray):
-            field = mine = self.to_device(field, field.dtype)
         T, Cc = field.shape
         carry = acc is not None
         if carry:
@@ -1284,15 +1276,11 @@ class Context:
         else:
             s, n = self.empty((G, Cc)), self.empty((G, Cc), np.int32)
         out = self._result_buffer(out, (G, Cc), True) if finish else None
-        try:
-            for name, a in (("field", field), ("sum", s), ("count", n), ("out", out)):
-                if a is not None and a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_groupby_reduce: `{name}` belongs to another context")
+        with self._uploads() as up:
+            field = up(field, field.dtype)
+            self._same_context("sd_groupby_reduce", field=field, sum=s, count=n, out=out)
             check(self.lib.sd_groupby_reduce_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, s.vptr, n.vptr, s.ld,
                                                  int(carry), None if out is None else out.vptr, 0 if out is None else out.ld))
-        finally:
-            if mine is not None:
-                mine.free()
         return out, (s, n)
 
     def groupby_reduce_host(self, field, group, G, op="mean"):
@@ -1316,24 +1304,13 @@ class Context:
         field, group, G, code, f32 = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
         if table.shape[1] != field.shape[1]:
             raise ValueError(f"table: expected a float64 [G, {field.shape[1]}] field, got shape {tuple(table.shape)}")
-        mine = []  # (what this call uploads, freed when it is over)
         T, Cc = field.shape
         out = self._result_buffer(out, (T, Cc), True)
-        try:
-            if not isinstance(field, DeviceArray):
-                field = self.to_device(field, field.dtype)
-                mine.append(field)
-            if not isinstance(table, DeviceArray):
-                table = self.to_device(table)
-                mine.append(table)
-            for name, a in (("field", field), ("table", table), ("out", out)):
-                if a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_groupby_apply: `{name}` belongs to another context")
+        with self._uploads() as up:
+            field, table = up(field, field.dtype), up(table)
+            self._same_context("sd_groupby_apply", field=field, table=table, out=out)
             check(self.lib.sd_groupby_apply_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, table.vptr, table.ld, out.vptr,
                                                 out.ld))
-        finally:
-            for a in mine:
-                a.free()
         return out
 
     def groupby_apply_host(self, field, group, table, op):
@@ -1351,10 +1328,7 @@ class Context:
     def _quantile_args(field, q, group, G, method):
         if method not in _lib.QUANTILE_METHODS:
             raise ValueError(f"quantile method {method!r}: expected one of {', '.join(repr(k) for k in _lib.QUANTILE_METHODS)}")
-        if not isinstance(field, DeviceArray):
-            field = _lib.as_field(field)
-        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
-            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        field = Context._time_field(field)
         T, Cc = field.shape
         if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
             raise ValueError(f"sd_downscale: sd_quantile: bad sizes (T={T}, C={Cc})")
@@ -1379,19 +1353,12 @@ class Context:
         one.  Groups of more than 19 456 rows are refused (sd_quantile_dev)."""
         field, q, group, G, code, f32 = self._quantile_args(field, q, group, G, method)
         T, Cc = field.shape
-        mine = None
         out = self._result_buffer(out, (len(q) * G, Cc), True)
-        try:
-            if not isinstance(field, DeviceArray):
-                field = mine = self.to_device(field, field.dtype)
-            for name, a in (("field", field), ("out", out)):
-                if a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_quantile: `{name}` belongs to another context")
+        with self._uploads() as up:
+            field = up(field, field.dtype)
+            self._same_context("sd_quantile", field=field, out=out)
             check(self.lib.sd_quantile_dev(self.handle, code, int(bool(skipna)), field.vptr, f32, field.ld, T, Cc, None if group is None else ptr(group),
                                            G, ptr(q), len(q), out.vptr, out.ld))
-        finally:
-            if mine is not None:
-                mine.free()
         return out
 
     def quantile_host(self, field, q, group=None, G=None, method="linear", skipna=True):
@@ -1410,10 +1377,7 @@ class Context:
     def _rolling_args(field, window, op, back, min_periods, ddof):
         if op not in _lib.ROLLING_OPS:
             raise NotImplementedError(f"rolling op {op!r}: only {', '.join(repr(k) for k in _lib.ROLLING_OPS)} are implemented")
-        if not isinstance(field, DeviceArray):
-            field = _lib.as_field(field)
-        if len(field.shape) != 2 or field.dtype not in (np.float32, np.float64):
-            raise ValueError(f"field: expected a float32 or float64 [T, C] field, got shape {tuple(field.shape)} of {field.dtype}")
+        field = Context._time_field(field)
         T, Cc = field.shape
         if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
             raise ValueError(f"sd_downscale: sd_rolling: bad sizes (T={T}, C={Cc})")
@@ -1435,19 +1399,12 @@ class Context:
         n_out = T - t0 if n_out is None else int(n_out)
         if n_out < 1:
             raise ValueError(f"sd_downscale: sd_rolling: the output rows {t0} .. {t0 + n_out - 1} lie outside the {T} rows of the source")
-        mine = None
         out = self._result_buffer(out, (n_out, Cc), True)
-        try:
-            if not isinstance(field, DeviceArray):
-                field = mine = self.to_device(field, field.dtype)
-            for name, a in (("field", field), ("out", out)):
-                if a.ctx is not self:
-                    raise ValueError(f"sd_downscale: sd_rolling: `{name}` belongs to another context")
+        with self._uploads() as up:
+            field = up(field, field.dtype)
+            self._same_context("sd_rolling", field=field, out=out)
             check(self.lib.sd_rolling_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, window, back, min_periods, ddof, int(bool(wrap)), t0,
                                           n_out, out.vptr, out.ld))
-        finally:
-            if mine is not None:
-                mine.free()
         return out
 
     def rolling_host(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False):

@@ -23,7 +23,8 @@ import numpy as np
 import pandas as pd
 
 from .core import DeferredGridArray, GridArray, chunk_lengths
-from .resample import DEFAULT_SCRATCH_BYTES, ResampledGridArray, host_rows, resident_source
+from .resample import DEFAULT_SCRATCH_BYTES
+from .timesource import _halo_blocks, _time_blocks, takes_whole, walk  # noqa: F401 -- the cutters stay importable from where they lived
 
 OPS = ("mean", "sum")
 APPLY_OPS = {"sub": "-", "add": "+", "mul": "*", "div": "/"}
@@ -49,84 +50,6 @@ def group_labels(coord, field):
         raise ValueError(f"unknown group field {field!r}: expected 'season' or a per-step attribute of pandas' DatetimeIndex such as 'month', "
                          f"'dayofyear', 'year', 'day', 'hour', 'quarter', 'dayofweek'")
     return np.asarray(labels)
-
-
-def _time_blocks(T, max_rows):
-    return [(r0, min(T, r0 + max_rows)) for r0 in range(0, T, max_rows)]
-
-
-def _halo_blocks(T, max_rows, halo):
-    """[0, T) in consecutive runs [r0, r1) with the rows [b0, b1) = [r0 - before, r1 + after) clipped to [0, T) that a window reaching
-    ``halo = (before, after)`` rows around each of its rows touches: ``(r0, r1, b0, b1)`` with at most ``max_rows`` rows in [b0, b1).
-    None where ``max_rows`` has no room for one row beside its halo."""
-    before, after = halo
-    if max_rows >= T:
-        return [(0, T, 0, T)]
-    step = max_rows - before - after
-    if step < 1:
-        return None
-    return [(r0, min(T, r0 + step), max(0, r0 - before), min(T, r0 + step + after)) for r0 in range(0, T, step)]
-
-
-def _lazy_dim(source, also=()):
-    """the dim along which a not yet computed lazy array gives its field as [rows of that dim, cells of the other dims in their order]
-    through ``device_field``; None for any other array.  ``also``: classes taken beside ``ResampledGridArray`` / ``RolledGridArray``"""
-    from .order_stats import TimeQuantileGridArray
-    from .rolling import RolledGridArray
-
-    if isinstance(source, TimeQuantileGridArray):  # (a [G, C] table where a lazy GroupReducedGridArray is taken)
-        return source._row_dim() if GroupReducedGridArray in also and not source.computed else None
-    if not isinstance(source, (ResampledGridArray, RolledGridArray) + tuple(also)) or source.computed:
-        return None
-    return source._gdim if isinstance(source, GroupReducedGridArray) else source._dim
-
-
-def _walk_source(source, dim, ctx, scratch_bytes, visit, halo=None, also_lazy=()):
-    """``visit(r0, r1, block)`` for consecutive blocks of time steps of ``source``: ``block`` is the [r1 - r0, C] DeviceArray of the rows
-    r0 .. r1 - 1 (C = cells of the other dims in their order, the last fastest), valid during the visit.  A lazy ``ResampledGridArray``
-    or ``RolledGridArray`` (and those of ``also_lazy``) is one block, computed in HBM; an unchunked ``coarse.interp_like(obs)`` is
-    regridded, an unchunked ``fine.remap_like(coarse)`` over a host array uploaded and remapped, and any other array uploaded, in blocks
-    of at most ``scratch_bytes`` of device scratch.
-
-    With ``halo = (before, after)`` a block also holds up to ``before`` rows in front of r0 and ``after`` rows behind r1 - 1, clipped to
-    the array: ``visit(r0, r1, block, b0)`` with ``block`` the rows b0 .. of the source, through r1 - 1 + after."""
-    T = source.sizes[dim]
-    if _lazy_dim(source, also_lazy) == dim:
-        field = source.device_field(ctx)
-        try:
-            visit(0, T, field) if halo is None else visit(0, T, field, 0)
-        finally:
-            field.free()
-        return
-    resident = resident_source(source, dim)
-    if resident is not None:
-        rg = resident._regridder_on(ctx)
-        rows, dtype = resident._coarse_stack(), np.dtype(np.float64)
-        C = int(np.prod(rg.shape_out, dtype=np.int64))
-    else:
-        rows = host_rows(source, dim)
-        dtype, C = rows.dtype, rows.shape[1]
-    if min(T, C) < 1:
-        raise ValueError(f"nothing to group: the array has sizes {source.sizes}")
-    max_rows = min(T, max(1, int(scratch_bytes) // (C * dtype.itemsize)))
-    if halo is None:
-        blocks = [(r0, r1, r0, r1) for r0, r1 in _time_blocks(T, max_rows)]
-    else:
-        blocks = _halo_blocks(T, max_rows, halo)
-        if blocks is None:
-            raise ValueError(f"scratch_bytes={int(scratch_bytes)} holds {max_rows} steps of {C} cells: too few for one step and the "
-                             f"{halo[0]} + {halo[1]} steps of its window around it; raise scratch_bytes")
-    scratch = ctx.empty((max(b1 - b0 for _, _, b0, b1 in blocks), C), dtype)
-    try:
-        for r0, r1, b0, b1 in blocks:
-            block = scratch.rows(0, b1 - b0)
-            if resident is not None:
-                rg.regrid(rows[b0:b1], out=block)
-            else:
-                block.copy_from_host(rows[b0:b1])
-            visit(r0, r1, block) if halo is None else visit(r0, r1, block, b0)
-    finally:
-        scratch.free()
 
 
 class GridGroupBy:
@@ -217,6 +140,8 @@ class GroupReducedGridArray(DeferredGridArray):
     """A ``GridArray`` whose ``dim`` is reduced over groups of its steps: the dims of the source with ``dim`` replaced in place by the
     group dim, whose coordinate is the sorted labels."""
 
+    _kind = "group_reduced"
+
     def __init__(self, source, dim, gdim, labels, group, op="mean", ctx=None, scratch_bytes=DEFAULT_SCRATCH_BYTES, chunksizes=None):
         if op not in OPS:
             raise NotImplementedError(f"groupby reduction {op!r}: only mean and sum are implemented")
@@ -266,30 +191,27 @@ class GroupReducedGridArray(DeferredGridArray):
     def _rest_dims(self):
         return tuple(d for d in self.dims if d != self._gdim)
 
+    def _row_dim(self):
+        return self._gdim
+
+    def _field_order(self):
+        return (self._gdim,) + self._rest_dims()
+
     def device_field(self, ctx=None):
         """the reduced field as a [G, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest).  The time
         axis is walked in blocks of at most ``scratch_bytes``; the sums of a group are carried from block to block and every cell's
         samples are added in time order: the result does not depend on the block size."""
         ctx = self._context(ctx)
-        G = len(self._labels)
-        state = {"acc": None, "out": None}
-
-        def visit(r0, r1, block):
-            last = r1 == self._source.sizes[self._dim]
-            state["out"], state["acc"] = ctx.groupby_reduce(block, self._group[r0:r1], G, self._op, acc=state["acc"], finish=last)
-
+        G, T = len(self._labels), self._source.sizes[self._dim]
+        out = acc = None
         try:
-            _walk_source(self._source, self._dim, ctx, self._scratch_bytes, visit)
+            with walk(self._source, self._dim, ctx, self._scratch_bytes, "groupby") as w:
+                for r0, r1, block, _ in w:
+                    out, acc = ctx.groupby_reduce(block, self._group[r0:r1], G, self._op, acc=acc, finish=r1 == T)
         finally:
-            for a in state["acc"] or ():
+            for a in acc or ():
                 a.free()
-        return state["out"]
-
-    def _compute_values(self):
-        field = self.device_field()
-        vals = self._in_dims(field.to_host(), (self._gdim,) + self._rest_dims())
-        field.free()
-        return vals
+        return out
 
     def __repr__(self):
         return (f"<GroupReducedGridArray {self.sizes} {self._op} over {self._dim} -> {self._gdim} of {self._source.sizes} "
@@ -299,6 +221,8 @@ class GroupReducedGridArray(DeferredGridArray):
 class GroupAppliedGridArray(DeferredGridArray):
     """``gb (op) other``: every step of the source combined with the row of ``other`` that carries its label; dims, coords and sizes
     are the source's."""
+
+    _kind = "group_applied"
 
     def __init__(self, gb, other, op, ctx=None):
         if op not in APPLY_OPS:
@@ -345,16 +269,18 @@ class GroupAppliedGridArray(DeferredGridArray):
     def group(self):
         return self._group
 
+    def _row_dim(self):
+        return self._dim
+
+    def _field_order(self):
+        return (self._dim,) + self._rest
+
     def _table(self, ctx):
         """other as a [G', C] float64 DeviceArray in this array's cell order: a lazy reduction or a lazy grouped quantile in that order,
         or a lazy rolling statistic of one, is computed in HBM, any other array goes up once"""
         order = (self._gdim,) + self._rest
         o = self._other
-        from .order_stats import TimeQuantileGridArray
-        from .rolling import RolledGridArray
-
-        lazy = isinstance(o, (GroupReducedGridArray, RolledGridArray, TimeQuantileGridArray)) and _lazy_dim(o, (GroupReducedGridArray,)) == self._gdim
-        if lazy and tuple(o.dims) == order:
+        if takes_whole(o, "table", self._gdim) and tuple(o.dims) == order:
             return o.device_field(ctx)
         v = np.ascontiguousarray((o if tuple(o.dims) == order else o.transpose(*order)).values, dtype=np.float64)
         return ctx.to_device(v.reshape(v.shape[0], -1))
@@ -364,25 +290,14 @@ class GroupAppliedGridArray(DeferredGridArray):
         walked in blocks of time steps as for the reduction; the table is uploaded (or computed) once"""
         ctx = self._context(ctx)
         table = self._table(ctx)
-        T = self._source.sizes[self._dim]
-        out = []
-
-        def visit(r0, r1, block):
-            if not out:
-                out.append(ctx.empty((T, block.shape[1])))
-            ctx.groupby_apply(block, self._group[r0:r1], table, self._op, out=out[0].rows(r0, r1))
-
         try:
-            _walk_source(self._source, self._dim, ctx, self._scratch_bytes, visit)
+            with walk(self._source, self._dim, ctx, self._scratch_bytes, "groupby") as w:
+                out = w.result((self._source.sizes[self._dim], w.cells))
+                for r0, r1, block, _ in w:
+                    ctx.groupby_apply(block, self._group[r0:r1], table, self._op, out=out.rows(r0, r1))
         finally:
             table.free()
-        return out[0]
-
-    def _compute_values(self):
-        field = self.device_field()
-        vals = self._in_dims(field.to_host(), (self._dim,) + self._rest)
-        field.free()
-        return vals
+        return out
 
     def __repr__(self):
         return f"<GroupAppliedGridArray {self.sizes} {self._dim} {APPLY_OPS[self._op]} {self._gdim} computed={self.computed}>"

@@ -18,9 +18,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
 from .core import DeferredGridArray
-from .resample import DEFAULT_SCRATCH_BYTES, host_rows, resident_source
+from .groupby import GridGroupBy
+from .resample import DEFAULT_SCRATCH_BYTES
+from .timesource import walk
 
 METHODS = ("linear", "lower", "higher", "nearest", "midpoint")
 QUANTILE_DIM = "quantile"
@@ -36,56 +37,14 @@ def check_quantiles(q):
     return np.atleast_1d(arr).copy(), arr.ndim == 0
 
 
-def lazy_whole_source(source, dim):
-    """whether ``source`` is a not yet computed lazy array that gives its whole field as [steps of ``dim``, C] through its own
-    ``device_field``: a ``resample`` / ``groupby`` / ``rolling`` result, a ``GroupApplied`` anomaly, ``disaggregate``, or a
-    ``remap_like`` of such a field"""
-    from .disagg import DisaggregatedGridArray
-    from .groupby import GroupAppliedGridArray, GroupReducedGridArray, _lazy_dim
-    from .remap import RemappedGridArray
-
-    if _lazy_dim(source, (GroupReducedGridArray, GroupAppliedGridArray, DisaggregatedGridArray)) == dim:
-        return True
-    return (isinstance(source, RemappedGridArray) and not source.computed and not source._host_source() and len(source.dims) == 3
-            and source.dims[0] == dim and source._lead_dims() == source.dims[:1])
-
-
-def _whole_field(source, dim, ctx, block_bytes):
-    """``source`` as one [T, C] DeviceArray the caller frees (C = cells of the other dims in their order, the last fastest)"""
-    if lazy_whole_source(source, dim):
-        return source.device_field(ctx)
-    T = source.sizes[dim]
-    resident = resident_source(source, dim)
-    if resident is None:
-        rows = host_rows(source, dim)
-        if min(rows.shape) < 1:
-            raise ValueError(f"nothing to sort: the array has sizes {source.sizes}")
-        return ctx.to_device(rows, rows.dtype)
-    rg = resident._regridder_on(ctx)
-    rows = resident._coarse_stack()
-    C = int(np.prod(rg.shape_out, dtype=np.int64))
-    if min(T, C) < 1:
-        raise ValueError(f"nothing to sort: the array has sizes {source.sizes}")
-    field = ctx.empty((T, C))
-    try:
-        step = max(1, int(block_bytes) // (C * 8))
-        for r0 in range(0, T, step):
-            r1 = min(T, r0 + step)
-            rg.regrid(rows[r0:r1], out=field.rows(r0, r1))
-    except BaseException:
-        field.free()
-        raise
-    return field
-
-
 class TimeQuantileGridArray(DeferredGridArray):
     """Quantiles (or the median) of a ``GridArray`` over ``dim``, per cell and, with ``by``, per group of steps.  Dims: the source's
     with ``dim`` dropped (``by=None``) or replaced in place by the group dim, whose coordinate is the sorted labels; an array ``q``
     adds a leading ``"quantile"`` dim whose coordinate is ``q``."""
 
-    def __init__(self, source, dim, q=0.5, by=None, method="linear", skipna=True, name="group", ctx=None, scratch_bytes=DEFAULT_SCRATCH_BYTES):
-        from .groupby import GridGroupBy
+    _kind = "quantile"
 
+    def __init__(self, source, dim, q=0.5, by=None, method="linear", skipna=True, name="group", ctx=None, scratch_bytes=DEFAULT_SCRATCH_BYTES):
         if method != "median" and method not in METHODS:
             raise ValueError(f"quantile method {method!r}: expected one of {', '.join(repr(m) for m in METHODS)}")
         if dim not in source.dims:
@@ -177,23 +136,17 @@ class TimeQuantileGridArray(DeferredGridArray):
         group dim of a scalar-q (or median) grouped result; else None"""
         return self._gdim if self._scalar else None
 
+    def _field_order(self):
+        return (() if self._scalar else (QUANTILE_DIM,)) + (() if self._gdim is None else (self._gdim,)) + self._rest_dims()
+
     def device_field(self, ctx=None):
         """the result as a [Q * G, C] float64 DeviceArray, row ``q * G + g`` (G = 1 without ``by``; C = cells of the other dims in
         their order, the last fastest): [G, C] for one quantile or the median"""
         ctx = self._context(ctx)
-        field = _whole_field(self._source, self._dim, ctx, self._scratch_bytes)
-        try:
-            G = None if self._group is None else len(self._labels)
-            return ctx.quantile(field, self._q, self._group, G, self._method, self._skipna)
-        finally:
-            field.free()
-
-    def _compute_values(self):
-        field = self.device_field()
-        lead = (() if self._scalar else (QUANTILE_DIM,)) + (() if self._gdim is None else (self._gdim,))
-        vals = self._in_dims(field.to_host(), lead + self._rest_dims())
-        field.free()
-        return vals
+        G = None if self._group is None else len(self._labels)
+        with walk(self._source, self._dim, ctx, self._scratch_bytes, "any", whole=True, verb="sort") as w:
+            for _, _, field, _ in w:
+                return ctx.quantile(field, self._q, self._group, G, self._method, self._skipna)
 
     def __repr__(self):
         what = "median" if self._method == "median" else f"quantile q={self.q!r} method={self._method!r}"

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from .core import DEFAULT_FEATURE_DIM, DeferredGridArray, _block_slices, chunk_lengths
+from .timesource import RowProducer
 
 METHODS = ("linear", "nearest")
 PASS_THROUGH_DIMS = ("time", DEFAULT_FEATURE_DIM)  # never interpolated over
@@ -106,6 +107,8 @@ def interp_dims(array, target_names):
 class InterpolatedGridArray(DeferredGridArray):
     """A coarse ``GridArray`` seen on a finer grid: same dims, the two interpolated dims at the target's sizes and coordinates."""
 
+    _kind = "interp"
+
     def __init__(self, source, target_coords, method="linear", ctx=None, chunksizes=None):
         self._source = source
         self._spatial = tuple(d for d in source.dims if d in target_coords)
@@ -173,6 +176,16 @@ class InterpolatedGridArray(DeferredGridArray):
         if ctx is not None and rg._ctx is not ctx:
             rg = self._regridder = Regridder(rg.src_coords, rg.dst_coords, self._method, ctx)
         return rg
+
+    def _block_producer(self, ctx, dim):
+        """the fine field as [steps of ``dim``, C], regridded in HBM block of rows by block of rows: for an array with dims
+        (dim, y, x) that is not chunked in space"""
+        if (len(self.dims) != 3 or self.dims[0] != dim or self._lead_dims() != self.dims[:1]
+                or (self.chunksizes is not None and any(len(self.chunksizes[d]) > 1 for d in self.dims[1:]))):
+            return None
+        rg, stack = self._regridder_on(ctx), self._coarse_stack()
+        return RowProducer(len(stack), int(np.prod(rg.shape_out, dtype=np.int64)), np.dtype(np.float64),
+                           lambda r0, r1, out: rg.regrid(stack[r0:r1], out=out), False)
 
     def _compute_values(self):
         order = self._lead_dims() + self._spatial

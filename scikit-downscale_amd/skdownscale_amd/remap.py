@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _lib
 from .core import DeferredGridArray
+from .timesource import RowProducer, takes_whole, upload_rows, walk
 
 WEIGHTS = ("area", "plain")
 LATITUDE_NAMES = ("lat", "latitude")
@@ -136,21 +137,10 @@ class ConservativeRemapper:
         if field.ndim not in (2, 3) or field.shape[0] < 1 or field.size != field.shape[0] * cells:
             raise ValueError(f"field: expected a [T, {self.shape_in[0]}, {self.shape_in[1]}] field, got shape {field.shape}")
         field = field.reshape(field.shape[0], cells)
-        T = field.shape[0]
-        rows = max(1, int(scratch_bytes) // (cells * field.dtype.itemsize))
-        if rows >= T:
-            return self.state.apply(field, min_valid, out=out)
-        ctx = self.ctx
-        out = ctx._result_buffer(out, (T, int(np.prod(self.shape_out, dtype=np.int64))), True)
-        scratch = ctx.empty((rows, cells), field.dtype)
-        try:
-            for r0 in range(0, T, rows):
-                r1 = min(T, r0 + rows)
-                block = scratch.rows(0, r1 - r0)
-                block.copy_from_host(field[r0:r1])
+        with walk(upload_rows(field), None, self.ctx, scratch_bytes) as w:
+            out = w.result((field.shape[0], int(np.prod(self.shape_out, dtype=np.int64))), out)
+            for r0, r1, block, _ in w:
                 self.state.apply(block, min_valid, out=out.rows(r0, r1))
-        finally:
-            scratch.free()
         return out
 
     __call__ = remap
@@ -170,31 +160,10 @@ class ConservativeRemapper:
             self._state = None
 
 
-class _BlockRemap:
-    """what the walkers of the time axis (``resample``, ``groupby``, ``rolling``) ask of a source that is produced in HBM block by
-    block: ``shape_out`` and ``regrid(rows, out=block)``"""
-
-    def __init__(self, remapper, min_valid, scratch_bytes):
-        self._remapper, self._min_valid, self._scratch_bytes = remapper, min_valid, scratch_bytes
-        self.shape_out = remapper.shape_out
-
-    def regrid(self, rows, out=None):
-        return self._remapper.remap(rows, self._min_valid, out=out, scratch_bytes=self._scratch_bytes)
-
-
-def _lazy_time_source(src, spatial):
-    """``src`` when it is a not yet computed lazy time-axis result with dims (dim, y, x) that gives its field as [rows, ny * nx]
-    through ``device_field``; else None"""
-    from .disagg import DisaggregatedGridArray
-    from .groupby import GroupAppliedGridArray, GroupReducedGridArray, _lazy_dim
-
-    if len(src.dims) != 3 or tuple(src.dims[1:]) != tuple(spatial):
-        return None
-    return src if _lazy_dim(src, (GroupReducedGridArray, GroupAppliedGridArray, DisaggregatedGridArray)) == src.dims[0] else None
-
-
 class RemappedGridArray(DeferredGridArray):
     """A fine ``GridArray`` seen on a coarser grid: same dims, the two remapped dims at the target's sizes and coordinates."""
+
+    _kind = "remap"
 
     def __init__(self, source, target_coords, weights="area", latitude="auto", min_valid=0.5, src_bounds=None, dst_bounds=None, ctx=None,
                  scratch_bytes=None):
@@ -263,15 +232,22 @@ class RemappedGridArray(DeferredGridArray):
         v = _lib.as_field((src if tuple(src.dims) == order else src.transpose(*order)).values)
         return v.reshape((-1,) + v.shape[-2:])
 
-    # (the names under which the walkers of the time axis know a source that is produced in HBM: resample.resident_source)
-    _coarse_stack = _source_stack
-
-    def _regridder_on(self, ctx):
-        return _BlockRemap(self._remapper_on(ctx), self._min_valid, self._scratch_bytes)
-
     def _remapper_on(self, ctx):
         self._remapper = self._remapper.on(ctx)
         return self._remapper
+
+    def _row_dim(self):
+        """the leading dim where the coarse field is made in HBM from a lazy source's field"""
+        return self.dims[0] if len(self.dims) == 3 and not self._host_source() and self._lead_dims() == self.dims[:1] else None
+
+    def _block_producer(self, ctx, dim):
+        """the coarse field as [steps of ``dim``, C] from a host source with dims (dim, y, x): a block of fine rows is uploaded and
+        remapped into the block"""
+        if self.computed or not self._host_source() or len(self.dims) != 3 or self.dims[0] != dim or self._lead_dims() != self.dims[:1]:
+            return None
+        rm, stack = self._remapper_on(ctx), self._source_stack()
+        return RowProducer(len(stack), int(np.prod(rm.shape_out, dtype=np.int64)), np.dtype(np.float64),
+                           lambda r0, r1, out: rm.remap(stack[r0:r1], self._min_valid, out=out, scratch_bytes=self._scratch_bytes), False)
 
     def device_field(self, ctx=None):
         """the coarse field as a [T, C] float64 DeviceArray (C = cells of the two remapped dims, the second fastest); the array must be
@@ -281,13 +257,11 @@ class RemappedGridArray(DeferredGridArray):
             raise ValueError(f"device_field needs dims (time, y, x); this array has {self.dims}")
         ctx = self._context(ctx)
         rm = self._remapper_on(ctx)
-        lazy = None if self._host_source() else _lazy_time_source(self._source, self._spatial)
-        if lazy is not None:
-            fine = lazy.device_field(ctx)
-            try:
-                return rm.remap(fine, self._min_valid)
-            finally:
-                fine.free()
+        src = self._source
+        if len(src.dims) == 3 and tuple(src.dims[1:]) == self._spatial and takes_whole(src, "remap", src.dims[0]):
+            with walk(src, src.dims[0], ctx, self._scratch_bytes, "remap") as w:
+                for _, _, fine, _ in w:
+                    return rm.remap(fine, self._min_valid)
         return rm.remap(self._source_stack(), self._min_valid, scratch_bytes=self._scratch_bytes)
 
     def _compute_values(self):
@@ -296,9 +270,10 @@ class RemappedGridArray(DeferredGridArray):
             field = self.device_field()
         else:
             field = self._remapper_on(self._context()).remap(self._source_stack(), self._min_valid, scratch_bytes=self._scratch_bytes)
-        vals = self._in_dims(field.to_host(), order)
-        field.free()
-        return vals
+        try:
+            return self._in_dims(field.to_host(), order)
+        finally:
+            field.free()
 
     def __repr__(self):
         return (f"<RemappedGridArray {self.sizes} from {self._source.sizes} weights={self._remapper.weights!r} "

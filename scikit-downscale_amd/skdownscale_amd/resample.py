@@ -17,8 +17,8 @@ from __future__ import annotations
 import numpy as np
 import pandas as pd
 
-from . import _lib
 from .core import DeferredGridArray, chunk_lengths
+from .timesource import walk
 
 OPS = ("mean", "sum")
 DEFAULT_SCRATCH_BYTES = 1 << 30
@@ -46,48 +46,6 @@ def time_bins(time, rule, **kw):
     if offsets[-1] != len(index):
         raise ValueError(f"the resampler kept {int(offsets[-1])} of the {len(index)} samples (NaT in the time coordinate?)")
     return counts.index, offsets
-
-
-def _bin_blocks(offsets, max_rows):
-    """the bins in consecutive runs [m0, m1) of at most ``max_rows`` samples -- at least one bin, however long, and at least one
-    sample (a run of empty bins joins its neighbour)"""
-    M = len(offsets) - 1
-    blocks, m0 = [], 0
-    for m in range(1, M + 1):
-        have = offsets[m] - offsets[m0]
-        if m == M or (have > 0 and offsets[m + 1] - offsets[m0] > max_rows):
-            blocks.append((m0, m))
-            m0 = m
-    if len(blocks) > 1 and offsets[blocks[-1][1]] == offsets[blocks[-1][0]]:
-        (a, _), (_, b) = blocks[-2], blocks[-1]
-        blocks[-2:] = [(a, b)]
-    return blocks
-
-
-def resident_source(src, dim):
-    """``src`` when it is an unchunked ``coarse.interp_like(obs)`` with dims (dim, y, x): its fine field can be produced in HBM, block
-    of rows by block of rows (``src._regridder_on(ctx).regrid(src._coarse_stack()[r0:r1], out=block)``); else None.  The rule of every
-    lazy array that walks the time axis of a source (``ResampledGridArray``, the groupby arrays).  Likewise ``src`` when it is a not
-    yet computed ``fine.remap_like(coarse)`` with those dims over a host array: a block of fine rows is uploaded and remapped into
-    the block."""
-    from .regrid import InterpolatedGridArray
-    from .remap import RemappedGridArray
-
-    if isinstance(src, RemappedGridArray) and (src.computed or not src._host_source()):
-        return None
-    if (not isinstance(src, (InterpolatedGridArray, RemappedGridArray)) or len(src.dims) != 3 or src.dims[0] != dim
-            or src._lead_dims() != src.dims[:1]):
-        return None
-    if src.chunksizes is not None and any(len(src.chunksizes[d]) > 1 for d in src.dims[1:]):
-        return None
-    return src
-
-
-def host_rows(src, dim):
-    """``src`` as a host [T, C] array, ``dim`` first and the other dims flattened in their order; float32 stays float32"""
-    rest = tuple(d for d in src.dims if d != dim)
-    v = _lib.as_field((src.transpose(dim, *rest) if src.dims[0] != dim else src).values)
-    return v.reshape(v.shape[0], -1)
 
 
 class GridResample:
@@ -129,6 +87,8 @@ class GridResample:
 class ResampledGridArray(DeferredGridArray):
     """A ``GridArray`` whose ``dim`` is reduced over pandas' bins of ``rule``: same dims, ``dim`` at the number of bins with the bin
     labels as its coordinate."""
+
+    _kind = "resample"
 
     def __init__(self, source, dim, rule, op="mean", kw=None, ctx=None, scratch_bytes=DEFAULT_SCRATCH_BYTES, chunksizes=None, bins=None):
         if op not in OPS:
@@ -180,50 +140,24 @@ class ResampledGridArray(DeferredGridArray):
     def _rest_dims(self):
         return tuple(d for d in self.dims if d != self._dim)
 
-    def _resident_source(self):
-        return resident_source(self._source, self._dim)
+    def _row_dim(self):
+        return self._dim
 
-    def _host_rows(self):
-        return host_rows(self._source, self._dim)
+    def _field_order(self):
+        return (self._dim,) + self._rest_dims()
 
     def device_field(self, ctx=None):
         """the reduced field as an [M, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest).  The
-        time axis is walked in blocks of whole bins of at most ``scratch_bytes``: a block of ``coarse.interp_like(obs)`` is regridded
-        into device scratch, a block of a host array is uploaded into it (float32 as float32), and reduced into its rows of the
-        result.  A bin is always reduced within one block, in time order: the result does not depend on the block size."""
+        time axis is walked in blocks of whole bins of at most ``scratch_bytes`` (``timesource.walk``) and every block reduced into
+        its rows of the result.  A bin is always reduced within one block, in time order: the result does not depend on the block
+        size."""
         ctx = self._context(ctx)
         off = self._offsets
-        M = len(off) - 1
-        resident = self._resident_source()
-        if resident is not None:
-            rg = resident._regridder_on(ctx)
-            rows, dtype = resident._coarse_stack(), np.dtype(np.float64)
-            C = int(np.prod(rg.shape_out, dtype=np.int64))
-        else:
-            rows = self._host_rows()
-            dtype, C = rows.dtype, rows.shape[1]
-        if C < 1:
-            raise ValueError(f"nothing to resample: the array has sizes {self._source.sizes}")
-        max_rows = max(1, self._scratch_bytes // (C * dtype.itemsize))
-        blocks = _bin_blocks(off, max_rows)
-        scratch = ctx.empty((max(int(off[b] - off[a]) for a, b in blocks), C), dtype)
-        out = ctx.empty((M, C))
-        for a, b in blocks:
-            r0, r1 = int(off[a]), int(off[b])
-            block = scratch.rows(0, r1 - r0)
-            if resident is not None:
-                rg.regrid(rows[r0:r1], out=block)
-            else:
-                block.copy_from_host(rows[r0:r1])
-            ctx.resample(block, off[a:b + 1] - r0, self._op, out=out.rows(a, b))
-        scratch.free()
+        with walk(self._source, self._dim, ctx, self._scratch_bytes, "resample", bins=off, verb="resample") as w:
+            out = w.result((len(off) - 1, w.cells))
+            for a, b, block, r0 in w:
+                ctx.resample(block, off[a:b + 1] - r0, self._op, out=out.rows(a, b))
         return out
-
-    def _compute_values(self):
-        field = self.device_field()
-        vals = self._in_dims(field.to_host(), (self._dim,) + self._rest_dims())
-        field.free()
-        return vals
 
     def __repr__(self):
         return (f"<ResampledGridArray {self.sizes} {self._op} over {self._dim}={self._rule!r} of {self._source.sizes} "

@@ -6,7 +6,7 @@ an n-day precipitation accumulation, the running mean and spread of a future ser
 ``GridRolling`` is what ``GridArray.rolling`` returns and ``RolledGridArray`` what its ``mean()`` / ``sum()`` / ``var()`` / ``std()``
 return: the source and the window, computed when the field is asked for -- on the host through ``values``, or as a ``[T, C]``
 ``DeviceArray`` through ``device_field``.  The source is walked in blocks of time steps that carry the rows their windows reach
-(``groupby._walk_source`` with a halo): a block of ``coarse.interp_like(obs)`` is regridded into device scratch, a block of a host
+(``timesource.walk`` with a halo): a block of ``coarse.interp_like(obs)`` is regridded into device scratch, a block of a host
 array is uploaded into it (float32 as float32), and a lazy ``resample`` / ``groupby`` / ``rolling`` result is taken from its own
 ``device_field``; none of them crosses PCIe as a fine float64 field.
 
@@ -22,6 +22,7 @@ from __future__ import annotations
 
 from .core import DeferredGridArray, chunk_lengths
 from .resample import DEFAULT_SCRATCH_BYTES
+from .timesource import walk
 
 OPS = ("mean", "sum", "var", "std")
 # what pandas' rolling offers beyond the four statistics the engine has: asked for by name, refused by name
@@ -107,6 +108,8 @@ class RolledGridArray(DeferredGridArray):
     """A ``GridArray`` whose every step is a statistic of the window of steps around it along ``dim``: dims, coords and sizes are the
     source's."""
 
+    _kind = "rolling"
+
     def __init__(self, source, dim, window, op="mean", center=False, min_periods=None, ddof=1, wrap=False, ctx=None,
                  scratch_bytes=DEFAULT_SCRATCH_BYTES, chunksizes=None):
         if op not in OPS:
@@ -155,42 +158,30 @@ class RolledGridArray(DeferredGridArray):
     def _rest_dims(self):
         return tuple(d for d in self.dims if d != self._dim)
 
+    def _row_dim(self):
+        return self._dim
+
+    def _field_order(self):
+        return (self._dim,) + self._rest_dims()
+
     def device_field(self, ctx=None):
         """the field as a [T, C] float64 DeviceArray (C = cells of the other dims in their order, the last fastest).  The source is
         walked in blocks of time steps of at most ``scratch_bytes``, each with the steps its windows reach before and behind it; a
         window is evaluated from its own samples only, so the result does not depend on the block size.  ``wrap`` needs the whole
         axis in one block."""
-        from .groupby import GroupAppliedGridArray, GroupReducedGridArray, _walk_source
-
         ctx = self._context(ctx)
         T = self._source.sizes[self._dim]
         back = window_back(self._window, self._center)
-        out = []
-
-        def visit(r0, r1, block, b0):
-            if not out:
-                out.append(ctx.empty((T, block.shape[1])))
-            if self._wrap and (r0, r1, block.shape[0]) != (0, T, T):
-                raise ValueError(f"wrap=True needs the {T} steps of dim {self._dim!r} in one block: scratch_bytes={self._scratch_bytes} holds "
-                                 f"{block.shape[0]} of them; raise scratch_bytes")
-            # the block holds every row a window of r0 .. r1 - 1 touches inside the array: clipping to the block is clipping to the array
-            ctx.rolling(block, self._window, self._op, back, self._min_periods, self._ddof, self._wrap, t0=r0 - b0, n_out=r1 - r0,
-                        out=out[0].rows(r0, r1))
-
-        try:
-            _walk_source(self._source, self._dim, ctx, self._scratch_bytes, visit, halo=(back, self._window - 1 - back),
-                         also_lazy=(GroupReducedGridArray, GroupAppliedGridArray))
-        except BaseException:
-            for a in out:
-                a.free()
-            raise
-        return out[0]
-
-    def _compute_values(self):
-        field = self.device_field()
-        vals = self._in_dims(field.to_host(), (self._dim,) + self._rest_dims())
-        field.free()
-        return vals
+        with walk(self._source, self._dim, ctx, self._scratch_bytes, "rolling", halo=(back, self._window - 1 - back)) as w:
+            out = w.result((T, w.cells))
+            for r0, r1, block, b0 in w:
+                if self._wrap and (r0, r1, block.shape[0]) != (0, T, T):
+                    raise ValueError(f"wrap=True needs the {T} steps of dim {self._dim!r} in one block: scratch_bytes={self._scratch_bytes} "
+                                     f"holds {block.shape[0]} of them; raise scratch_bytes")
+                # the block holds every row a window of r0 .. r1 - 1 touches inside the array: clipping to the block is clipping to the array
+                ctx.rolling(block, self._window, self._op, back, self._min_periods, self._ddof, self._wrap, t0=r0 - b0, n_out=r1 - r0,
+                            out=out.rows(r0, r1))
+        return out
 
     def __repr__(self):
         return (f"<RolledGridArray {self.sizes} {self._op} over {self._dim}={self._window} center={self._center} wrap={self._wrap} "

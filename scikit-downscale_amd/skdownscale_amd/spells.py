@@ -36,7 +36,9 @@ import numpy as np
 
 from . import _lib
 from .core import DeferredGridArray, GridArray
-from .resample import DEFAULT_SCRATCH_BYTES, _bin_blocks, host_rows, resident_source, time_bins
+from .groupby import GridGroupBy, GroupAppliedGridArray
+from .resample import DEFAULT_SCRATCH_BYTES, time_bins
+from .timesource import walk
 
 OPS = tuple(_lib.SPELL_OPS)
 STATS = tuple(_lib.SPELL_STATS)
@@ -64,8 +66,6 @@ class GridCondition:
     same condition over pandas' bins; ``count()``, ``longest_spell()``, ... -> ``SpellGridArray``."""
 
     def __init__(self, source, op, threshold, dim="time", by=None, name="group", scratch_bytes=DEFAULT_SCRATCH_BYTES, bins=None, rule=None):
-        from .groupby import GridGroupBy, GroupAppliedGridArray
-
         if op not in OPS:
             raise ValueError(f"where op {op!r}: expected one of {', '.join(repr(o) for o in OPS)}")
         if dim not in source.dims:
@@ -263,60 +263,25 @@ class SpellGridArray(DeferredGridArray):
         of whole bins of at most ``scratch_bytes`` as ``ResampledGridArray.device_field`` walks it; a lazy source that gives its field
         through ``device_field`` is taken whole.  A bin is always evaluated within one block: the result does not depend on the block
         size, and one bin over the whole axis needs the whole field in HBM."""
-        from .order_stats import lazy_whole_source
-
         ctx = self._context(ctx)
         c = self._cond
-        src, dim, off = c._source, c._dim, np.asarray(c.offsets, dtype=np.int64)
-        M, nstat = len(off) - 1, len(self._stats)
+        off = np.asarray(c.offsets, dtype=np.int64)
+        M = len(off) - 1
         thr, group = self._threshold_on(ctx)
         try:
-            if lazy_whole_source(src, dim):
-                field = src.device_field(ctx)
-                try:
-                    return ctx.spells(field, c._op, thr, off, self._stats, self._min_length, group)
-                finally:
-                    field.free()
-            resident = resident_source(src, dim)
-            if resident is not None:
-                rg = resident._regridder_on(ctx)
-                rows, dtype = resident._coarse_stack(), np.dtype(np.float64)
-                C = int(np.prod(rg.shape_out, dtype=np.int64))
-            else:
-                rows = host_rows(src, dim)
-                dtype, C = rows.dtype, rows.shape[1]
-            if C < 1:
-                raise ValueError(f"nothing to count: the array has sizes {src.sizes}")
-            blocks = _bin_blocks(off, max(1, c._scratch_bytes // (C * dtype.itemsize)))
-            scratch = ctx.empty((max(int(off[b] - off[a]) for a, b in blocks), C), dtype)
-            out = ctx.empty((nstat * M, C))
-            try:
-                for a, b in blocks:
-                    r0, r1 = int(off[a]), int(off[b])
-                    block = scratch.rows(0, r1 - r0)
-                    if resident is not None:
-                        rg.regrid(rows[r0:r1], out=block)
-                    else:
-                        block.copy_from_host(rows[r0:r1])
-                    ctx.spells(block, c._op, thr, off[a:b + 1] - r0, self._stats, self._min_length, None if group is None else group[r0:r1],
-                               out=out.rows(a, b), plane_rows=M)
-            except BaseException:
-                out.free()
-                raise
-            finally:
-                scratch.free()
+            with walk(c._source, c._dim, ctx, c._scratch_bytes, "any", bins=off, verb="count") as w:
+                out = w.result((len(self._stats) * M, w.cells))
+                for a, b, block, r0 in w:
+                    ctx.spells(block, c._op, thr, off[a:b + 1] - r0, self._stats, self._min_length,
+                               None if group is None else group[r0:int(off[b])], out=out.rows(a, b), plane_rows=M)
             return out
         finally:
             if not isinstance(thr, float):
                 thr.free()
 
-    def _compute_values(self):
+    def _field_order(self):
         c = self._cond
-        field = self.device_field()
-        lead = ((INDEX_DIM,) if self._indexed else ()) + ((c._dim,) if c._bins is not None else ())
-        vals = self._in_dims(field.to_host(), lead + c._rest)
-        field.free()
-        return vals
+        return ((INDEX_DIM,) if self._indexed else ()) + ((c._dim,) if c._bins is not None else ()) + c._rest
 
     def __repr__(self):
         what = ", ".join(self._stats) + (f" (min_length={self._min_length})" if self._min_length != 1 else "")

@@ -169,13 +169,15 @@ def test_the_grouped_spellings_stay_refused(grid):
 
 def test_a_grouped_quantile_is_taken_where_a_lazy_reduction_is(grid):
     """as ``other`` of ``gb - other`` and as the source of a rolling window over the group dim: nothing is computed when the chain is made"""
-    from skdownscale_amd.groupby import GroupReducedGridArray, _lazy_dim
+    from skdownscale_amd.timesource import TAKEN_WHOLE, takes_whole
 
     a = grid.transpose("time", "lat", "lon")
     thr = a.quantile(0.9, "time", by="time.dayofyear")
-    assert _lazy_dim(thr, (GroupReducedGridArray,)) == "dayofyear" and _lazy_dim(thr) is None
-    assert _lazy_dim(a.quantile([0.9], "time", by="time.dayofyear"), (GroupReducedGridArray,)) is None  # [Q * G, C]: not a [G, C] table
-    assert _lazy_dim(a.quantile(0.9), (GroupReducedGridArray,)) is None
+    with_reductions = [c for c, kinds in TAKEN_WHOLE.items() if "group_reduced" in kinds]  # (who takes a lazy reduction takes this)
+    assert thr._row_dim() == "dayofyear" and all(takes_whole(thr, c, "dayofyear") for c in with_reductions)
+    assert not any(takes_whole(thr, c, "dayofyear") for c in TAKEN_WHOLE if c not in with_reductions)
+    assert a.quantile([0.9], "time", by="time.dayofyear")._row_dim() is None  # [Q * G, C]: not a [G, C] table
+    assert a.quantile(0.9)._row_dim() is None
     smooth = thr.rolling(dayofyear=5, center=True, wrap=True).mean()
     anom = a.groupby("time.month") - a.median("time", by="time.month")
     assert not thr.computed and not smooth.computed and not anom.computed

@@ -4,13 +4,14 @@
   tests/golden/g24_regrid.npz and against a live scipy where one is installed; it agrees with RegularGridInterpolator to 1e-14.
 * ``Regridder`` refuses bad coordinates with its messages before any engine call.
 * ``GridArray.interp_like`` / ``interp``: dims, coords, pass-through of ``time`` and ``variable``, blocks, slices -- on an engine
-  replaced by the oracle (a stand-in for ``Context.regrid_create``), so nothing here needs the library."""
+  replaced by the oracle (tests/_oracle_engine.py), so nothing here needs the library."""
 import os
 
 import numpy as np
 import pytest
 
 import _regrid_oracle as ro
+from _oracle_engine import OracleState, engine  # noqa: F401  (engine: the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g24_regrid.npz")
@@ -106,48 +107,6 @@ def test_regridder_refuses_bad_coordinates():
 
 
 # ---- GridArray.interp_like on a stand-in engine -----------------------------------------------------------------------------------
-class OracleState:
-    """what Context.regrid_create returns, computed by the oracle on the host"""
-
-    created = 0
-
-    def __init__(self, sy, sx, dy, dx, method):
-        self.args = (np.array(sy), np.array(sx), np.array(dy), np.array(dx), method)
-        OracleState.created += 1
-
-    def apply(self, src, out=None):
-        assert src.ndim == 3 and src.dtype in (np.float32, np.float64) and src.flags.c_contiguous
-        sy, sx, dy, dx, method = self.args
-        fine = ro.regrid(src, sy, sx, dy, dx, method).reshape(src.shape[0], -1)
-
-        class Field:
-            shape = fine.shape
-
-            @staticmethod
-            def to_host():
-                return fine
-
-        return Field
-
-    def close(self):
-        pass
-
-
-class OracleContext:
-    def regrid_create(self, sy, sx, dy, dx, method="linear"):
-        return OracleState(sy, sx, dy, dx, method)
-
-
-@pytest.fixture
-def engine(monkeypatch):
-    from skdownscale_amd import engine
-
-    ctx = OracleContext()
-    monkeypatch.setattr(engine, "default_context", lambda: ctx)
-    OracleState.created = 0
-    return ctx
-
-
 def coarse_and_obs(T=4, dtype=np.float64):
     from skdownscale_amd import GridArray
 

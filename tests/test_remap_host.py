@@ -6,7 +6,7 @@
   ``np.longdouble`` within ``(ky + kx + 4) * 2^-53 * sum w|v| / den``.
 * ``cell_bounds`` and ``ConservativeRemapper``: inference of bounds, the area / plain / latitude choices, explicit bounds, refusals.
 * ``GridArray.remap_like``: dims, coords, laziness, ``isel``, the chains into ``resample`` / ``groupby`` / ``rolling`` and block
-  independence -- on an engine replaced by the oracles (a stand-in for ``Context``), so nothing here needs the library."""
+  independence -- on an engine replaced by the oracles (tests/_oracle_engine.py), so nothing here needs the library."""
 import numpy as np
 import pandas as pd
 import pytest
@@ -15,6 +15,7 @@ import _groupby_oracle as go
 import _remap_oracle as mo
 import _resample_oracle as so
 import _rolling_oracle as rol
+from _oracle_engine import engine  # noqa: F401  (the fixture)
 
 
 def same_bits(a, b):
@@ -163,97 +164,6 @@ def test_remapper_refusals():
 
 
 # ---- GridArray.remap_like on a stand-in engine ------------------------------------------------------------------------------------------
-class FakeArray:
-    """a DeviceArray stand-in over a NumPy buffer"""
-
-    def __init__(self, a, ctx):
-        self.a, self.ctx = a, ctx
-
-    shape = property(lambda self: self.a.shape)
-    dtype = property(lambda self: self.a.dtype)
-    ld = property(lambda self: self.a.strides[0] // self.a.itemsize)
-
-    def rows(self, r0, r1):
-        assert 0 <= r0 < r1 <= self.a.shape[0]
-        return FakeArray(self.a[r0:r1], self.ctx)
-
-    def copy_from_host(self, x):
-        assert x.shape == self.a.shape
-        self.ctx.uploads.append((x.shape[0], x.dtype))
-        self.a[...] = x
-        return self
-
-    def to_host(self):
-        return self.a.copy()
-
-    def free(self):
-        pass
-
-
-class OracleRemapState:
-    def __init__(self, ctx, bounds):
-        self.ctx, self.bounds = ctx, [np.array(b) for b in bounds]
-        ctx.created += 1
-
-    def apply(self, field, min_valid=0.5, out=None):
-        if isinstance(field, FakeArray):
-            v = field.a
-        else:
-            assert field.dtype in (np.float32, np.float64) and field.flags.c_contiguous
-            self.ctx.uploads.append((field.shape[0], field.dtype))
-            v = field
-        ny, nx = len(self.bounds[0]) - 1, len(self.bounds[1]) - 1
-        coarse = mo.remap(v.reshape(v.shape[0], ny, nx), *self.bounds, min_valid).reshape(v.shape[0], -1)
-        out = self.ctx._result_buffer(out, coarse.shape, True)
-        out.a[...] = coarse
-        return out
-
-    def close(self):
-        pass
-
-
-class OracleContext:
-    """what the lazy arrays ask of a Context, computed by the oracles on the host"""
-
-    def __init__(self):
-        self.created, self.uploads = 0, []
-
-    def empty(self, shape, dtype=np.float64):
-        return FakeArray(np.full(shape, -777.0, dtype=dtype), self)
-
-    def to_device(self, a, dtype=np.float64):
-        return FakeArray(np.array(a, dtype=dtype), self)
-
-    def _result_buffer(self, out, shape, on_device):
-        assert out is None or tuple(out.shape) == tuple(shape)
-        return self.empty(shape) if out is None else out
-
-    def remap_create(self, syb, sxb, dyb, dxb):
-        return OracleRemapState(self, (syb, sxb, dyb, dxb))
-
-    def resample(self, field, offsets, op="mean", out=None):
-        out.a[...] = so.resample(field.a, offsets, op)
-        return out
-
-    def groupby_reduce(self, field, group, G, op="mean", acc=None, out=None, finish=True):
-        s, n = go.accumulate(field.a, group, G, None if acc is None else (acc[0].a, acc[1].a))
-        return (FakeArray(go.finish((s, n), op), self) if finish else None), (FakeArray(s, self), FakeArray(n, self))
-
-    def rolling(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False, t0=0, n_out=None, out=None):
-        out.a[...] = rol.rolling(field.a, window, op, min_periods=min_periods, ddof=ddof, wrap=wrap, back=back)[t0:t0 + n_out]
-        return out
-
-
-@pytest.fixture
-def engine(monkeypatch):
-    from skdownscale_amd import core, engine
-
-    ctx = OracleContext()
-    monkeypatch.setattr(engine, "default_context", lambda: ctx)
-    monkeypatch.setattr(core, "default_context", lambda: ctx)
-    return ctx
-
-
 def obs_and_gcm(T=90, dtype=np.float64):
     from skdownscale_amd import GridArray
 

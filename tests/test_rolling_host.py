@@ -1,5 +1,5 @@
 """CPU, no engine: the host side of GridArray.rolling (skdownscale_amd/rolling.py) -- the window arithmetic, the lazy surface, the
-refusals and their messages, the halo block cutter of groupby._walk_source -- and the NumPy oracle (tests/_rolling_oracle.py) against
+refusals and their messages, the halo block cutter of timesource.walk -- and the NumPy oracle (tests/_rolling_oracle.py) against
 what pandas made of the golden cases (tests/golden/g27_rolling.npz, written by tests/golden/make_golden_rolling.py with pandas 2.3.3).
 
 Tolerance (measured, tests/_rolling_oracle.py: pandas' online update carries rounding from earlier windows, so no bound follows from a
@@ -135,7 +135,7 @@ def test_refusals_and_their_messages():
 @pytest.mark.parametrize("halo", [(0, 0), (8, 0), (4, 4), (15, 14), (0, 30), (30, 0)])
 @pytest.mark.parametrize("T", [1, 37, 120, 400])
 def test_halo_blocks_cover_every_row_once_and_hold_every_window(T, halo):
-    from skdownscale_amd.groupby import _halo_blocks, _time_blocks
+    from skdownscale_amd.timesource import _halo_blocks, _time_blocks
 
     before, after = halo
     for max_rows in (1, before + after, before + after + 1, before + after + 7, 64, T - 1, T, T + 5):
