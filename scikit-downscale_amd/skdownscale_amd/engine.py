@@ -82,11 +82,21 @@ class DeviceArray:
         return self
 
 
+def vptr(a):
+    """device pointer of a DeviceArray (or None)"""
+    return None if a is None else a.vptr
+
+
 class _State:
-    def __init__(self, ctx, handle, destroy):
+    """A handle of the library.  ``ABI`` is the prefix of the family's entry points (``ABI_info``, ``ABI_destroy``), ``INFO`` the
+    (key, ctype) of what ``ABI_info`` gives, in the order of its arguments."""
+    ABI = None
+    INFO = ()
+
+    def __init__(self, ctx, handle):
         self.ctx = ctx
         self.handle = handle
-        self._fin = weakref.finalize(self, _State._destroy, ctx, handle, destroy)
+        self._fin = weakref.finalize(self, _State._destroy, ctx, handle, getattr(ctx.lib, self.ABI + "_destroy"))
 
     @staticmethod
     def _destroy(ctx, handle, destroy):
@@ -104,14 +114,33 @@ class _State:
             raise ValueError("state has been destroyed")
         return C.c_void_p(self.handle)
 
+    def info(self):
+        v = [ctype() for _, ctype in self.INFO]
+        check(getattr(self.ctx.lib, self.ABI + "_info")(self.vptr, *[C.byref(x) for x in v]))
+        return {key: x.value for (key, _), x in zip(self.INFO, v)}
+
+
+class _FittedState(_State):
+    """A state whose ``ABI_export`` takes ``PLANES`` optional outputs (NULL: not wanted) and then the cell status [C]."""
+    PLANES = 0
+
+    def _export(self, cells, *planes):
+        status = np.empty(cells, dtype=np.int32)
+        check(getattr(self.ctx.lib, self.ABI + "_export")(self.vptr, *[ptr(p) for p in planes], ptr(status)))
+        return status
+
+    def status(self):
+        return self._export(self.info()["C"], *[None] * self.PLANES)
+
 
 class BcsdState(_State):
+    ABI = "sd_bcsd_state"
+    INFO = (("kind", C.c_int), ("G", C.c_int), ("T", C.c_int64), ("C", C.c_int64), ("flags", C.c_int))
+
     def info(self):
-        kind, G, ra = C.c_int(), C.c_int(), C.c_int()
-        T, Cc = C.c_int64(), C.c_int64()
-        check(self.ctx.lib.sd_bcsd_state_info(self.vptr, C.byref(kind), C.byref(G), C.byref(T), C.byref(Cc), C.byref(ra)))
-        return dict(kind=kind.value, G=G.value, T=T.value, C=Cc.value, return_anoms=bool(ra.value & _lib.BCSD_RETURN_ANOMS),
-                    detrend=bool(ra.value & _lib.BCSD_QM_DETREND))
+        i = super().info()
+        flags = i.pop("flags")
+        return dict(i, return_anoms=bool(flags & _lib.BCSD_RETURN_ANOMS), detrend=bool(flags & _lib.BCSD_QM_DETREND))
 
     def status(self):
         st = np.empty(self.info()["C"], dtype=np.int32)
@@ -142,17 +171,14 @@ class BcsdState(_State):
 
 
 class AnalogState(_State):
-    def info(self):
-        T, Cc, F = C.c_int64(), C.c_int64(), C.c_int()
-        check(self.ctx.lib.sd_analog_state_info(self.vptr, C.byref(T), C.byref(F), C.byref(Cc)))
-        return dict(T=T.value, F=F.value, C=Cc.value)
+    ABI = "sd_analog_state"
+    INFO = (("T", C.c_int64), ("F", C.c_int), ("C", C.c_int64))
 
 
-class LinregState(_State):
-    def info(self):
-        T, Cc, F = C.c_int64(), C.c_int64(), C.c_int()
-        check(self.ctx.lib.sd_linreg_state_info(self.vptr, C.byref(T), C.byref(F), C.byref(Cc)))
-        return dict(T=T.value, F=F.value, C=Cc.value)
+class LinregState(_FittedState):
+    ABI = "sd_linreg_state"
+    INFO = (("T", C.c_int64), ("F", C.c_int), ("C", C.c_int64))
+    PLANES = 5
 
     def export(self):
         """coef [F, C], intercept [C], fit_error [C], status [C]; with a threshold also logistic_coef [F, C],
@@ -161,46 +187,31 @@ class LinregState(_State):
         coef, icpt, err = np.empty((i["F"], i["C"])), np.empty(i["C"]), np.empty(i["C"])
         logit = np.full((i["F"] + 1, i["C"]), np.nan)
         dropped = np.full(i["C"], -1, dtype=np.int32)
-        status = np.empty(i["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_linreg_state_export(self.vptr, ptr(coef), ptr(icpt), ptr(err), ptr(logit), ptr(dropped), ptr(status)))
+        status = self._export(i["C"], coef, icpt, err, logit, dropped)
         out = dict(coef=coef, intercept=icpt, fit_error=err, status=status, T=i["T"])
         if (dropped >= 0).all():  # a model with a threshold
             out.update(logistic_coef=logit[:-1], logistic_intercept=logit[-1], thresh_dropped=dropped.astype(bool))
         return out
 
 
-class ZscoreState(_State):
+class ZscoreState(_FittedState):
+    ABI = "sd_zscore_state"
+    INFO = (("K", C.c_int64), ("C", C.c_int64), ("window_width", C.c_int))
     STATS = ("x_mean", "x_std", "y_mean", "y_std", "shift", "scale")
-
-    def info(self):
-        K, Cc, w = C.c_int64(), C.c_int64(), C.c_int()
-        check(self.ctx.lib.sd_zscore_state_info(self.vptr, C.byref(K), C.byref(Cc), C.byref(w)))
-        return dict(K=K.value, C=Cc.value, window_width=w.value)
-
-    def status(self):
-        status = np.empty(self.info()["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_zscore_state_export(self.vptr, None, None, None, None, None, None, ptr(status)))
-        return status
+    PLANES = len(STATS)
 
     def export(self):
         """x_mean, x_std, y_mean, y_std, shift, scale [K, C] (kept day windows x cells), status [C], window_width"""
         i = self.info()
         planes = {k: np.empty((i["K"], i["C"])) for k in self.STATS}
-        status = np.empty(i["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_zscore_state_export(self.vptr, *[ptr(planes[k]) for k in self.STATS], ptr(status)))
+        status = self._export(i["C"], *planes.values())
         return dict(planes, status=status, window_width=i["window_width"])
 
 
-class GroupedState(_State):
-    def info(self):
-        n, F, Cc, w = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
-        check(self.ctx.lib.sd_grouped_state_info(self.vptr, C.byref(n), C.byref(F), C.byref(Cc), C.byref(w)))
-        return dict(n=n.value, F=F.value, C=Cc.value, window=w.value)
-
-    def status(self):
-        status = np.empty(self.info()["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_grouped_state_export(self.vptr, None, None, None, ptr(status)))
-        return status
+class GroupedState(_FittedState):
+    ABI = "sd_grouped_state"
+    INFO = (("n", C.c_int), ("F", C.c_int), ("C", C.c_int64), ("window", C.c_int))
+    PLANES = 3
 
     def fitted(self):
         fitted = np.empty(self.info()["n"], dtype=np.int32)
@@ -210,55 +221,41 @@ class GroupedState(_State):
     def export(self):
         """coef [n, F, C], intercept [n, C], fitted [n] (bool), status [C], window"""
         i = self.info()
-        coef, icpt = np.empty((i["n"], i["F"], i["C"])), np.empty((i["n"], i["C"]))
-        fitted, status = np.empty(i["n"], dtype=np.int32), np.empty(i["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_grouped_state_export(self.vptr, ptr(coef), ptr(icpt), ptr(fitted), ptr(status)))
+        coef, icpt, fitted = np.empty((i["n"], i["F"], i["C"])), np.empty((i["n"], i["C"])), np.empty(i["n"], dtype=np.int32)
+        status = self._export(i["C"], coef, icpt, fitted)
         return dict(coef=coef, intercept=icpt, fitted=fitted.astype(bool), status=status, window=i["window"])
 
 
-class ArrmState(_State):
-    def info(self):
-        B, Cc, T = C.c_int(), C.c_int64(), C.c_int64()
-        check(self.ctx.lib.sd_arrm_state_info(self.vptr, C.byref(B), C.byref(Cc), C.byref(T)))
-        return dict(B=B.value, C=Cc.value, T=T.value)
-
-    def status(self):
-        status = np.empty(self.info()["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_arrm_state_export(self.vptr, None, None, None, None, ptr(status)))
-        return status
+class ArrmState(_FittedState):
+    ABI = "sd_arrm_state"
+    INFO = (("B", C.c_int), ("C", C.c_int64), ("T", C.c_int64))
+    PLANES = 4
 
     def export(self):
         """breaks [B, C], break_index [B, C] (int32), beta [B, C], ssr [C], status [C], T"""
         i = self.info()
         breaks, beta = np.empty((i["B"], i["C"])), np.empty((i["B"], i["C"]))
-        index, ssr, status = np.empty((i["B"], i["C"]), dtype=np.int32), np.empty(i["C"]), np.empty(i["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_arrm_state_export(self.vptr, ptr(breaks), ptr(index), ptr(beta), ptr(ssr), ptr(status)))
+        index, ssr = np.empty((i["B"], i["C"]), dtype=np.int32), np.empty(i["C"])
+        status = self._export(i["C"], breaks, index, beta, ssr)
         return dict(breaks=breaks, break_index=index, beta=beta, ssr=ssr, status=status, T=i["T"])
 
 
-class QmState(_State):
-    def info(self):
-        T, Cc = C.c_int64(), C.c_int64()
-        check(self.ctx.lib.sd_qm_state_info(self.vptr, C.byref(T), C.byref(Cc)))
-        return dict(T=T.value, C=Cc.value)
+class QmState(_FittedState):
+    ABI = "sd_qm_state"
+    INFO = (("T", C.c_int64), ("C", C.c_int64))
+    PLANES = 2
 
     def export(self, with_y=True):
         i = self.info()
         xs = np.empty((i["C"], i["T"]))
         ys = np.empty((i["C"], i["T"])) if with_y else None
-        status = np.empty(i["C"], dtype=np.int32)
-        check(self.ctx.lib.sd_qm_state_export(self.vptr, ptr(xs), None if ys is None else ptr(ys), ptr(status)))
-        return dict(x_sorted=xs, y_sorted=ys, status=status)
+        return dict(x_sorted=xs, y_sorted=ys, status=self._export(i["C"], xs, ys))
 
 
 class RegridState(_State):
     """Separable interpolation tables of one (source grid, target grid, method) on the device (sd_regrid_create)."""
-
-    def info(self):
-        method = C.c_int()
-        ny, nx, Ny, Nx = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        check(self.ctx.lib.sd_regrid_info(self.vptr, C.byref(method), C.byref(ny), C.byref(nx), C.byref(Ny), C.byref(Nx)))
-        return dict(method=method.value, ny=ny.value, nx=nx.value, Ny=Ny.value, Nx=Nx.value)
+    ABI = "sd_regrid"
+    INFO = (("method", C.c_int), ("ny", C.c_int64), ("nx", C.c_int64), ("Ny", C.c_int64), ("Nx", C.c_int64))
 
     def apply(self, src, out=None):
         """src [T, ny, nx]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray -> [T, Ny * Nx]
@@ -296,11 +293,8 @@ class RegridState(_State):
 
 class RemapState(_State):
     """Separable area-overlap tables of one (source grid, target grid) on the device (sd_remap_create)."""
-
-    def info(self):
-        v = [C.c_int64() for _ in range(6)]
-        check(self.ctx.lib.sd_remap_info(self.vptr, *[C.byref(x) for x in v]))
-        return dict(zip(("ny", "nx", "Ny", "Nx", "y_entries", "x_entries"), (x.value for x in v)))
+    ABI = "sd_remap"
+    INFO = tuple((key, C.c_int64) for key in ("ny", "nx", "Ny", "Nx", "y_entries", "x_entries"))
 
     def apply(self, field, min_valid=0.5, out=None):
         """field: a float32 / float64 host array [T, ny, nx] or [T, ny * nx] (any other dtype is taken as float64) or a DeviceArray
@@ -314,9 +308,7 @@ class RemapState(_State):
             field = mine = self.ctx.to_device(field, field.dtype)
         try:
             out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
-            for name, a in (("field", field), ("out", out)):
-                if a.ctx is not self.ctx:
-                    raise ValueError(f"sd_downscale: sd_remap: `{name}` belongs to another context")
+            self.ctx._same_context("sd_remap", field=field, out=out)
             check(self.ctx.lib.sd_remap_apply_dev(self.ctx.handle, self.vptr, field.vptr, f32, field.ld, T, min_valid, out.vptr, out.ld))
         finally:
             if mine is not None:
@@ -457,18 +449,95 @@ class Context:
                                      cell_scale, p_dry, -1 if stream2 is None else stream2, amp2))
         return out
 
-    # ---- BCSD ----
+    # ---- the argument layer of the estimator wrappers: the C ABI takes raw pointers and cannot check them, so every field, result
+    # buffer and state passes one of these before it reaches the library ----
+    def _same_context(self, who, **arrays):
+        for name, a in arrays.items():
+            if a is not None and a.ctx is not self:
+                raise ValueError(f"sd_downscale: {who}: `{name}` belongs to another context")
+
+    def _result_buffer(self, out, shape, on_device, who=None):
+        """the caller's result buffer, checked (a wrong one would be written past its end), or a fresh one; with ``who`` a resident one
+        must also be this context's"""
+        if out is None:
+            return self.empty(shape) if on_device else np.empty(shape)
+        if on_device:
+            if not isinstance(out, DeviceArray) or tuple(out.shape) != tuple(shape) or out.dtype != np.float64 or out.ld < shape[-1]:
+                raise ValueError(f"out: expected a float64 DeviceArray of shape {tuple(shape)}")
+            if who is not None:
+                self._same_context(who, out=out)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == tuple(shape) and out.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"out: expected a C-contiguous float64 array of shape {tuple(shape)}")
+        return out
+
     @staticmethod
-    def _field2(name, a, T=None, Cc=None):
-        """[T, C] field (numpy or DeviceArray) with the expected sizes: the C ABI takes raw pointers and cannot check them."""
-        if a is None:
-            return None
+    def _float64(name, a, layout):
+        """``a`` as the estimator entry points read a field: a float64 DeviceArray as it is, a host array made contiguous float64"""
         if not isinstance(a, DeviceArray):
-            a = _lib.as_f64(a)
-        if len(a.shape) != 2 or (T is not None and a.shape[0] != T) or (Cc is not None and a.shape[1] != Cc):
-            raise ValueError(f"{name}: expected a [{'T' if T is None else T}, {'C' if Cc is None else Cc}] field, got shape {tuple(a.shape)}")
+            return _lib.as_f64(a)
+        if a.dtype != np.float64:  # (it would be read to twice its length)
+            raise ValueError(f"{name}: expected a float64 {layout} field, got shape {tuple(a.shape)} of {a.dtype}")
         return a
 
+    @staticmethod
+    def _field(name, a, *dims):
+        """a field of rank ``len(dims)`` (numpy or DeviceArray, None stays None) with the expected sizes: a number in ``dims`` is the
+        size that axis must have, a string only names the axis in the refusal"""
+        if a is None:
+            return None
+        layout = f"[{', '.join(str(d) for d in dims)}]"
+        a = Context._float64(name, a, layout)
+        if len(a.shape) != len(dims) or any(not isinstance(d, str) and s != d for s, d in zip(a.shape, dims)):
+            raise ValueError(f"{name}: expected a {layout} field, got shape {tuple(a.shape)}")
+        return a
+
+    @staticmethod
+    def _train3(X, y, same_kind=""):
+        """the training pair X [T, F, C], y [T, C] of the analog and regression fits -> (X, y, the words that refuse the pair)"""
+        X, y = Context._float64("X", X, "[T, F, C]"), Context._float64("y", y, "[T, C]")
+        words = f"expected X [T, F, C] and y [T, C]{same_kind}, got {tuple(X.shape)} and {tuple(y.shape)}"
+        if len(X.shape) != 3 or tuple(y.shape) != (X.shape[0], X.shape[2]):
+            raise ValueError(words)
+        return X, y, words
+
+    @staticmethod
+    def _beside(X, y):
+        """``y`` beside ``X``: a resident y that comes with a host X joins it on the host"""
+        return y.to_host() if isinstance(y, DeviceArray) and not isinstance(X, DeviceArray) else y
+
+    @staticmethod
+    def _threshold(thresh):
+        return (0, 0.0) if thresh is None else (1, float(thresh))
+
+    _ONE_PITCH = "X and y: expected two DeviceArrays with the same row pitch"
+
+    def _resident(self, who, one_ld=(), mixed=None, **arrays):
+        """The residency rule, -> True for the resident form of a call: its array arguments (None: not given) are all host arrays or
+        all DeviceArrays of this context, and the resident ones named in ``one_ld``, for which the ABI has one ``ld``, share their
+        row pitch."""
+        given = {name: a for name, a in arrays.items() if a is not None}
+        on = [isinstance(a, DeviceArray) for a in given.values()]
+        if any(on) != all(on):
+            raise ValueError(mixed or f"{' and '.join(given)} must both be host arrays or both be DeviceArrays")
+        if not any(on):
+            return False
+        self._same_context(who, **given)
+        if len({given[name].ld for name in one_ld if name in given}) > 1:
+            raise ValueError(self._ONE_PITCH)
+        return True
+
+    def _info_of(self, who, state):
+        """``state.info()`` of a state of this context"""
+        self._same_context(who, state=state)
+        return state.info()
+
+    def _create(self, cls, fn, *args):
+        """the creating call ``fn(*args, &handle)`` -> the handle as a ``cls``"""
+        h = C.c_void_p()
+        check(fn(*args, C.byref(h)))
+        return cls(self, h.value)
+
+    # ---- BCSD ----
     @staticmethod
     def _group_ids(name, gid, T, G):
         gid = _lib.as_i32(gid)
@@ -485,34 +554,25 @@ class Context:
     def bcsd_fit(self, kind, X, y, gid, G, return_anoms=True, detrend=False):
         """X, y: numpy [T,C] (host path) or DeviceArray [T,C] (resident path); X may be None for PR.  ``detrend``:
         qm_kwargs={'detrend': True} (quantile.py:95-98,128-145)."""
-        return_anoms = self._bcsd_options(return_anoms, detrend)
+        flags = self._bcsd_options(return_anoms, detrend)
         if self._is_f32_host(y) and (X is None or self._is_f32_host(X)) and y.ndim == 2 and y.size > 0:
             y = self.widen_to_device(y)  # float32 grids: 4 bytes per sample over PCIe, widened in HBM
             X = None if X is None else self.widen_to_device(X)
-        y = self._field2("y", y)
-        X = self._field2("X", X, *y.shape)
-        if X is not None and isinstance(X, DeviceArray) != isinstance(y, DeviceArray):
-            raise ValueError("X and y must both be host arrays or both be DeviceArrays")
-        gid = self._group_ids("group_id", gid, y.shape[0], G)
-        h = C.c_void_p()
-        if isinstance(y, DeviceArray):
-            T, Cc = y.shape
-            assert X is None or X.ld == y.ld
-            check(self.lib.sd_bcsd_fit_dev(self.handle, kind, None if X is None else X.vptr, y.vptr, y.ld, ptr(gid), G, T, Cc,
-                                           int(return_anoms), C.byref(h)))
-        else:
-            y = _lib.as_f64(y)
-            X = None if X is None else _lib.as_f64(X)
-            T, Cc = y.shape
-            check(self.lib.sd_bcsd_fit(self.handle, kind, ptr(X), ptr(y), ptr(gid), G, T, Cc, int(return_anoms), C.byref(h)))
-        return BcsdState(self, h.value, self.lib.sd_bcsd_state_destroy)
+        y = self._field("y", y, "T", "C")
+        X = self._field("X", X, *y.shape)
+        dev = self._resident("sd_bcsd_fit", ("X", "y"), X=X, y=y)
+        T, Cc = y.shape
+        gid = self._group_ids("group_id", gid, T, G)
+        if dev:
+            return self._create(BcsdState, self.lib.sd_bcsd_fit_dev, self.handle, kind, vptr(X), y.vptr, y.ld, ptr(gid), G, T, Cc, flags)
+        return self._create(BcsdState, self.lib.sd_bcsd_fit, self.handle, kind, ptr(X), ptr(y), ptr(gid), G, T, Cc, flags)
 
     def bcsd_fit_groups(self, kind, X, y, order, offsets, return_anoms=True, detrend=False):
         """Fit on explicitly listed (possibly overlapping) groups: ``order`` = time indices group by group,
         ``offsets[G+1]`` (time_grouper='daily_nasa-nex': bcsd.py:36-38,50-55)."""
-        return_anoms = self._bcsd_options(return_anoms, detrend)
-        y = self._field2("y", y)
-        X = self._field2("X", X, *y.shape)
+        flags = self._bcsd_options(return_anoms, detrend)
+        y = self._field("y", y, "T", "C")
+        X = self._field("X", X, *y.shape)
         T, Cc = y.shape
         order = _lib.as_i32(order)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -521,49 +581,31 @@ class Context:
             raise ValueError("group offsets must start at 0, not decrease and end at len(order)")
         if len(order) and (order.min() < 0 or order.max() >= T):
             raise ValueError(f"group order entries must lie in [0, {T})")
-        h = C.c_void_p()
-        if isinstance(y, DeviceArray):
-            assert X is None or X.ld == y.ld
-            check(self.lib.sd_bcsd_fit_groups_dev(self.handle, kind, None if X is None else X.vptr, y.vptr, y.ld, ptr(order),
-                                                  ptr(offsets), G, T, Cc, int(return_anoms), C.byref(h)))
-        else:
-            check(self.lib.sd_bcsd_fit_groups(self.handle, kind, ptr(X), ptr(y), ptr(order), ptr(offsets), G, T, Cc,
-                                              int(return_anoms), C.byref(h)))
-        return BcsdState(self, h.value, self.lib.sd_bcsd_state_destroy)
+        if self._resident("sd_bcsd_fit_groups", ("X", "y"), X=X, y=y):
+            return self._create(BcsdState, self.lib.sd_bcsd_fit_groups_dev, self.handle, kind, vptr(X), y.vptr, y.ld, ptr(order),
+                                ptr(offsets), G, T, Cc, flags)
+        return self._create(BcsdState, self.lib.sd_bcsd_fit_groups, self.handle, kind, ptr(X), ptr(y), ptr(order), ptr(offsets), G, T, Cc,
+                            flags)
 
-    def _result_buffer(self, out, shape, on_device):
-        """the caller's result buffer, checked (a wrong one would be written past its end), or a fresh one"""
-        if out is None:
-            return self.empty(shape) if on_device else np.empty(shape)
-        if on_device:
-            if not isinstance(out, DeviceArray) or tuple(out.shape) != tuple(shape) or out.dtype != np.float64 or out.ld < shape[-1]:
-                raise ValueError(f"out: expected a float64 DeviceArray of shape {tuple(shape)}")
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == tuple(shape) and out.flags["C_CONTIGUOUS"]):
-            raise ValueError(f"out: expected a C-contiguous float64 array of shape {tuple(shape)}")
-        return out
-
-    def bcsd_predict_trend(self, state, Xp, gid_p, gid_trend, G_trend, out=None):
-        """Predict with a climate-trend grouper of its own: rolling mean over ``gid_trend`` groups, climatologies and
-        quantile mapping over ``gid_p`` (groups of the state) -- bcsd.py:247-267."""
-        info = state.info()
-        Xp = self._field2("X", Xp, None, info["C"])
-        Tp, Cc = Xp.shape
-        gid_p = self._group_ids("group_id", gid_p, Tp, info["G"])
-        gid_trend = self._group_ids("trend_group_id", gid_trend, Tp, G_trend)
-        status = np.empty(Cc, dtype=np.int32)
-        out = self._result_buffer(out, (Tp, Cc), isinstance(Xp, DeviceArray))
-        if isinstance(Xp, DeviceArray):
-            check(self.lib.sd_bcsd_predict_trend_dev(self.handle, state.vptr, Xp.vptr, Xp.ld, ptr(gid_p), ptr(gid_trend), G_trend, Tp,
-                                                     out.vptr, out.ld, ptr(status)))
-        else:
-            check(self.lib.sd_bcsd_predict_trend(self.handle, state.vptr, ptr(Xp), ptr(gid_p), ptr(gid_trend), G_trend, Tp, ptr(out),
-                                                 ptr(status)))
-        return out, status
+    def bcsd_import(self, exported):
+        i = exported["info"]
+        detrend = i.get("detrend", False)
+        if detrend:
+            trend = _lib.as_f64(exported["y_trend"])
+            if trend.shape != (i["C"], i["G"], 2):
+                raise ValueError(f"y_trend: expected shape {(i['C'], i['G'], 2)}, got {trend.shape}")
+        st = self._create(BcsdState, self.lib.sd_bcsd_state_import, self.handle, i["kind"], i["G"], i["T"], i["C"],
+                          self._bcsd_options(i["return_anoms"], detrend), ptr(_lib.as_f64(exported["y_sorted"])),
+                          ptr(_lib.as_f64(exported["x_climo"])), ptr(_lib.as_f64(exported["y_climo"])), ptr(_lib.as_i32(exported["status"])),
+                          ptr(np.ascontiguousarray(exported["group_offsets"], dtype=np.int64)))
+        if detrend:
+            check(self.lib.sd_bcsd_state_set_trend(st.vptr, ptr(trend)))
+        return st
 
     def bcsd_predict(self, state, Xp, gid_p, out=None, out_dtype=None):
         """``out_dtype=np.float32`` with a float32 host ``Xp``: the field goes in and the result comes back as float32
         (widened / narrowed on the device); everything else as before (float64 results)."""
-        info = state.info()
+        info = self._info_of("sd_bcsd_predict", state)
         want32 = out_dtype is not None and np.dtype(out_dtype) == np.float32
         if out_dtype is not None and not want32 and np.dtype(out_dtype) != np.float64:
             raise ValueError("bcsd_predict: out_dtype must be float64 or float32")
@@ -575,95 +617,84 @@ class Context:
                 raise ValueError("bcsd_predict: out_dtype=float32 does not combine with a float64 `out` buffer")
             res, status = self.bcsd_predict(state, Xp, gid_p)
             return (self.narrow_to_host(res) if isinstance(res, DeviceArray) else res.astype(np.float32)), status
-        Xp = self._field2("X", Xp, None, info["C"])
-        gid_p = self._group_ids("group_id", gid_p, Xp.shape[0], info["G"])
         Cc = info["C"]
+        Xp = self._field("X", Xp, "T", Cc)
+        Tp = Xp.shape[0]
+        gid_p = self._group_ids("group_id", gid_p, Tp, info["G"])
+        dev = self._resident("sd_bcsd_predict", X=Xp)
+        out = self._result_buffer(out, (Tp, Cc), dev, "sd_bcsd_predict")
         status = np.empty(Cc, dtype=np.int32)
-        if isinstance(Xp, DeviceArray):
-            Tp = Xp.shape[0]
-            out = self._result_buffer(out, (Tp, Cc), True)
+        if dev:
             check(self.lib.sd_bcsd_predict_dev(self.handle, state.vptr, Xp.vptr, Xp.ld, ptr(gid_p), Tp, out.vptr, out.ld, ptr(status)))
         else:
-            Xp = _lib.as_f64(Xp)
-            Tp = Xp.shape[0]
-            out = self._result_buffer(out, (Tp, Cc), False)  # (a reused result buffer)
             check(self.lib.sd_bcsd_predict(self.handle, state.vptr, ptr(Xp), ptr(gid_p), Tp, ptr(out), ptr(status)))
+        return out, status
+
+    def bcsd_predict_trend(self, state, Xp, gid_p, gid_trend, G_trend, out=None):
+        """Predict with a climate-trend grouper of its own: rolling mean over ``gid_trend`` groups, climatologies and
+        quantile mapping over ``gid_p`` (groups of the state) -- bcsd.py:247-267."""
+        info = self._info_of("sd_bcsd_predict_trend", state)
+        Cc = info["C"]
+        Xp = self._field("X", Xp, "T", Cc)
+        Tp = Xp.shape[0]
+        gid_p = self._group_ids("group_id", gid_p, Tp, info["G"])
+        gid_trend = self._group_ids("trend_group_id", gid_trend, Tp, G_trend)
+        dev = self._resident("sd_bcsd_predict_trend", X=Xp)
+        out = self._result_buffer(out, (Tp, Cc), dev, "sd_bcsd_predict_trend")
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
+            check(self.lib.sd_bcsd_predict_trend_dev(self.handle, state.vptr, Xp.vptr, Xp.ld, ptr(gid_p), ptr(gid_trend), G_trend, Tp,
+                                                     out.vptr, out.ld, ptr(status)))
+        else:
+            check(self.lib.sd_bcsd_predict_trend(self.handle, state.vptr, ptr(Xp), ptr(gid_p), ptr(gid_trend), G_trend, Tp, ptr(out),
+                                                 ptr(status)))
         return out, status
 
     def bcsd_fit_predict(self, kind, X, y, gid, G, Xp, gid_p, return_anoms=True, out=None, detrend=False):
         """Fused resident path (DeviceArrays only)."""
-        return_anoms = self._bcsd_options(return_anoms, detrend)
-        y = self._field2("y", y)
-        X = self._field2("X", X, *y.shape)
-        Xp = self._field2("Xp", Xp, None, y.shape[1])
+        flags = self._bcsd_options(return_anoms, detrend)
+        y = self._field("y", y, "T", "C")
+        X = self._field("X", X, *y.shape)
+        Xp = self._field("Xp", Xp, "T", y.shape[1])
+        resident_only = "bcsd_fit_predict takes resident fields: X, y and Xp must be DeviceArrays"
+        if not self._resident("sd_bcsd_fit_predict", ("X", "y"), resident_only, X=X, y=y, Xp=Xp):
+            raise ValueError(resident_only)
         T, Cc = y.shape
         Tp = Xp.shape[0]
         gid, gid_p = self._group_ids("group_id", gid, T, G), self._group_ids("group_id_p", gid_p, Tp, G)
-        out = self.empty((Tp, Cc)) if out is None else out
-        if tuple(out.shape) != (Tp, Cc):
-            raise ValueError(f"out: expected shape {(Tp, Cc)}, got {tuple(out.shape)}")
+        out = self._result_buffer(out, (Tp, Cc), True, "sd_bcsd_fit_predict")
         status = np.empty(Cc, dtype=np.int32)
-        assert X is None or X.ld == y.ld
-        check(self.lib.sd_bcsd_fit_predict_dev(self.handle, kind, None if X is None else X.vptr, y.vptr, y.ld, ptr(gid), G, T,
-                                               Cc, int(return_anoms), Xp.vptr, Xp.ld, ptr(gid_p), Tp, out.vptr, out.ld,
-                                               ptr(status)))
+        check(self.lib.sd_bcsd_fit_predict_dev(self.handle, kind, vptr(X), y.vptr, y.ld, ptr(gid), G, T, Cc, flags, Xp.vptr, Xp.ld, ptr(gid_p),
+                                               Tp, out.vptr, out.ld, ptr(status)))
         return out, status
-
-    def bcsd_import(self, exported):
-        i = exported["info"]
-        h = C.c_void_p()
-        check(self.lib.sd_bcsd_state_import(
-            self.handle, i["kind"], i["G"], i["T"], i["C"], self._bcsd_options(i["return_anoms"], i.get("detrend", False)),
-            ptr(_lib.as_f64(exported["y_sorted"])),
-            ptr(_lib.as_f64(exported["x_climo"])), ptr(_lib.as_f64(exported["y_climo"])), ptr(_lib.as_i32(exported["status"])),
-            ptr(np.ascontiguousarray(exported["group_offsets"], dtype=np.int64)), C.byref(h)))
-        st = BcsdState(self, h.value, self.lib.sd_bcsd_state_destroy)
-        if i.get("detrend", False):
-            trend = _lib.as_f64(exported["y_trend"])
-            if trend.shape != (i["C"], i["G"], 2):
-                raise ValueError(f"y_trend: expected shape {(i['C'], i['G'], 2)}, got {trend.shape}")
-            check(self.lib.sd_bcsd_state_set_trend(st.vptr, ptr(trend)))
-        return st
 
     # ---- quantile-mapping regressors ----
     def qm_fit(self, X, y=None):
         """X, y [T, C] numpy or DeviceArray -> QmState (sorted series per cell); y=None keeps only the CDF of X
         (CunnaneTransformer)."""
-        X = self._field2("X", X)
-        y = self._field2("y", y, *X.shape)
-        if y is not None and isinstance(X, DeviceArray) != isinstance(y, DeviceArray):
-            raise ValueError("X and y must both be host arrays or both be DeviceArrays")
-        h = C.c_void_p()
-        if isinstance(X, DeviceArray):
-            T, Cc = X.shape
-            assert y is None or X.ld == y.ld
-            check(self.lib.sd_qm_fit_dev(self.handle, X.vptr, None if y is None else y.vptr, X.ld, T, Cc, C.byref(h)))
-        else:
-            X = _lib.as_f64(X)
-            y = None if y is None else _lib.as_f64(y)
-            T, Cc = X.shape
-            check(self.lib.sd_qm_fit(self.handle, ptr(X), None if y is None else ptr(y), T, Cc, C.byref(h)))
-        return QmState(self, h.value, self.lib.sd_qm_state_destroy)
+        X = self._field("X", X, "T", "C")
+        y = self._field("y", y, *X.shape)
+        T, Cc = X.shape
+        if self._resident("sd_qm_fit", ("X", "y"), X=X, y=y):
+            return self._create(QmState, self.lib.sd_qm_fit_dev, self.handle, X.vptr, vptr(y), X.ld, T, Cc)
+        return self._create(QmState, self.lib.sd_qm_fit, self.handle, ptr(X), ptr(y), T, Cc)
 
     def qm_cunnane(self, state, direction, X, extrapolate="both", n_endpoints=10, out=None):
         """CunnaneTransformer.transform (direction 0) / inverse_transform (1) of X [Tp, C] on the fitted CDFs."""
-        Cc = state.info()["C"]
-        X = self._field2("X", X, None, Cc)
-        status = np.empty(Cc, dtype=np.int32)
+        Cc = self._info_of("sd_qm_cunnane", state)["C"]
+        X = self._field("X", X, "T", Cc)
         if extrapolate not in _lib.EXTRAP_CODES:
             raise ValueError(f"unknown value for extrapolate: {extrapolate}")
         code = _lib.EXTRAP_CODES[extrapolate]
-        if isinstance(X, DeviceArray):
-            Tp = X.shape[0]
-            out = self.empty((Tp, Cc)) if out is None else out
+        Tp = X.shape[0]
+        dev = self._resident("sd_qm_cunnane", X=X)
+        out = self._result_buffer(out, (Tp, Cc), dev, "sd_qm_cunnane")
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
             check(self.lib.sd_qm_cunnane_dev(self.handle, state.vptr, int(direction), code, int(n_endpoints), X.vptr, X.ld, Tp,
                                              out.vptr, out.ld, ptr(status)))
         else:
-            X = _lib.as_f64(X)
-            Tp = X.shape[0]
-            out = np.empty((Tp, Cc))
-            check(self.lib.sd_qm_cunnane(self.handle, state.vptr, int(direction), code, int(n_endpoints), ptr(X), Tp, ptr(out),
-                                         ptr(status)))
+            check(self.lib.sd_qm_cunnane(self.handle, state.vptr, int(direction), code, int(n_endpoints), ptr(X), Tp, ptr(out), ptr(status)))
         return out, status
 
     def qm_predict(self, state, model, Xp, extrapolate=None, n_endpoints=10, out=None):
@@ -672,148 +703,116 @@ class Context:
         if extrapolate not in _lib.QM_EXTRAP_CODES:
             raise ValueError(f"unknown value for extrapolate: {extrapolate}")
         code = _lib.QM_EXTRAP_CODES[extrapolate]
-        Cc = state.info()["C"]
-        Xp = self._field2("X", Xp, None, Cc)
-        status = np.empty(Cc, dtype=np.int32)
+        Cc = self._info_of("sd_qm_predict", state)["C"]
+        Xp = self._field("X", Xp, "T", Cc)
         Tp = Xp.shape[0]
-        if isinstance(Xp, DeviceArray):
-            out = self.empty((Tp, Cc)) if out is None else out
+        dev = self._resident("sd_qm_predict", X=Xp)
+        out = self._result_buffer(out, (Tp, Cc), dev, "sd_qm_predict")
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
             check(self.lib.sd_qm_predict_dev(self.handle, state.vptr, int(model), code, int(n_endpoints), Xp.vptr, Xp.ld, Tp,
                                              out.vptr, out.ld, ptr(status)))
         else:
-            out = np.empty((Tp, Cc))
-            check(self.lib.sd_qm_predict(self.handle, state.vptr, int(model), code, int(n_endpoints), ptr(Xp), Tp, ptr(out),
-                                         ptr(status)))
+            check(self.lib.sd_qm_predict(self.handle, state.vptr, int(model), code, int(n_endpoints), ptr(Xp), Tp, ptr(out), ptr(status)))
         return out, status
 
     # ---- analogs ----
     def analog_fit(self, X, y):
         """X [T,F,C], y [T,C] numpy or DeviceArray."""
-        if not isinstance(X, DeviceArray):
-            X, y = _lib.as_f64(X), _lib.as_f64(y)
-        if len(X.shape) != 3 or tuple(y.shape) != (X.shape[0], X.shape[2]) or isinstance(X, DeviceArray) != isinstance(y, DeviceArray):
-            raise ValueError(f"expected X [T, F, C] and y [T, C] of the same kind, got {tuple(X.shape)} and {tuple(y.shape)}")
-        h = C.c_void_p()
-        if isinstance(X, DeviceArray):
-            T, F, Cc = X.shape
-            assert X.ld == y.ld
-            check(self.lib.sd_analog_fit_dev(self.handle, X.vptr, y.vptr, y.ld, T, F, Cc, C.byref(h)))
-        else:
-            X, y = _lib.as_f64(X), _lib.as_f64(y)
-            T, F, Cc = X.shape
-            check(self.lib.sd_analog_fit(self.handle, ptr(X), ptr(y), T, F, Cc, C.byref(h)))
-        return AnalogState(self, h.value, self.lib.sd_analog_state_destroy)
-
-    def analog_fit_predict(self, X, y, Xq, k, kind, thresh=None, out=None):
-        """AnalogBase.fit + PureAnalog.predict in one call without a fitted state (sd_analog_fit_predict*): X [T,F,C], y [T,C],
-        Xq [Tq,F,C], all numpy or all DeviceArray -> (out [Tq,3,C], status [C]); bit-identical to analog_fit -> analog_predict."""
-        dev = isinstance(X, DeviceArray)
-        if not dev:
-            X, y, Xq = _lib.as_f64(X), _lib.as_f64(y), _lib.as_f64(Xq)
-        if isinstance(y, DeviceArray) != dev or isinstance(Xq, DeviceArray) != dev:
-            raise ValueError("X, y and Xq must all be numpy arrays or all DeviceArrays")
-        if len(X.shape) != 3 or tuple(y.shape) != (X.shape[0], X.shape[2]):
-            raise ValueError(f"expected X [T, F, C] and y [T, C], got {tuple(X.shape)} and {tuple(y.shape)}")
+        X, y, words = self._train3(X, y, " of the same kind")
         T, F, Cc = X.shape
-        if len(Xq.shape) != 3 or Xq.shape[1] != F or Xq.shape[2] != Cc:
-            raise ValueError(f"Xq: expected a [Tq, {F}, {Cc}] field, got shape {tuple(Xq.shape)}")
-        k = int(k)
-        if k < 1 or k > T:
-            raise ValueError(f"k={k}: expected 1 <= k <= {T} (the number of training samples)")
-        Tq = Xq.shape[0]
-        status = np.empty(Cc, dtype=np.int32)
-        has_t, tv = (0, 0.0) if thresh is None else (1, float(thresh))
-        if dev:
-            assert X.ld == y.ld
-            out = self.empty((Tq, 3, Cc)) if out is None else out
-            check(self.lib.sd_analog_fit_predict_dev(self.handle, X.vptr, y.vptr, y.ld, T, F, Cc, Xq.vptr, Xq.ld, Tq, k, kind, has_t, tv,
-                                                     out.vptr, out.ld, ptr(status)))
-        else:
-            if out is None:
-                out = np.empty((Tq, 3, Cc))
-            elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (Tq, 3, Cc) and out.flags.c_contiguous):
-                raise ValueError(f"out: expected a C-contiguous float64 array of shape {(Tq, 3, Cc)}")
-            check(self.lib.sd_analog_fit_predict(self.handle, ptr(X), ptr(y), T, F, Cc, ptr(Xq), Tq, k, kind, has_t, tv, ptr(out), ptr(status)))
-        return out, status
+        if self._resident("sd_analog_fit", ("X", "y"), words, X=X, y=y):
+            return self._create(AnalogState, self.lib.sd_analog_fit_dev, self.handle, X.vptr, y.vptr, y.ld, T, F, Cc)
+        return self._create(AnalogState, self.lib.sd_analog_fit, self.handle, ptr(X), ptr(y), T, F, Cc)
+
+    def _queries(self, who, state, Xq):
+        """Xq [Tq, F, C] for a fitted state of F features and C cells -> (Xq, the state's info, resident?)"""
+        info = self._info_of(who, state)
+        Xq = self._field("Xq", Xq, "Tq", info["F"], info["C"])
+        return Xq, info, self._resident(who, Xq=Xq)
 
     def analog_predict(self, state, Xq, k, kind, thresh=None, sample_inds=None, want_neighbors=False, out=None):
-        info = state.info()
-        Cc = info["C"]
-        if not isinstance(Xq, DeviceArray):
-            Xq = _lib.as_f64(Xq)
-        if len(Xq.shape) != 3 or Xq.shape[1] != info["F"] or Xq.shape[2] != Cc:
-            raise ValueError(f"Xq: expected a [Tq, {info['F']}, {Cc}] field, got shape {tuple(Xq.shape)}")
+        Xq, info, dev = self._queries("sd_analog_predict", state, Xq)
+        Tq, Cc = Xq.shape[0], info["C"]
         k = int(k)
         if k < 1 or k > info["T"]:
             raise ValueError(f"k={k}: expected 1 <= k <= {info['T']} (the number of training samples)")
         if sample_inds is not None:
-            if not isinstance(sample_inds, DeviceArray):
+            resident = isinstance(sample_inds, DeviceArray)
+            if not resident:
                 sample_inds = _lib.as_i32(sample_inds)
-            if tuple(sample_inds.shape) != (Xq.shape[0], Cc):
-                raise ValueError(f"sample_inds: expected shape {(Xq.shape[0], Cc)}, got {tuple(sample_inds.shape)}")
-            if not isinstance(sample_inds, DeviceArray) and len(sample_inds) and (np.min(sample_inds) < 0 or np.max(sample_inds) >= k):
+            if tuple(sample_inds.shape) != (Tq, Cc):
+                raise ValueError(f"sample_inds: expected shape {(Tq, Cc)}, got {tuple(sample_inds.shape)}")
+            if not resident and len(sample_inds) and (np.min(sample_inds) < 0 or np.max(sample_inds) >= k):
                 raise ValueError(f"sample_inds must lie in [0, {k})")
+            if resident:  # (host indices also go beside a resident Xq: they are uploaded below)
+                if sample_inds.dtype != np.int32 or sample_inds.ld != Cc:
+                    raise ValueError(f"sample_inds: expected a contiguous int32 DeviceArray, got pitch {sample_inds.ld} of {sample_inds.dtype}")
+                self._resident("sd_analog_predict", Xq=Xq, sample_inds=sample_inds)
+        out = self._result_buffer(out, (Tq, 3, Cc), dev, "sd_analog_predict")
+        if dev and want_neighbors and out.ld != Cc:
+            raise ValueError("analog_predict: the neighbour fields share the pitch of `out`, which must be contiguous here")
+        has_t, tv = self._threshold(thresh)
         status = np.empty(Cc, dtype=np.int32)
-        has_t, tv = (0, 0.0) if thresh is None else (1, float(thresh))
-        if isinstance(Xq, DeviceArray):
-            Tq = Xq.shape[0]
-            out = self.empty((Tq, 3, Cc)) if out is None else out
-            samp = None if sample_inds is None else (sample_inds if isinstance(sample_inds, DeviceArray) else self.to_device(sample_inds, np.int32))
+        if dev:
+            samp = sample_inds if sample_inds is None or isinstance(sample_inds, DeviceArray) else self.to_device(sample_inds, np.int32)
             inds = self.empty((Tq, k, Cc), np.int64) if want_neighbors else None
             dist = self.empty((Tq, k, Cc)) if want_neighbors else None
-            assert not want_neighbors or out.ld == Cc
-            check(self.lib.sd_analog_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, k, kind, has_t, tv,
-                                                 None if samp is None else samp.vptr, out.vptr, out.ld,
-                                                 None if inds is None else inds.vptr, None if dist is None else dist.vptr, ptr(status)))
+            check(self.lib.sd_analog_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, k, kind, has_t, tv, vptr(samp), out.vptr, out.ld,
+                                                 vptr(inds), vptr(dist), ptr(status)))
         else:
-            Xq = _lib.as_f64(Xq)
-            Tq = Xq.shape[0]
-            out = np.empty((Tq, 3, Cc))
-            samp = None if sample_inds is None else _lib.as_i32(sample_inds)
             inds = np.empty((Tq, k, Cc), dtype=np.int64) if want_neighbors else None
             dist = np.empty((Tq, k, Cc)) if want_neighbors else None
-            check(self.lib.sd_analog_predict(self.handle, state.vptr, ptr(Xq), Tq, k, kind, has_t, tv, ptr(samp), ptr(out),
+            check(self.lib.sd_analog_predict(self.handle, state.vptr, ptr(Xq), Tq, k, kind, has_t, tv, ptr(sample_inds), ptr(out),
                                              ptr(inds), ptr(dist), ptr(status)))
         return (out, status, inds, dist) if want_neighbors else (out, status)
 
     def analogreg_predict(self, state, Xq, k, thresh=None, out=None):
         """AnalogRegression.predict for every cell; ``thresh``: exceedance probability by logistic regression on the analogs
         (gard.py:201-212), linear model on the exceeding analogs."""
-        info = state.info()
-        Cc = info["C"]
-        if not isinstance(Xq, DeviceArray):
-            Xq = _lib.as_f64(Xq)
-        if len(Xq.shape) != 3 or Xq.shape[1] != info["F"] or Xq.shape[2] != Cc:
-            raise ValueError(f"Xq: expected a [Tq, {info['F']}, {Cc}] field, got shape {tuple(Xq.shape)}")
+        Xq, info, dev = self._queries("sd_analogreg_predict", state, Xq)
+        Tq, Cc = Xq.shape[0], info["C"]
+        out = self._result_buffer(out, (Tq, 3, Cc), dev, "sd_analogreg_predict")
+        has, thr = self._threshold(thresh)
         status = np.empty(Cc, dtype=np.int32)
-        has, thr = (0, 0.0) if thresh is None else (1, float(thresh))
-        Tq = Xq.shape[0]
-        if isinstance(Xq, DeviceArray):
-            out = self.empty((Tq, 3, Cc)) if out is None else out
+        if dev:
             check(self.lib.sd_analogreg_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, int(k), has, thr, out.vptr, out.ld,
                                                     ptr(status)))
         else:
-            out = np.empty((Tq, 3, Cc))
             check(self.lib.sd_analogreg_predict(self.handle, state.vptr, ptr(Xq), Tq, int(k), has, thr, ptr(out), ptr(status)))
+        return out, status
+
+    def analog_fit_predict(self, X, y, Xq, k, kind, thresh=None, out=None):
+        """AnalogBase.fit + PureAnalog.predict in one call without a fitted state (sd_analog_fit_predict*): X [T,F,C], y [T,C],
+        Xq [Tq,F,C], all numpy or all DeviceArray -> (out [Tq,3,C], status [C]); bit-identical to analog_fit -> analog_predict."""
+        dev = self._resident("sd_analog_fit_predict", ("X", "y"), "X, y and Xq must all be numpy arrays or all DeviceArrays", X=X, y=y, Xq=Xq)
+        X, y, _ = self._train3(X, y)
+        T, F, Cc = X.shape
+        Xq = self._field("Xq", Xq, "Tq", F, Cc)
+        Tq = Xq.shape[0]
+        k = int(k)
+        if k < 1 or k > T:
+            raise ValueError(f"k={k}: expected 1 <= k <= {T} (the number of training samples)")
+        out = self._result_buffer(out, (Tq, 3, Cc), dev, "sd_analog_fit_predict")
+        has_t, tv = self._threshold(thresh)
+        status = np.empty(Cc, dtype=np.int32)
+        if dev:
+            check(self.lib.sd_analog_fit_predict_dev(self.handle, X.vptr, y.vptr, y.ld, T, F, Cc, Xq.vptr, Xq.ld, Tq, k, kind, has_t, tv,
+                                                     out.vptr, out.ld, ptr(status)))
+        else:
+            check(self.lib.sd_analog_fit_predict(self.handle, ptr(X), ptr(y), T, F, Cc, ptr(Xq), Tq, k, kind, has_t, tv, ptr(out), ptr(status)))
         return out, status
 
     # ---- PureRegression (thresh=None) ----
     def linreg_fit(self, X, y, thresh=None):
         """X [T,F,C], y [T,C] numpy or DeviceArray -> LinregState (coefficients, intercept, fit error per cell; with ``thresh``
         also the logistic model of the exceedance probability, gard.py:416-437)."""
-        if not isinstance(X, DeviceArray):
-            X, y = _lib.as_f64(X), _lib.as_f64(y)
-        if len(X.shape) != 3 or tuple(y.shape) != (X.shape[0], X.shape[2]) or isinstance(X, DeviceArray) != isinstance(y, DeviceArray):
-            raise ValueError(f"expected X [T, F, C] and y [T, C] of the same kind, got {tuple(X.shape)} and {tuple(y.shape)}")
-        has, thr = (0, 0.0) if thresh is None else (1, float(thresh))
-        h = C.c_void_p()
+        X, y, words = self._train3(X, y, " of the same kind")
         T, F, Cc = X.shape
-        if isinstance(X, DeviceArray):
-            assert X.ld == y.ld
-            check(self.lib.sd_linreg_fit_dev(self.handle, X.vptr, y.vptr, y.ld, T, F, Cc, has, thr, C.byref(h)))
-        else:
-            check(self.lib.sd_linreg_fit(self.handle, ptr(X), ptr(y), T, F, Cc, has, thr, C.byref(h)))
-        return LinregState(self, h.value, self.lib.sd_linreg_state_destroy)
+        has, thr = self._threshold(thresh)
+        if self._resident("sd_linreg_fit", ("X", "y"), words, X=X, y=y):
+            return self._create(LinregState, self.lib.sd_linreg_fit_dev, self.handle, X.vptr, y.vptr, y.ld, T, F, Cc, has, thr)
+        return self._create(LinregState, self.lib.sd_linreg_fit, self.handle, ptr(X), ptr(y), T, F, Cc, has, thr)
 
     def linreg_import(self, exported):
         """device state from ``LinregState.export()`` (pickling, checkpoint / resume)"""
@@ -823,50 +822,35 @@ class Context:
         if "logistic_coef" in exported:
             logit = _lib.as_f64(np.vstack([exported["logistic_coef"], np.asarray(exported["logistic_intercept"]).reshape(1, Cc)]))
             dropped = _lib.as_i32(exported["thresh_dropped"])
-        h = C.c_void_p()
-        check(self.lib.sd_linreg_state_import(self.handle, int(exported["T"]), F, Cc, ptr(coef), ptr(_lib.as_f64(exported["intercept"])),
-                                              ptr(_lib.as_f64(exported["fit_error"])), ptr(logit), ptr(dropped),
-                                              ptr(_lib.as_i32(exported["status"])), C.byref(h)))
-        return LinregState(self, h.value, self.lib.sd_linreg_state_destroy)
+        return self._create(LinregState, self.lib.sd_linreg_state_import, self.handle, int(exported["T"]), F, Cc, ptr(coef),
+                            ptr(_lib.as_f64(exported["intercept"])), ptr(_lib.as_f64(exported["fit_error"])), ptr(logit), ptr(dropped),
+                            ptr(_lib.as_i32(exported["status"])))
 
     def linreg_predict(self, state, Xq, out=None):
-        info = state.info()
-        Cc = info["C"]
-        if not isinstance(Xq, DeviceArray):
-            Xq = _lib.as_f64(Xq)
-        if len(Xq.shape) != 3 or Xq.shape[1] != info["F"] or Xq.shape[2] != Cc:
-            raise ValueError(f"Xq: expected a [Tq, {info['F']}, {Cc}] field, got shape {tuple(Xq.shape)}")
+        Xq, info, dev = self._queries("sd_linreg_predict", state, Xq)
+        Tq, Cc = Xq.shape[0], info["C"]
+        out = self._result_buffer(out, (Tq, 3, Cc), dev, "sd_linreg_predict")
         status = np.empty(Cc, dtype=np.int32)
-        if isinstance(Xq, DeviceArray):
-            Tq = Xq.shape[0]
-            out = self.empty((Tq, 3, Cc)) if out is None else out
+        if dev:
             check(self.lib.sd_linreg_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, out.vptr, out.ld, ptr(status)))
         else:
-            Xq = _lib.as_f64(Xq)
-            Tq = Xq.shape[0]
-            out = np.empty((Tq, 3, Cc))
             check(self.lib.sd_linreg_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(out), ptr(status)))
         return out, status
 
     # ---- ZScoreRegressor ----
     def zscore_fit(self, X, y, window_width, day_idx, year, D):
         """X, y [T, C] (numpy or DeviceArray); day_idx / year: host [T] (sd_zscore_fit) -> ZscoreState"""
-        X = self._field2("X", X)
-        y = self._field2("y", y, *X.shape)
+        X = self._field("X", X, "T", "C")
+        y = self._field("y", self._beside(X, y), *X.shape)
         T, Cc = X.shape
         day_idx, year = _lib.as_i32(day_idx), _lib.as_i32(year)
         if day_idx.shape != (T,) or year.shape != (T,):
             raise ValueError(f"day_idx and year: expected {T} entries, got {day_idx.shape} and {year.shape}")
-        h = C.c_void_p()
-        if isinstance(X, DeviceArray):
-            if not isinstance(y, DeviceArray) or X.ld != y.ld:
-                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
-            check(self.lib.sd_zscore_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(window_width), ptr(day_idx), ptr(year), int(D),
-                                             C.byref(h)))
-        else:
-            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
-            check(self.lib.sd_zscore_fit(self.handle, ptr(X), ptr(y), T, Cc, int(window_width), ptr(day_idx), ptr(year), int(D), C.byref(h)))
-        return ZscoreState(self, h.value, self.lib.sd_zscore_state_destroy)
+        if self._resident("sd_zscore_fit", ("X", "y"), self._ONE_PITCH, X=X, y=y):
+            return self._create(ZscoreState, self.lib.sd_zscore_fit_dev, self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(window_width),
+                                ptr(day_idx), ptr(year), int(D))
+        return self._create(ZscoreState, self.lib.sd_zscore_fit, self.handle, ptr(X), ptr(y), T, Cc, int(window_width), ptr(day_idx),
+                            ptr(year), int(D))
 
     def zscore_import(self, exported):
         """device state from ``ZscoreState.export()`` (pickling)"""
@@ -874,22 +858,20 @@ class Context:
         K, Cc = planes[0].shape
         if any(p.shape != (K, Cc) for p in planes):
             raise ValueError("zscore_import: the six planes must share one [K, C] shape")
-        h = C.c_void_p()
-        check(self.lib.sd_zscore_state_import(self.handle, K, Cc, int(exported["window_width"]), *[ptr(p) for p in planes],
-                                              ptr(_lib.as_i32(exported["status"])), C.byref(h)))
-        return ZscoreState(self, h.value, self.lib.sd_zscore_state_destroy)
+        return self._create(ZscoreState, self.lib.sd_zscore_state_import, self.handle, K, Cc, int(exported["window_width"]),
+                            *[ptr(p) for p in planes], ptr(_lib.as_i32(exported["status"])))
 
     def zscore_predict(self, state, Xp, out=None, with_stats=False):
         """Xp [Tp, C] -> (out [Tp, C], cell status [C], stats): stats = dict(meani, stdi, meanf, stdf) of [Tp, C] fields (on the
         device for a DeviceArray input) when ``with_stats``, else None"""
-        Cc = state.info()["C"]
-        Xp = self._field2("Xp", Xp, None, Cc)
+        Cc = self._info_of("sd_zscore_predict", state)["C"]
+        Xp = self._field("Xp", Xp, "T", Cc)
         Tp = Xp.shape[0]
-        dev = isinstance(Xp, DeviceArray)
-        out = self._result_buffer(out, (Tp, Cc), dev)
-        stats = {k: (self.empty((Tp, Cc)) if dev else np.empty((Tp, Cc))) for k in ("meani", "stdi", "meanf", "stdf")} if with_stats else None
-        if dev and stats is not None and out.ld != Cc:
+        dev = self._resident("sd_zscore_predict", Xp=Xp)
+        out = self._result_buffer(out, (Tp, Cc), dev, "sd_zscore_predict")
+        if dev and with_stats and out.ld != Cc:
             raise ValueError("zscore_predict: the stats fields share the pitch of `out`, which must be contiguous here")
+        stats = {k: (self.empty((Tp, Cc)) if dev else np.empty((Tp, Cc))) for k in ("meani", "stdi", "meanf", "stdf")} if with_stats else None
         sp = [None] * 4 if stats is None else [s.vptr if dev else ptr(s) for s in stats.values()]
         status = np.empty(Cc, dtype=np.int32)
         if dev:
@@ -901,24 +883,16 @@ class Context:
     # ---- GroupedRegressor ----
     def grouped_fit(self, X, y, key, n, window):
         """X [T, F, C], y [T, C] (numpy or DeviceArray); key: host [T] in [0, n) (sd_grouped_fit) -> GroupedState"""
-        if not isinstance(X, DeviceArray):
-            X = _lib.as_f64(X)
-        if len(X.shape) != 3:
-            raise ValueError(f"X: expected a [T, F, C] field, got shape {tuple(X.shape)}")
+        X = self._field("X", X, "T", "F", "C")
         T, F, Cc = X.shape
-        y = self._field2("y", y, T, Cc)
+        y = self._field("y", self._beside(X, y), T, Cc)
         key = _lib.as_i32(key)
         if key.shape != (T,):
             raise ValueError(f"key: expected {T} entries, got shape {key.shape}")
-        h = C.c_void_p()
-        if isinstance(X, DeviceArray):
-            if not isinstance(y, DeviceArray) or X.ld != y.ld:
-                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
-            check(self.lib.sd_grouped_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, F, Cc, ptr(key), int(n), int(window), C.byref(h)))
-        else:
-            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
-            check(self.lib.sd_grouped_fit(self.handle, ptr(X), ptr(y), T, F, Cc, ptr(key), int(n), int(window), C.byref(h)))
-        return GroupedState(self, h.value, self.lib.sd_grouped_state_destroy)
+        if self._resident("sd_grouped_fit", ("X", "y"), self._ONE_PITCH, X=X, y=y):
+            return self._create(GroupedState, self.lib.sd_grouped_fit_dev, self.handle, X.vptr, y.vptr, X.ld, T, F, Cc, ptr(key), int(n),
+                                int(window))
+        return self._create(GroupedState, self.lib.sd_grouped_fit, self.handle, ptr(X), ptr(y), T, F, Cc, ptr(key), int(n), int(window))
 
     def grouped_import(self, exported):
         """device state from ``GroupedState.export()`` (pickling)"""
@@ -927,25 +901,17 @@ class Context:
         fitted = _lib.as_i32(exported["fitted"])
         if icpt.shape != (n, Cc) or fitted.shape != (n,):
             raise ValueError("grouped_import: expected coef [n, F, C], intercept [n, C] and fitted [n]")
-        h = C.c_void_p()
-        check(self.lib.sd_grouped_state_import(self.handle, n, F, Cc, int(exported["window"]), ptr(coef), ptr(icpt), ptr(fitted),
-                                               ptr(_lib.as_i32(exported["status"])), C.byref(h)))
-        return GroupedState(self, h.value, self.lib.sd_grouped_state_destroy)
+        return self._create(GroupedState, self.lib.sd_grouped_state_import, self.handle, n, F, Cc, int(exported["window"]), ptr(coef),
+                            ptr(icpt), ptr(fitted), ptr(_lib.as_i32(exported["status"])))
 
     def grouped_predict(self, state, Xq, key, out=None):
         """Xq [Tq, F, C], key: host [Tq] -> (out [Tq, C], cell status [C]); a key without a fitted model is a ValueError"""
-        info = state.info()
-        Cc = info["C"]
-        if not isinstance(Xq, DeviceArray):
-            Xq = _lib.as_f64(Xq)
-        if len(Xq.shape) != 3 or Xq.shape[1] != info["F"] or Xq.shape[2] != Cc:
-            raise ValueError(f"Xq: expected a [Tq, {info['F']}, {Cc}] field, got shape {tuple(Xq.shape)}")
-        Tq = Xq.shape[0]
+        Xq, info, dev = self._queries("sd_grouped_predict", state, Xq)
+        Tq, Cc = Xq.shape[0], info["C"]
         key = _lib.as_i32(key)
         if key.shape != (Tq,):
             raise ValueError(f"key: expected {Tq} entries, got shape {key.shape}")
-        dev = isinstance(Xq, DeviceArray)
-        out = self._result_buffer(out, (Tq, Cc), dev)
+        out = self._result_buffer(out, (Tq, Cc), dev, "sd_grouped_predict")
         status = np.empty(Cc, dtype=np.int32)
         if dev:
             check(self.lib.sd_grouped_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, ptr(key), out.vptr, out.ld, ptr(status)))
@@ -956,21 +922,15 @@ class Context:
     # ---- PiecewiseLinearRegression(fit_option='arrm') ----
     def arrm_fit(self, X, y, max_breakpoints, with_r2=False):
         """X, y [T, C] (numpy or DeviceArray) -> ArrmState, or (ArrmState, r2 [T, C]) with ``with_r2`` (sd_arrm_fit)"""
-        X = self._field2("X", X)
-        y = self._field2("y", y, *X.shape)
+        X = self._field("X", X, "T", "C")
+        y = self._field("y", self._beside(X, y), *X.shape)
         T, Cc = X.shape
-        h = C.c_void_p()
-        if isinstance(X, DeviceArray):
-            if not isinstance(y, DeviceArray) or X.ld != y.ld:
-                raise ValueError("X and y: expected two DeviceArrays with the same row pitch")
+        if self._resident("sd_arrm_fit", ("X", "y"), self._ONE_PITCH, X=X, y=y):
             r2 = self.empty((T, Cc)) if with_r2 else None
-            check(self.lib.sd_arrm_fit_dev(self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(max_breakpoints), r2.vptr if with_r2 else None,
-                                           C.byref(h)))
+            state = self._create(ArrmState, self.lib.sd_arrm_fit_dev, self.handle, X.vptr, y.vptr, X.ld, T, Cc, int(max_breakpoints), vptr(r2))
         else:
-            y = _lib.as_f64(y.to_host() if isinstance(y, DeviceArray) else y)
             r2 = np.empty((T, Cc)) if with_r2 else None
-            check(self.lib.sd_arrm_fit(self.handle, ptr(X), ptr(y), T, Cc, int(max_breakpoints), ptr(r2), C.byref(h)))
-        state = ArrmState(self, h.value, self.lib.sd_arrm_state_destroy)
+            state = self._create(ArrmState, self.lib.sd_arrm_fit, self.handle, ptr(X), ptr(y), T, Cc, int(max_breakpoints), ptr(r2))
         return (state, r2) if with_r2 else state
 
     def arrm_import(self, exported):
@@ -980,18 +940,16 @@ class Context:
         index, ssr = _lib.as_i32(exported["break_index"]), _lib.as_f64(exported["ssr"])
         if beta.shape != (B, Cc) or index.shape != (B, Cc) or ssr.shape != (Cc,):
             raise ValueError("arrm_import: expected breaks, break_index and beta [B, C] and ssr [C]")
-        h = C.c_void_p()
-        check(self.lib.sd_arrm_state_import(self.handle, B, Cc, int(exported["T"]), ptr(breaks), ptr(index), ptr(beta), ptr(ssr),
-                                            ptr(_lib.as_i32(exported["status"])), C.byref(h)))
-        return ArrmState(self, h.value, self.lib.sd_arrm_state_destroy)
+        return self._create(ArrmState, self.lib.sd_arrm_state_import, self.handle, B, Cc, int(exported["T"]), ptr(breaks), ptr(index),
+                            ptr(beta), ptr(ssr), ptr(_lib.as_i32(exported["status"])))
 
     def arrm_predict(self, state, Xq, out=None):
         """Xq [Tq, C] -> (out [Tq, C], cell status [C])"""
-        Cc = state.info()["C"]
-        Xq = self._field2("Xq", Xq, None, Cc)
+        Cc = self._info_of("sd_arrm_predict", state)["C"]
+        Xq = self._field("Xq", Xq, "T", Cc)
         Tq = Xq.shape[0]
-        dev = isinstance(Xq, DeviceArray)
-        out = self._result_buffer(out, (Tq, Cc), dev)
+        dev = self._resident("sd_arrm_predict", Xq=Xq)
+        out = self._result_buffer(out, (Tq, Cc), dev, "sd_arrm_predict")
         status = np.empty(Cc, dtype=np.int32)
         if dev:
             check(self.lib.sd_arrm_predict_dev(self.handle, state.vptr, Xq.vptr, Xq.ld, Tq, out.vptr, out.ld, ptr(status)))
@@ -999,17 +957,14 @@ class Context:
             check(self.lib.sd_arrm_predict(self.handle, state.vptr, ptr(Xq), Tq, ptr(out), ptr(status)))
         return out, status
 
-
     # ---- regridding (GridArray.interp_like) ----
     def regrid_create(self, src_y, src_x, dst_y, dst_x, method="linear"):
         """Tables that take a [T, len(src_y), len(src_x)] field onto the (dst_y, dst_x) grid -> RegridState"""
         if method not in _lib.REGRID_METHODS:
             raise NotImplementedError(f"regrid method {method!r}: expected 'linear' or 'nearest'")
         sy, sx, dy, dx = (_lib.as_f64(np.ravel(a)) for a in (src_y, src_x, dst_y, dst_x))
-        h = C.c_void_p()
-        check(self.lib.sd_regrid_create(self.handle, _lib.REGRID_METHODS[method], len(sy), len(sx), ptr(sy), ptr(sx), len(dy), len(dx),
-                                        ptr(dy), ptr(dx), C.byref(h)))
-        return RegridState(self, h.value, self.lib.sd_regrid_destroy)
+        return self._create(RegridState, self.lib.sd_regrid_create, self.handle, _lib.REGRID_METHODS[method], len(sy), len(sx), ptr(sy),
+                            ptr(sx), len(dy), len(dx), ptr(dy), ptr(dx))
 
     # ---- conservative remapping (GridArray.remap_like) ----
     def remap_create(self, src_yb, src_xb, dst_yb, dst_xb):
@@ -1022,10 +977,8 @@ class Context:
             if a.ndim != 1 or len(a) < 2:
                 raise ValueError(f"{name}: expected the n + 1 bounds of n >= 1 cells, got shape {a.shape}")
             b[name] = _lib.as_f64(a)
-        h = C.c_void_p()
-        check(self.lib.sd_remap_create(self.handle, len(b["src_yb"]) - 1, len(b["src_xb"]) - 1, ptr(b["src_yb"]), ptr(b["src_xb"]),
-                                       len(b["dst_yb"]) - 1, len(b["dst_xb"]) - 1, ptr(b["dst_yb"]), ptr(b["dst_xb"]), C.byref(h)))
-        return RemapState(self, h.value, self.lib.sd_remap_destroy)
+        return self._create(RemapState, self.lib.sd_remap_create, self.handle, len(b["src_yb"]) - 1, len(b["src_xb"]) - 1, ptr(b["src_yb"]),
+                            ptr(b["src_xb"]), len(b["dst_yb"]) - 1, len(b["dst_xb"]) - 1, ptr(b["dst_yb"]), ptr(b["dst_xb"]))
 
     def remap_host(self, field, src_yb, src_xb, dst_yb, dst_xb, min_valid=0.5):
         """host [T, ny, nx] -> host [T, Ny * Nx]: tables, upload, run, download (sd_remap_create + sd_remap_apply)"""
@@ -1062,11 +1015,6 @@ class Context:
         finally:
             for a in mine:
                 a.free()
-
-    def _same_context(self, who, **arrays):
-        for name, a in arrays.items():
-            if a is not None and a.ctx is not self:
-                raise ValueError(f"sd_downscale: {who}: `{name}` belongs to another context")
 
     # ---- resampling of the time axis (GridArray.resample) ----
     @staticmethod

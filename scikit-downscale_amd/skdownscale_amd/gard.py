@@ -15,7 +15,7 @@ from sklearn.base import BaseEstimator, RegressorMixin
 from sklearn.exceptions import NotFittedError
 
 from . import _lib
-from .base import LINEAR_NEUTRAL, LOGISTIC_NEUTRAL, _finite_error, check_sklearn_kwargs
+from .base import LINEAR_NEUTRAL, LOGISTIC_NEUTRAL, _finite_error, _to_2d, check_sklearn_kwargs
 from .engine import default_context
 
 KIND_CODES = {"best_analog": _lib.ANALOG_BEST, "sample_analogs": _lib.ANALOG_SAMPLE,
@@ -80,11 +80,7 @@ def check_tree_kwargs(model):
 
 
 def _as_2d(X, name="X"):
-    a = np.asarray(X.values if isinstance(X, (pd.DataFrame, pd.Series)) else X, dtype=np.float64)
-    if a.ndim == 1 and name == "X":
-        raise ValueError(
-            f"Expected 2D array, got 1D array instead:\narray={a}.\nReshape your data either using array.reshape(-1, 1) "
-            "if your data has a single feature or array.reshape(1, -1) if it contains a single sample.")
+    a = _to_2d(X, name)
     if not np.isfinite(a).all():
         raise _finite_error(name, a)
     return a
