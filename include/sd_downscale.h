@@ -140,6 +140,14 @@ extern "C" {
 #define SD_SPELL_LONGEST_SPELL 3  /* the longest run of consecutive hits */
 #define SD_SPELL_SPELL_DAYS 4     /* steps inside runs of at least min_length hits */
 #define SD_SPELL_SPELL_COUNT 5    /* runs of at least min_length hits */
+/* sd_skill: statistics of a bin of two fields a and b, from the sums over its valid pairs */
+#define SD_SKILL_COUNT 0      /* n: the valid pairs */
+#define SD_SKILL_BIAS 1       /* sd / n */
+#define SD_SKILL_RATIO 2      /* sa / sb */
+#define SD_SKILL_MAE 3        /* sabs / n */
+#define SD_SKILL_RMSE 4       /* sqrt(sq / n) */
+#define SD_SKILL_CORR 5       /* qab / (sqrt(qaa) * sqrt(qbb)), clamped to [-1, 1] */
+#define SD_SKILL_STD_RATIO 6  /* sqrt(qaa / qbb) */
 
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
@@ -622,6 +630,40 @@ int sd_spells_dev(sd_ctx* ctx, const void* src_dev, int src_is_f32, int64_t ld, 
 int sd_spells(sd_ctx* ctx, const void* src_host, int src_is_f32, int64_t T, int64_t C, int op, double threshold,
               const double* table_host_or_null, const int32_t* group_or_null, int64_t G, const int64_t* offsets, int64_t M, int64_t min_length,
               const int* stats, int nstat, double* out_host);
+
+/* ---- paired skill statistics per period: GridArray.compare(other).resample(time=rule).bias() / .rmse() / .corr() ... ----
+ * a and b are [T, C] fields (cells fastest, rows ld_a, ld_b >= C elements apart; each float64, or float32 with its is_f32 != 0); they
+ * may be the same pointer.  The bins are those of sd_resample: offsets, a host array of M + 1 entries that starts at 0, never
+ * decreases and ends at T.  Nothing is aligned or broadcast: row r of a is paired with row r of b.
+ *
+ * The rule, per cell over the steps of one bin in time order.  A float32 sample is widened to double first.  A step is a valid pair
+ * when neither a nor b is NaN; +-inf are ordinary values and IEEE arithmetic follows from them.  Every sum starts at +0.0 and adds one
+ * term per valid pair in time order, ((+0.0 + t1) + t2) + ...; an invalid pair adds +0.0.  No contraction (-ffp-contract=off): a
+ * product and the addition of it are two operations.
+ *   pass 1:  n = the valid pairs;  sa = sum a;  sb = sum b;  sd = sum (a - b);  sabs = sum |a - b|;  sq = sum (a - b) * (a - b)
+ *   pass 2 (only if SD_SKILL_CORR or SD_SKILL_STD_RATIO is asked for):  ma = sa / n, mb = sb / n;
+ *            qaa = sum (a - ma) * (a - ma);  qbb = sum (b - mb) * (b - mb);  qab = sum (a - ma) * (b - mb)
+ * out holds nstat float64 fields [M, C] (rows ld_out >= C apart, the fields stride_out >= M * ld_out elements apart): field s is the
+ * statistic stats[s] (a host array of nstat codes, 1 <= nstat <= 7; a code may repeat):
+ *   SD_SKILL_COUNT      n; 0 for an empty or all-invalid bin
+ *   SD_SKILL_BIAS       sd / n
+ *   SD_SKILL_RATIO      sa / sb as IEEE gives it
+ *   SD_SKILL_MAE        sabs / n
+ *   SD_SKILL_RMSE       sqrt(sq / n)
+ *   SD_SKILL_CORR       qab / (sqrt(qaa) * sqrt(qbb)) clamped to [-1, 1], NaN staying NaN; NaN where n < 2, qaa == 0 or qbb == 0
+ *   SD_SKILL_STD_RATIO  sqrt(qaa / qbb); NaN where n < 2
+ * Every statistic but SD_SKILL_COUNT is NaN where n == 0.  Each value is one fixed sequence of IEEE operations: the result is the
+ * same bit for bit whatever the layout, the leading dimensions or the launch geometry.
+ *
+ * An unknown statistic code, nstat outside 1 .. 7, sizes <= 0, T >= 2^31 (the counts are int32), a leading dimension below C,
+ * stride_out < M * ld_out, a field too large and a table of bins that breaks the rules above are SD_ERR_INVALID, in this order,
+ * refused before anything is allocated or launched. */
+int sd_skill_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, const void* b_dev, int b_is_f32, int64_t ld_b, int64_t T,
+                 int64_t C, const int64_t* offsets, int64_t M, const int* stats, int nstat, double* out_dev, int64_t ld_out,
+                 int64_t stride_out);
+/* host buffers: a, b [T, C], out [nstat * M, C]; upload, run, download */
+int sd_skill(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
+             const int64_t* offsets, int64_t M, const int* stats, int nstat, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

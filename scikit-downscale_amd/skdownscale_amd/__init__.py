@@ -17,6 +17,7 @@ from .groupby import GridGroupBy, GroupAppliedGridArray, GroupReducedGridArray, 
 from .rolling import GridRolling, RolledGridArray
 from .order_stats import TimeQuantileGridArray
 from .spells import GridCondition, SpellGridArray
+from .skill import GridComparison, SkillGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -71,5 +72,7 @@ __all__ = [
     "TimeQuantileGridArray",
     "GridCondition",
     "SpellGridArray",
+    "GridComparison",
+    "SkillGridArray",
 ]
 __version__ = "0.1.0"

@@ -234,6 +234,23 @@ class GridArray:
 
         return GridCondition(self, op, threshold, dim, by, name, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
 
+    def compare(self, other, dim="time", scratch_bytes=None):
+        """``compare(obs).resample(time="YS").rmse()``: paired skill statistics per period and cell on the GPU, both fields walked in
+        lock-step.  ``other``: a ``GridArray`` of any kind, lazy ones included, with the same dims (in any order) and the same size on
+        every dim; where both arrays carry a coordinate for ``dim`` the two must be equal.  Nothing is aligned or broadcast: anything
+        else is a ``ValueError``.  A step is a valid pair when neither sample is NaN (float32 samples are widened first); every sum
+        runs over the valid pairs of a bin in time order.  -> ``GridComparison``: nothing is computed yet.  Its
+        ``resample(time=rule, **pandas_kw)`` cuts the axis into pandas' bins; without it the whole axis is one bin, the dim is dropped
+        and both whole fields are held in HBM.  ``count()``, ``bias()`` (mean of a - b), ``ratio()`` (sum a / sum b: precipitation's
+        relative bias), ``mae()``, ``rmse()``, ``corr()`` (Pearson, NaN for fewer than two pairs or a constant series) and
+        ``std_ratio()`` give a lazy ``SkillGridArray`` (float64; NaN for a bin without a valid pair, ``count`` 0); ``indices(names)``
+        several of them behind a leading ``"index"`` dim from one call.  The summation order is fixed: the result does not depend on
+        ``scratch_bytes`` (device scratch of one block of whole bins of both fields together, default 1 GiB; at least one bin)."""
+        from .resample import DEFAULT_SCRATCH_BYTES
+        from .skill import GridComparison
+
+        return GridComparison(self, other, dim, DEFAULT_SCRATCH_BYTES if scratch_bytes is None else scratch_bytes)
+
     def disaggregate(self, daily_obs, kind="shift", stat=None, years=None, seed=0, climatology=None, scratch_bytes=1 << 30, dim="time"):
         """Temporal disaggregation of this monthly array on the GPU (the last step of BCSD, Wood et al. 2004): every month becomes
         daily weather by borrowing the daily pattern of a historical month of ``daily_obs`` -- the same one for every cell -- and

@@ -1130,6 +1130,68 @@ class Context:
                                  1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), len(codes), ptr(out)))
         return out
 
+    # ---- paired skill statistics per bin of the time axis (GridArray.compare) ----
+    @staticmethod
+    def _skill_args(a, b, offsets, stats):
+        stats = [stats] if isinstance(stats, str) else list(stats)
+        for s in stats:
+            if s not in _lib.SKILL_STATS:
+                raise ValueError(f"skill statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SKILL_STATS)}")
+        if not 1 <= len(stats) <= len(_lib.SKILL_STATS):
+            raise ValueError(f"sd_downscale: sd_skill: nstat = {len(stats)}, expected 1 to {len(_lib.SKILL_STATS)} statistics")
+        a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
+        T, Cc = a.shape
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
+        M = len(offsets) - 1
+        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_skill: bad sizes (T={T}, C={Cc}, M={M})")
+        codes = np.ascontiguousarray([_lib.SKILL_STATS[s] for s in stats], dtype=np.intc)
+        return a, b, offsets, codes
+
+    def skill(self, a, b, offsets, stats, out=None, plane_rows=None):
+        """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
+        may be the same array), paired row by row; offsets: host int64 [M + 1], bin m = rows offsets[m] .. offsets[m + 1] - 1; stats:
+        one name or a list of 'count' | 'bias' | 'ratio' | 'mae' | 'rmse' | 'corr' | 'std_ratio' -> [nstat * M, C] float64 DeviceArray,
+        row ``s * M + m`` the statistic s of bin m; both fields are read once, or twice where 'corr' or 'std_ratio' is among them
+        (sd_skill_dev; the rule is in include/sd_downscale.h).  ``out`` and ``plane_rows``: as for ``spells``."""
+        a, b, offsets, codes = self._skill_args(a, b, offsets, stats)
+        T, Cc = a.shape
+        M, nstat = len(offsets) - 1, len(codes)
+        if plane_rows is None:
+            out = self._result_buffer(out, (nstat * M, Cc), True)
+            stride = M * out.ld
+        else:
+            out = self._result_buffer(out, (M, Cc), True)
+            base = out.base
+            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
+            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
+                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
+            stride = int(plane_rows) * out.ld
+        with self._uploads() as up:
+            same = b is a
+            a = up(a, a.dtype)
+            b = a if same else up(b, b.dtype)
+            self._same_context("sd_skill", a=a, b=b, out=out)
+            check(self.lib.sd_skill_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T, Cc,
+                                        ptr(offsets), M, ptr(codes), nstat, out.vptr, out.ld, stride))
+        return out
+
+    def skill_host(self, a, b, offsets, stats):
+        """host [T, C] twice -> host [nstat * M, C] through sd_skill (upload, run, download in one call)"""
+        a, b, offsets, codes = self._skill_args(a, b, offsets, stats)
+        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
+            raise ValueError("skill_host: expected host arrays")
+        T, Cc = a.shape
+        M = len(offsets) - 1
+        out = np.empty((len(codes) * M, Cc))
+        check(self.lib.sd_skill(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(offsets), M,
+                                ptr(codes), len(codes), ptr(out)))
+        return out
+
     # ---- temporal disaggregation (GridArray.disaggregate) ----
     @staticmethod
     def _disagg_args(target, obs, src_row, offsets, op, climo, group):

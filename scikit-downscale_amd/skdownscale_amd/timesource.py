@@ -1,5 +1,5 @@
 """How the source of a lazy time-axis array comes into HBM: the one place that decides it for ``resample``, ``groupby``, ``rolling``,
-``quantile`` / ``median``, ``where``, ``remap_like`` and ``disaggregate``.
+``quantile`` / ``median``, ``where``, ``compare``, ``remap_like`` and ``disaggregate``.
 
 A source is one of three things.  A not yet computed lazy array of a kind the consumer accepts (``TAKEN_WHOLE``) whose
 ``_row_dim()`` is the walked dim gives its whole [T, C] field through its own ``device_field`` and stays uncomputed.  A lazy array
@@ -7,10 +7,12 @@ with a ``_block_producer`` (an unchunked ``coarse.interp_like(obs)``, a ``fine.r
 HBM, rows [r0, r1) at a time.  Anything else is a host array -- a computed lazy array is one -- whose rows are uploaded, float32 as
 float32.  ``walk`` cuts the axis by the consumer's plan, fills one block of device scratch after the other and owns every buffer it
 made: scratch and a lazy source's field are freed when the ``with`` block ends, the result only when it ends in an exception.
+``walk_pair`` walks two sources in lock-step (``compare``): one ``walk`` each, cut at the same bins.
 """
 from __future__ import annotations
 
 import collections
+import contextlib
 
 from . import _lib
 from .core import DeferredGridArray
@@ -22,7 +24,7 @@ TAKEN_WHOLE = {
     "resample": frozenset(),
     "groupby": _REDUCED,  # the source of GroupReducedGridArray and GroupAppliedGridArray
     "rolling": _TABLES,
-    "any": _TABLES | {"disagg", "remap"},  # TimeQuantileGridArray, SpellGridArray
+    "any": _TABLES | {"disagg", "remap"},  # TimeQuantileGridArray, SpellGridArray, SkillGridArray (both sources)
     "remap": _TABLES | {"disagg"},  # dims must be (lead, *spatial)
     "table": frozenset({"group_reduced", "rolling", "quantile"}),  # GroupAppliedGridArray's other: dims must be in order
     "target": frozenset({"resample"}),  # DisaggregatedGridArray's monthly field: dims must be in order
@@ -77,6 +79,11 @@ def upload_rows(rows):
     return RowProducer(rows.shape[0], rows.shape[1], rows.dtype, lambda r0, r1, out: out.copy_from_host(rows[r0:r1]), True)
 
 
+def producer_of(source, dim, ctx):
+    """the ``RowProducer`` of a source that is not taken whole: a lazy array's own block producer, else the upload of its host rows"""
+    return (source._block_producer(ctx, dim) if isinstance(source, DeferredGridArray) else None) or upload_rows(host_rows(source, dim))
+
+
 def takes_whole(source, consumer, dim):
     """whether ``consumer`` takes ``source`` from HBM as [steps of ``dim``, C] through the source's own ``device_field``"""
     return (isinstance(source, DeferredGridArray) and source._kind in TAKEN_WHOLE[consumer] and not source.computed
@@ -98,12 +105,12 @@ class walk:
     halo; a lazy source the consumer takes whole is one block.  ``w.result(shape)`` allocates a float64 result.  Leaving the ``with``
     block frees the scratch or the lazy source's field, and after an exception the results as well."""
 
-    def __init__(self, source, dim, ctx, scratch_bytes, consumer=None, halo=None, bins=None, whole=False, verb="group"):
-        self._args = source, dim, int(scratch_bytes), consumer, halo, bins, whole, verb
+    def __init__(self, source, dim, ctx, scratch_bytes, consumer=None, halo=None, bins=None, whole=False, verb="group", row_budget=None):
+        self._args = source, dim, int(scratch_bytes), consumer, halo, bins, whole, verb, row_budget
         self._ctx, self._buffer, self._results, self._producer, self._piece = ctx, None, [], None, None
 
     def __enter__(self):
-        source, dim, scratch_bytes, consumer, halo, bins, whole, verb = self._args
+        source, dim, scratch_bytes, consumer, halo, bins, whole, verb, row_budget = self._args
         p = None
         if isinstance(source, RowProducer):
             p = source
@@ -112,12 +119,13 @@ class walk:
             T, C = field.shape
             max_rows = T  # (one block)
         else:
-            p = (source._block_producer(self._ctx, dim) if isinstance(source, DeferredGridArray) else None) or upload_rows(host_rows(source, dim))
+            p = producer_of(source, dim, self._ctx)
         if p is not None:
             T, C = p.rows, p.cells
             if min(T, C) < 1:
                 raise ValueError(f"nothing to {verb}: the array has sizes {source.sizes}")
-            max_rows = max(1, scratch_bytes // (C * p.dtype.itemsize))
+            # (``row_budget``: the rows of a block as ``walk_pair`` shares them between two sources, in place of this source's own)
+            max_rows = max(1, scratch_bytes // (C * p.dtype.itemsize)) if row_budget is None else max(1, int(row_budget))
             if whole:
                 self._piece, max_rows = (None if p.uploads else max_rows), T
         if bins is not None:
@@ -153,3 +161,48 @@ class walk:
         for a in [self._buffer] + (self._results if exc_type is not None else []):
             a.free()
         return False
+
+
+class walk_pair:
+    """``with walk_pair(a, b, dim, ctx, scratch_bytes, consumer, bins=offsets) as w: for i0, i1, block_a, block_b, b0 in w: ...``: two
+    sources of the same steps and cells walked in lock-step, each through a ``walk`` of its own.  If neither is a lazy array the
+    consumer takes whole from HBM, both are cut into the same runs of whole bins, sized so that the two blocks together stay within
+    ``scratch_bytes`` (at least one bin).  If one is taken whole, the other is brought in whole too (``whole=True``).  A bin always lies
+    within one block of both.  ``w.cells``, ``w.result(shape)`` and the freeing of every buffer are those of ``walk``."""
+
+    def __init__(self, a, b, dim, ctx, scratch_bytes, consumer, bins, verb="compare"):
+        self._args = a, b, dim, int(scratch_bytes), consumer, bins, verb
+        self._ctx, self._stack, self._walks = ctx, None, None
+
+    def __enter__(self):
+        a, b, dim, scratch_bytes, consumer, bins, verb = self._args
+        for s in (a, b):
+            if min(s.sizes.values(), default=1) < 1:
+                raise ValueError(f"nothing to {verb}: the array has sizes {s.sizes}")
+        if takes_whole(a, consumer, dim) or takes_whole(b, consumer, dim):
+            plans = [dict(source=s, whole=True) for s in (a, b)]
+        else:
+            pa, pb = producer_of(a, dim, self._ctx), producer_of(b, dim, self._ctx)
+            if (pa.rows, pa.cells) != (pb.rows, pb.cells):
+                raise ValueError(f"the sources differ: [{pa.rows}, {pa.cells}] and [{pb.rows}, {pb.cells}] steps by cells")
+            budget = max(1, scratch_bytes // (pa.cells * (pa.dtype.itemsize + pb.dtype.itemsize)))
+            plans = [dict(source=p, row_budget=budget) for p in (pa, pb)]
+        with contextlib.ExitStack() as stack:
+            self._walks = [stack.enter_context(walk(p.pop("source"), dim, self._ctx, scratch_bytes, consumer, bins=bins, verb=verb, **p))
+                           for p in plans]
+            wa, wb = self._walks
+            if wa.cells != wb.cells or [k[:2] for k in wa._blocks] != [k[:2] for k in wb._blocks]:
+                raise ValueError(f"the sources differ: {wa.cells} and {wb.cells} cells per step")
+            self.cells = wa.cells
+            self._stack = stack.pop_all()
+        return self
+
+    def result(self, shape, out=None):
+        return self._walks[0].result(shape, out)
+
+    def __iter__(self):
+        for (i0, i1, block_a, b0), (_, _, block_b, _) in zip(*self._walks):
+            yield i0, i1, block_a, block_b, b0
+
+    def __exit__(self, exc_type, exc, tb):
+        return self._stack.__exit__(exc_type, exc, tb)

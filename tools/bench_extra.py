@@ -596,9 +596,72 @@ def bench_spells(ctx, args):
     return res
 
 
+def bench_skill(ctx, args):
+    """skill_kernel on 14 600 daily steps x 100 000 cells, float64 against float64 (a synthetic downscaled field against synthetic
+    observations), with one whole-axis bin and with 'YS' bins: ["bias", "rmse"] (one pass over both fields) and ["bias", "rmse", "corr"]
+    (two passes), each timed through ctx.prof() -- median and [min, max] of 7 profiled calls after a warm-up -- beside sd_memcpy_d2d of
+    the same source bytes (both fields) and beside spells_kernel (one statistic of a scalar threshold over the same bins of one field)
+    in the same run; GB/s by algorithmic bytes (16 * T * C read per pass + 8 * nstat * M * C written); the first 256 cells compared bit
+    for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _skill_oracle as sk
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    labels, yearly = time_bins(index, "YS")
+    tabs = synth.tas_tables(index)
+
+    def fill(cells, tab):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(call, kernel, repeats):
+        call()
+        ctx.prof_enable(True)
+        times = []
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            times.append(ctx.prof()[kernel]["ms"])
+        ctx.prof_enable(False)
+        return {"kernel_ms": float(np.median(times)), "kernel_ms_min_max": [min(times), max(times)]}
+
+    a, b = fill(C, tabs["X_hist"]), fill(C, tabs["y_obs"])
+    first_a, first_b = fill(256, tabs["X_hist"]).to_host(), fill(256, tabs["y_obs"]).to_host()
+    repeats = 7
+    src_bytes = 2 * 8 * T * C
+    spare = ctx.empty((T, C))
+    one_ms, one_min_max = device_copy_ms(ctx, spare, a, src_bytes // 2, repeats)  # (two copies of one field's bytes: the same bytes moved)
+    spare.free()
+    copy_ms = 2 * one_ms
+    res = {"workload": f"skill {T} daily steps x {C} cells float64 against float64: one whole-axis bin and {len(labels)} 'YS' bins; bias, rmse (one pass) and bias, rmse, corr (two passes)",
+           "repeats": repeats, "device_copy": {"ms": copy_ms, "ms_of_one_field_min_max": one_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6}}
+    for bins_name, offsets in (("whole_axis", np.array([0, T], dtype=np.int64)), ("YS", np.asarray(yearly, dtype=np.int64))):
+        M = len(offsets) - 1
+        count = ctx.empty((M, C))
+        sp_r = timed(lambda: ctx.spells(b, ">", 13.0, offsets, ["count"], out=count), "spells_kernel", repeats)
+        sp_r["algorithmic_bytes"] = 8 * T * C + 8 * M * C
+        sp_r["GBps"] = sp_r["algorithmic_bytes"] / sp_r["kernel_ms"] / 1e6
+        count.free()
+        res[f"{bins_name}_spells_kernel_count"] = sp_r
+        for stats, passes in ((["bias", "rmse"], 1), (["bias", "rmse", "corr"], 2)):
+            out = ctx.empty((len(stats) * M, C))
+            r = timed(lambda: ctx.skill(a, b, offsets, stats, out=out), "skill_kernel", repeats)
+            ms = r["kernel_ms"]
+            nbytes = passes * src_bytes + 8 * len(stats) * M * C
+            got, want = out.cells(0, 256).to_host(), sk.skill(first_a, first_b, offsets, stats)
+            r.update({"statistics": stats, "passes": passes, "bins": M, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                      "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": bool(np.array_equal(got, want, equal_nan=True)),
+                      "kernel_over_copy_ms": ms / copy_ms, "read_rate_over_copy": (passes * src_bytes / ms) / (src_bytes / copy_ms),
+                      "read_rate_over_spells": (passes * src_bytes / ms) / (8 * T * C / sp_r["kernel_ms"])})
+            res[f"{bins_name}_{'_'.join(stats)}"] = r
+            out.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -617,9 +680,9 @@ def main():
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
         return
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells", "skill"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
-                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells}[args.workload](ctx, args))
+                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells, "skill": bench_skill}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
