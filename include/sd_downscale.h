@@ -70,6 +70,8 @@ extern "C" {
 #define SD_CELL_BAD_CLIMO 3 /* bcsd.py:140-141: y climatology <= 0 with return_anoms */
 #define SD_CELL_ONE_CLASS 4 /* gard.py:204-212: a thresholded regression met samples of one class only where the reference's
                              * LogisticRegression.fit raises -> ValueError on host */
+#define SD_CELL_EMPTY_RANGE 5 /* arrm.py:95: the smallest upper pick of an ARRM fit is 6, so the lower picks would come from
+                               * r2[:0] and the reference's np.argmin raises -> ValueError on host; no model for the cell */
 
 /* PureAnalog kinds (gard.py:258-262) */
 #define SD_ANALOG_BEST 0

@@ -8,6 +8,8 @@
 //                          HBM / L2, each thread sums its first window directly around a pivot at the window's centre and slides
 //                          to its next windows.  Of two windows that share a slot only the one the reference writes last stores.
 //                          Then the reference's sequence as it stands: upper picks with their masks, the lower windows, lower picks.
+//                          A cell whose lower range is empty (smallest upper pick 6), where the reference's argmin raises, gets
+//                          SDI_EMPTY_RANGE and no model.
 //   arrm_accum_kernel      one pass over the original (x, y) pairs, [T, C] with coalesced rows: the Gram sums of the hat-function
 //                          basis on the cell's knots, five per segment, in LDS per thread; fixed-order reduction.
 //   arrm_solve_kernel      one thread per cell: equilibrated tridiagonal Cholesky, conversion to pwlf's beta, minimum-norm
@@ -152,7 +154,7 @@ __device__ __forceinline__ void ar_mask(double* r2, int i, int T) {
 
 __global__ void __launch_bounds__(kWindowThreads) arrm_select_kernel(const double* __restrict__ xs_all, const double* __restrict__ ys_all, int T,
                                                                      int64_t C, int start, int w, int half,
-                                                                     const int32_t* __restrict__ status, double* __restrict__ breaks,
+                                                                     int32_t* status, double* __restrict__ breaks,
                                                                      int32_t* __restrict__ break_index, double* __restrict__ diag_all) {
     extern __shared__ double r2[];  // [T]
     __shared__ double red_v[kWindowThreads];
@@ -188,6 +190,14 @@ __global__ void __launch_bounds__(kWindowThreads) arrm_select_kernel(const doubl
         int start2 = picks[0];
         for (int k = 1; k < half; ++k) start2 = min(start2, picks[k]);
         start2 -= kMinWidth / 2 + 1;
+        if (start2 == 0) {  // (uniform) arrm.py:95: r2[:0] is empty and np.argmin raises: the cell gets no model, r2 keeps the upper windows
+            if (tid < B) {
+                breaks[(int64_t)tid * C + c] = ar_nan();
+                break_index[(int64_t)tid * C + c] = -1;
+            }
+            if (tid == 0) status[c] = SDI_EMPTY_RANGE;  // (read again by this workgroup only at its next cell; the later kernels see it)
+            continue;
+        }
         if (start2 >= 0) ar_window_pass(xs, ys, T, w, 0, start2, false, r2, diag, C);  // left = start2 .. 0
         __syncthreads();
         const int limit = start2 >= 0 ? start2 : T + start2;  // r2[:start2]
@@ -518,7 +528,7 @@ int sd_arrm_fit_dev(sd_ctx* ctx, const double* X_dev, const double* y_dev, int64
         SD_TRY(allow_lds(&arrm_select_kernel, pl.select));
         SD_LAUNCH(ctx, "arrm_select_kernel", arrm_select_kernel, grid_of(pl.select), dim3(pl.select.block), pl.select.lds,
                   (const double*)sorted->xs, (const double*)sorted->ys, (int)T, C, (int)pl.start, (int)pl.width, pl.half,
-                  (const int32_t*)st->status, st->breaks, st->break_index, r2_dev);
+                  st->status, st->breaks, st->break_index, r2_dev);
         sd_scratch part;
         SD_HIP(part.alloc(ctx, sizeof(double) * (size_t)pl.slices * pl.nacc * C));
         SD_TRY(allow_lds(&arrm_accum_kernel, pl.accum));

@@ -83,6 +83,7 @@ static inline QmDevSwitches sd_qm_dev_switches() {
 #define SDI_NONFINITE 2
 #define SDI_BAD_CLIMO 4
 #define SDI_ONE_CLASS 8
+#define SDI_EMPTY_RANGE 16
 
 struct sd_prof_entry {
     double ms = 0.0;
@@ -279,6 +280,7 @@ __host__ __device__ static inline int32_t sd_public_status(int32_t bits) {
     if (bits & SDI_NONFINITE) return SD_CELL_NONFINITE;
     if (bits & SDI_BAD_CLIMO) return SD_CELL_BAD_CLIMO;
     if (bits & SDI_ONE_CLASS) return SD_CELL_ONE_CLASS;
+    if (bits & SDI_EMPTY_RANGE) return SD_CELL_EMPTY_RANGE;
     return SD_CELL_OK;
 }
 static inline int32_t sd_internal_status(int32_t code) {
@@ -287,6 +289,7 @@ static inline int32_t sd_internal_status(int32_t code) {
         case SD_CELL_NONFINITE: return SDI_NONFINITE;
         case SD_CELL_BAD_CLIMO: return SDI_BAD_CLIMO;
         case SD_CELL_ONE_CLASS: return SDI_ONE_CLASS;
+        case SD_CELL_EMPTY_RANGE: return SDI_EMPTY_RANGE;
         default: return 0;
     }
 }

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SD_DOWNSCALE_LIB", os.path.join(os.path.dirname(_HERE
 SD_OK = 0
 BCSD_TAS, BCSD_PR = 0, 1
 BCSD_RETURN_ANOMS, BCSD_QM_DETREND = 1, 2  # bits of the `return_anoms` argument of the fit entry points
-CELL_OK, CELL_MASKED, CELL_NONFINITE, CELL_BAD_CLIMO, CELL_ONE_CLASS = 0, 1, 2, 3, 4
+CELL_OK, CELL_MASKED, CELL_NONFINITE, CELL_BAD_CLIMO, CELL_ONE_CLASS, CELL_EMPTY_RANGE = 0, 1, 2, 3, 4, 5
 ANALOG_BEST, ANALOG_SAMPLE, ANALOG_WEIGHT, ANALOG_MEAN = 0, 1, 2, 3
 QM_REGRESSOR, QM_EDCDF_DIFFERENCE, QM_EDCDF_RATIO = 0, 1, 2
 CUNNANE_FORWARD, CUNNANE_INVERSE = 0, 1

@@ -24,6 +24,7 @@ MIN_SAMPLES = 50
 MAX_BREAKS = 16
 # pwlf.PiecewiseLinFit keywords that cannot change the fitted model
 PWLF_NEUTRAL = {"disp_res": None, "lapack_driver": None, "seed": None, "degree": (1,), "weights": (None,)}
+EMPTY_RANGE_MESSAGE = "attempt to get argmin of an empty sequence"  # arrm.py:95, np.argmin(r2[:0])
 STOCHASTIC = ("fit_option='{}' runs pwlf's stochastic optimiser ({}), which the HIP engine does not offer: use fit_option='arrm', "
               "the deterministic breakpoint search")
 
@@ -68,6 +69,13 @@ class ArrmGridModel:
         res = self.ctx.arrm_fit(X, y, self.max_breakpoints, with_r2=with_r2)
         self.state, self.r2_ = res if with_r2 else (res, None)
         self.status_ = self.state.status()
+        # arrm.py:95: a cell whose smallest upper pick is 6 leaves r2[:0] for the lower picks, and the reference's np.argmin raises.
+        # The per-cell loop stops at the first cell that fails: a non-finite cell before it is the caller's to report.
+        empty = np.flatnonzero(self.status_ == _lib.CELL_EMPTY_RANGE)
+        if len(empty) and not (self.status_[:empty[0]] == _lib.CELL_NONFINITE).any():
+            self.state.close()
+            self.state = None
+            raise ValueError(EMPTY_RANGE_MESSAGE)
         return self
 
     def predict(self, Xq, out=None):

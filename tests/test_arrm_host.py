@@ -126,3 +126,52 @@ def test_fitted_model_object_predicts_like_the_oracle(golden):
     m = FittedPiecewiseModel(g["breaks"][:, 0], g["beta"][:, 0], g["ssr"][0])
     assert (m.n_segments, m.n_parameters) == (5, 6)
     assert np.allclose(m.predict(g["Xq"][:, 0]), g["pred"][:, 0], rtol=1e-13, atol=0)
+
+
+@pytest.fixture(scope="module")
+def golden_breaks():
+    return {c: ao.breaks_case(c) for c in ao.CASES_BREAKS}
+
+
+@pytest.mark.parametrize("c", ao.CASES_BREAKS)
+def test_oracle_reproduces_the_break_goldens(golden_breaks, c):
+    """g24: every cell's picks, breaks and start2 recorded from the reference, and the reference's ValueError exactly where the
+    ``raises`` flag says (start2 == 0: np.argmin of r2[:0])"""
+    g = golden_breaks[c]
+    for k in range(g["X"].shape[1]):
+        if g["raises"][k]:
+            with pytest.raises(ValueError, match="^attempt to get argmin of an empty sequence$"):
+                ao.breakpoints(g["X"][:, k], g["y"][:, k], 0.05, g["mb"])
+            assert g["start2"][k] == 0 and (g["index"][:, k] == -1).all() and np.isnan(g["breaks"][:, k]).all()
+            continue
+        o = ao.breakpoints(g["X"][:, k], g["y"][:, k], 0.05, g["mb"])
+        assert np.array_equal(o["index"], g["index"][:, k]) and np.array_equal(o["breaks"], g["breaks"][:, k]), (c, k)
+        assert o["start2"] == g["start2"][k] != 0 and o["sentinel_picks"] == g["sentinel"][k]
+        assert o["margin_computed"] == g["margin_computed"][k] >= o["margin"] == g["margin"][k]
+        assert np.array_equal(o["r2"], g["r2"][:, k], equal_nan=True)
+
+
+def test_break_goldens_cover_their_territory(golden_breaks):
+    short = [g for c, g in golden_breaks.items() if c.startswith("short")]
+    assert sum(int(g["raises"].sum()) for g in short) >= 1 and all(g["raises"].mean() <= 0.5 for g in short)
+    assert any((g["start2"] < 0).any() for g in short) and any((g["sentinel"] > 0).any() for g in short)
+    for c, g in golden_breaks.items():
+        live = ~g["raises"]
+        assert (g["margin_computed"][live] < 1e-6).mean() <= 0.05, c
+    assert not any(g["raises"].any() for c, g in golden_breaks.items() if not c.startswith("short"))
+    assert np.isnan(golden_breaks["quant300_mb8"]["r2"]).any(axis=0).all()
+    widths = {c: max(round(0.05 * len(g["X"])), 10) for c, g in golden_breaks.items()}
+    assert [widths[c] for c in ("w210_mb8", "w230_mb12", "w250_mb16", "w270_mb9", "w220_mb8", "w260_mb8")] == [10, 12, 12, 14, 11, 13]
+
+
+def test_oracle_solve_against_longdouble(golden_breaks):
+    """How far the float64 gelsd solve of the oracle is from a least-squares solve in np.longdouble, as a share of the std of the
+    predictions: the GPU tests ask 1e-9 of the engine, so the oracle must be good to a tenth of that where they use it"""
+    worst = 0.0
+    for c in ("short50_mb16", "w250_mb16", "mb17_1000", "quant300_mb8"):
+        g = golden_breaks[c]
+        for k in np.flatnonzero(~g["raises"])[:4]:
+            hp = ao.predict_longdouble(g["X"][:, k], g["y"][:, k], g["breaks"][:, k], g["X"][:, k])
+            worst = max(worst, float(np.abs(g["pred"][:, k] - hp).max() / np.std(g["pred"][:, k])))
+    print("oracle against longdouble, err / std", worst)
+    assert worst <= 1e-10

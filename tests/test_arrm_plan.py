@@ -36,7 +36,7 @@ def plan(tmp_path_factory):
         rows = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in lines[:-1]}
         half, B, start, width, nacc, slices = rows["plan"]
         return dict(half=half, B=B, start=start, width=width, nacc=nacc, slices=slices, select=rows["select"], accum=rows["accum"],
-                    upper=rows["upper"], lower=rows["lower"])
+                    predict=rows["predict"], upper=rows["upper"], lower=rows["lower"])
 
     return run
 
@@ -88,3 +88,33 @@ def test_launch_sizes(plan, T, C, mb):
     assert T // (agy * ablock // 64) >= min(64, T // (ablock // 64))  # a slice is not shorter than 64 steps where T allows
     # the slice count is a function of T alone: a chunk of a grid adds a cell's sums in the same order as the whole grid
     assert plan(T, 3, mb)["slices"] == p["slices"]
+
+
+SLICE_T = [50, 127, 128, 255, 256, 257, 1023, 1024, 2047, 2048, 19456]
+
+
+@pytest.mark.parametrize("mb", range(2, 18))
+def test_every_break_count(plan, mb):
+    """max_breakpoints 2 .. 17: B, the sums per (cell, slice), the accumulate workgroup (every thread keeps 5 (B - 1) doubles in
+    LDS: 256 threads while that is at most 64 KB, which is B <= 6, else 128) with its LDS bytes, and the slice count (64 steps per
+    thread at least, 8 slices at most), restated here from those rules and not from the header"""
+    B = 2 * (mb // 2)
+    block = 256 if B <= 6 else 128
+    assert (8 * 5 * (B - 1) * 256 <= 64 * 1024) == (block == 256)
+    lds = 8 * 5 * (B - 1) * block + 8 * 16 * 64  # the sums, and the knots of 64 cells
+    for T in SLICE_T:
+        p = plan(T, 67, mb)
+        assert (p["half"], p["B"], p["nacc"]) == (mb // 2, B, 5 * (B - 1) + 1)
+        rows_per_step = block // 64  # time steps a workgroup takes at once
+        slices = min(8, max(1, T // (64 * rows_per_step)))
+        assert p["slices"] == slices and p["accum"] == [2, slices, block, lds], (T, p["accum"])
+        assert lds <= LDS
+    if B == 16:
+        assert lds == 84992 and lds > 64 * 1024
+
+
+@pytest.mark.parametrize("mb,B", [(2, 2), (3, 2), (16, 16), (17, 16)])
+@pytest.mark.parametrize("T,C", [(50, 1), (255, 64), (256, 65), (257, 129), (1025, 67)])
+def test_predict_launch(plan, mb, B, T, C):
+    """256 rows and 64 cells per workgroup, breaks and beta of the 64 cells in LDS"""
+    assert plan(T, C, mb)["predict"] == [-(-C // 64), -(-T // 256), 256, 2 * 8 * B * 64]
