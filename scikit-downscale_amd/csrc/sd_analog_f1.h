@@ -760,19 +760,23 @@ __global__ void __launch_bounds__(1024) analog_f1_mean_kernel(int mode, const do
                         double ss = vyy - slope * vxy;
                         pred = (ybar + m1) + (qj - xm) * slope;
                         if (!(ss > ss_floor)) {
-                            // (nearly) exact fit or constant analogs: the sums directly, as analog_f1_window_kernel
+                            // (nearly) exact fit or constant analogs: the sums directly, in two passes centred on the window's means.
+                            // (Sums shifted by the window's first pair -- its smallest x -- carry raw / centred ~ 4 times the rounding
+                            // in the slope, and here the residuals are nothing but that rounding: at k = 200 an exact line came out
+                            // with 1.3 times the rounding of evaluating a residual, tests/test_gpu_fit_error.py.)
                             const double* yl = yx_all + c * T + L;
                             const double a0 = yl[0];
-                            double t1 = 0.0, txy = 0.0;
+                            double t1 = 0.0;
+                            for (int i = 0; i < k; ++i) t1 += yl[i] - a0;
+                            const double n1 = t1 / kk, ym = a0 + n1;
+                            double cxx = 0.0, cxy = 0.0;
                             for (int i = 0; i < k; ++i) {
-                                const double e = yl[i] - a0;
-                                t1 += e;
-                                txy += (xs[L + i] - x0) * e;
+                                const double dx = xs[L + i] - xm;
+                                cxx += dx * dx;
+                                cxy += dx * (yl[i] - ym);
                             }
-                            const double n1 = t1 / kk;
-                            const double wxy = txy - kk * mx * n1;
-                            const double sl = vxx > 0.0 ? wxy / vxx : 0.0;
-                            const double icpt = (a0 + n1) - xm * sl;
+                            const double sl = vxx > 0.0 && cxx > 0.0 ? cxy / cxx : 0.0;
+                            const double icpt = ym - xm * sl;
                             pred = icpt + qj * sl;
                             ss = 0.0;
                             for (int i = 0; i < k; ++i) {

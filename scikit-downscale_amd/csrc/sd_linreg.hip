@@ -7,8 +7,9 @@
 // (probability 1); a cell without any exceeding sample is flagged (the reference's LinearRegression gets 0 samples).
 //
 // Fields stay in their time-major layout: a workgroup owns 64 adjacent cells x 8 time slices, every load is a
-// 512-byte row fragment, so fit is two streaming passes (shifted sums and cross products, then the residuals) and
-// predict one.
+// 512-byte row fragment, so fit is one streaming pass (shifted sums and cross products), a second one over the residuals
+// for the cells whose fit error the sums do not carry (one more over the sums for a cell whose first sample lies far
+// from its series, one more over the residuals for a cell whose coefficients needed a refinement step), and predict one.
 #include <algorithm>
 #include <vector>
 
@@ -35,6 +36,7 @@ namespace {
 constexpr int kMaxF = sdlsq::kMaxF;
 constexpr int kCells = 64, kSlices = 8;
 constexpr int kFitUnroll = 4;  // time steps of a thread whose loads are in flight together in the fit pass
+constexpr double kRecentre = 16.0;  // fit: a cell whose shifted square sum of a feature exceeds this multiple of the centred one sums again
 
 __device__ __forceinline__ bool lr_finite(double v) { return (__double_as_longlong(v) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll; }
 
@@ -62,7 +64,8 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
     const int64_t c = (int64_t)blockIdx.x * kCells + cx;
     const bool live = c < C;
     // pass 1: sums and cross products of the data shifted by the cell's first sample (one pass; the shift keeps the
-    // centring subtraction below benign), plus the mask / finite bookkeeping of core.py:35-37, base.py:18-20
+    // centring subtraction below benign as long as that sample is an ordinary one, see kRecentre), plus the mask / finite
+    // bookkeeping of core.py:35-37, base.py:18-20
     double x0[F], sx[F], S[F][F], b[F], sy = 0.0, syy = 0.0;
     bool bad = false;
 #pragma unroll
@@ -73,7 +76,7 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
 #pragma unroll
         for (int g = 0; g < F; ++g) S[f][g] = 0.0;
     }
-    const double y0 = live ? y[c] : 0.0;
+    double y0 = live ? y[c] : 0.0;
     double cnt = 0.0;  // samples entering the linear model: all, or those above the threshold (gard.py:439)
     if (live)
         for (int64_t t0 = ty; t0 < T; t0 += kSlices * kFitUnroll) {
@@ -121,32 +124,95 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
         thresh_off[c] = n == (double)T ? 1 : 0;                  // every sample exceeds: the reference drops the threshold
         if (n == 0.0) atomicOr(&status[c], SDI_ONE_CLASS);       // none does: LinearRegression would get 0 samples
     }
-    double xm[F], dm[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-        dm[f] = slice_sum(sx[f], part, cx, ty) / n;  // mean of the shifted feature
-        xm[f] = x0[f] + dm[f];
-    }
-    const double em = slice_sum(sy, part, cx, ty) / n, ym = y0 + em;
-    const double Syy = slice_sum(syy, part, cx, ty) - n * em * em;  // centred: sum e^2 - n mean(e)^2
+    double xm[F], dm[F], em, ym, see, Syy;
     double A[kMaxF][kMaxF + 1], raw[F];
+#pragma unroll 1
+    for (int round = 0; round < 2; ++round) {
 #pragma unroll
-    for (int f = 0; f < F; ++f) {
-        A[f][F] = slice_sum(b[f], part, cx, ty) - n * dm[f] * em;  // centred: sum d e - n mean(d) mean(e)
+        for (int f = 0; f < F; ++f) {
+            dm[f] = slice_sum(sx[f], part, cx, ty) / n;  // mean of the shifted feature
+            xm[f] = x0[f] + dm[f];
+        }
+        em = slice_sum(sy, part, cx, ty) / n;
+        ym = y0 + em;
+        see = slice_sum(syy, part, cx, ty);
+        Syy = see - n * em * em;  // centred: sum e^2 - n mean(e)^2
 #pragma unroll
-        for (int g = f; g < F; ++g) {
-            const double s = slice_sum(S[f][g], part, cx, ty);
-            if (g == f) raw[f] = s;
-            const double v = s - n * dm[f] * dm[g];
-            A[f][g] = v;
-            A[g][f] = v;
+        for (int f = 0; f < F; ++f) {
+            A[f][F] = slice_sum(b[f], part, cx, ty) - n * dm[f] * em;  // centred: sum d e - n mean(d) mean(e)
+#pragma unroll
+            for (int g = f; g < F; ++g) {
+                const double s = slice_sum(S[f][g], part, cx, ty);
+                if (g == f) raw[f] = s;
+                const double v = s - n * dm[f] * dm[g];
+                A[f][g] = v;
+                A[g][f] = v;
+            }
+        }
+        if (round == 1) break;
+        // The shifted sums carry a rounding of ~ T u raw_f where the centred S_ff = raw_f - n dm_f^2 is wanted: a first sample
+        // far from the series (a bad value, a leverage point) costs raw_f / S_ff in accuracy, on every entry of the system.
+        // By the worst-case bound 3 m u (raw_f / S_ff) kappa <= 1e-7, 14 600 samples of features correlated 0.9999 tolerate a
+        // ratio of 16 (a first sample 3.9 standard deviations from the mean); beyond that (kRecentre) the cell sums once more,
+        // shifted by the means of pass 1, which are good to ~ u |x0 - mean|.  Decided per cell from the cell's own totals; a
+        // tile without such a cell skips the pass.  Gaussian fields never take it; skewed ones (precipitation) do in 1 to 2 %
+        // of their cells, which costs their tiles the pass (profiles/fit_error/README.md).
+        bool recentre = false;
+#pragma unroll
+        for (int f = 0; f < F; ++f) recentre |= kRecentre * A[f][f] < raw[f];
+        if (!__syncthreads_or(recentre)) break;
+        if (live && recentre) {
+            y0 = ym;
+            sy = 0.0;
+            syy = 0.0;
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                x0[f] = xm[f];
+                sx[f] = 0.0;
+                b[f] = 0.0;
+#pragma unroll
+                for (int g = 0; g < F; ++g) S[f][g] = 0.0;
+            }
+            for (int64_t t0 = ty; t0 < T; t0 += kSlices * kFitUnroll) {  // (loads batched like pass 1; the sums in time order)
+                double wv[kFitUnroll], xv[kFitUnroll][F];
+#pragma unroll
+                for (int u = 0; u < kFitUnroll; ++u) {
+                    const int64_t t = t0 + (int64_t)u * kSlices;
+                    const bool ok = t < T;
+                    wv[u] = ok ? y[t * ld + c] : y0;
+#pragma unroll
+                    for (int f = 0; f < F; ++f) xv[u][f] = ok ? X[(t * F + f) * ld + c] : x0[f];
+                }
+#pragma unroll
+                for (int u = 0; u < kFitUnroll; ++u) {
+                    if (t0 + (int64_t)u * kSlices >= T) break;
+                    const double w = wv[u];
+                    if (has_thresh && !(w > thresh)) continue;
+                    double d[F];
+                    const double e = w - y0;
+                    sy += e;
+                    syy += e * e;
+#pragma unroll
+                    for (int f = 0; f < F; ++f) d[f] = xv[u][f] - x0[f];
+#pragma unroll
+                    for (int f = 0; f < F; ++f) {
+                        sx[f] += d[f];
+                        b[f] += d[f] * e;
+#pragma unroll
+                        for (int g = f; g < F; ++g) S[f][g] += d[f] * d[g];
+                    }
+                }
+            }
         }
     }
     if (ty == 0) {
-        double coef[kMaxF], sxy[F];
+        double coef[kMaxF], sxy[F], sd[F];
         sdlsq::clear_unresolved(F, A, raw, n);  // a feature that is constant over the samples of the linear model
 #pragma unroll
-        for (int f = 0; f < F; ++f) sxy[f] = A[f][F];  // (the solver works in place)
+        for (int f = 0; f < F; ++f) {  // (the solver works in place)
+            sxy[f] = A[f][F];
+            sd[f] = A[f][f];
+        }
         sdlsq::minnorm_solve(F, A, coef);
         double icpt = ym;
 #pragma unroll
@@ -155,22 +221,41 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
             model[f * kCells + cx] = coef[f];
         }
         model[F * kCells + cx] = icpt;
-        // residual sum of squares of the least-squares solution from the sums of pass 1: Syy - coef . Sxy (the normal equations).
-        // Its relative error is ~ eps Syy / rss: far inside the parity contract unless the fit is (nearly) exact -- such a cell,
-        // and every cell with a threshold (subset fit: kept as it was), sums its residuals in a second pass.  The decision is
-        // per cell: a cell's result does not depend on the cells that share its tile.
-        double rss = Syy;
+        // Residual sum of squares of the least-squares solution from the sums of pass 1: rss = Syy - coef . Sxy (the normal
+        // equations), taken only where the error it carries is bounded by 1e-7 rss -- a tenth of the parity contract, which
+        // leaves the square root of the RMSE and the reference's own rounding inside 1e-6.  What it carries (u = 2^-53):
+        //  * every sum is m = T / 8 + 11 roundings deep (the additions of one time slice, the 8 slices, the shift and the
+        //    product of a term), so sum e^2 is off by <= m u sum e^2, and n mean(e)^2, formed from sum e, by twice that:
+        //    |d Syy| <= 3 m u sum e^2 -- of the *uncentred* sum, which a far first y sample makes much larger than Syy;
+        //    likewise |d Sxy_f| <= 3 m u sqrt(raw_f sum e^2) >= 3 m u (sum |d_f e| + n |dm_f em|) by Cauchy-Schwarz;
+        //  * with the computed coefficients the identity holds up to coef . r, r = S coef - Sxy the residual of the in-place
+        //    solve: cyclic Jacobi on the equilibrated system (norm <= F) applies at most 12 F^2 / 2 rotations of 6 roundings
+        //    each, |coef . r| <= 36 F^3 u (sum_f |coef_f| sqrt(S_ff))^2.
+        // Every cell beyond that bound, and every cell with a threshold (subset fit: kept as it was), sums its residuals in a
+        // second pass.  The decision is per cell: a cell's result does not depend on the cells that share its tile.
+        double rss = Syy, lin = 0.0, wsum = 0.0;
+        const double se = sqrt(see);
 #pragma unroll
-        for (int f = 0; f < F; ++f) rss -= coef[f] * sxy[f];
-        const bool second = has_thresh || !(rss > 1e-9 * Syy);
+        for (int f = 0; f < F; ++f) {
+            rss -= coef[f] * sxy[f];
+            lin += fabs(coef[f]) * sqrt(raw[f]) * se;
+            wsum += fabs(coef[f]) * sqrt(sd[f] > 0.0 ? sd[f] : 0.0);
+        }
+        const double m = (double)((T + kSlices - 1) / kSlices + kSlices + 3), u = 1.1102230246251565e-16;
+        const double carried = u * (3.0 * m * (see + lin) + 36.0 * F * F * F * wsum * wsum);
+        const bool second = has_thresh || !(carried <= 1e-7 * rss);
         rss1[cx] = second ? -1.0 : rss;
     }
     __syncthreads();
-    // pass 2 (cells that need it): residuals of the fit (root_mean_squared_error, gard.py:441-442)
-    double cf[F];
+    // pass 2 (cells that need it): residuals of the fit (root_mean_squared_error, gard.py:441-442), and their cross products
+    // with the centred features, g = Xc^T r -- zero for the exact least-squares coefficients
+    double cf[F], g[F];
 #pragma unroll
-    for (int f = 0; f < F; ++f) cf[f] = model[f * kCells + cx];
-    const double icpt = model[F * kCells + cx];
+    for (int f = 0; f < F; ++f) {
+        cf[f] = model[f * kCells + cx];
+        g[f] = 0.0;
+    }
+    double icpt = model[F * kCells + cx];
     const double rss_sums = rss1[cx];
     const bool second = rss_sums < 0.0;
     double ss = 0.0;
@@ -178,13 +263,67 @@ __global__ void __launch_bounds__(kCells * kSlices) linreg_fit_kernel(const doub
         for (int64_t t = ty; t < T; t += kSlices) {
             const double w = y[t * ld + c];
             if (has_thresh && !(w > thresh)) continue;
-            double yh = icpt;
+            double xv[F], yh = icpt;
 #pragma unroll
-            for (int f = 0; f < F; ++f) yh += X[(t * F + f) * ld + c] * cf[f];
+            for (int f = 0; f < F; ++f) {
+                xv[f] = X[(t * F + f) * ld + c];
+                yh += xv[f] * cf[f];
+            }
             const double r = w - yh;
             ss += r * r;
+#pragma unroll
+            for (int f = 0; f < F; ++f) g[f] += (xv[f] - xm[f]) * r;
         }
     ss = slice_sum(ss, part, cx, ty);
+#pragma unroll
+    for (int f = 0; f < F; ++f) g[f] = slice_sum(g[f], part, cx, ty);
+    // The residual sum splits into that of the exact solution and d . g, d = S^-1 g the error of the coefficients: the part that
+    // the sums and the solve put into the residuals (~ eps sqrt(T kappa) of the prediction; all there is when the fit is exact and
+    // the features are nearly collinear).  Where it exceeds 1e-7 of the sum -- a tenth of the contract again -- the cell takes the
+    // step d (one step of iterative refinement: the residuals come from the data, so they carry the error of the coefficients
+    // to the rounding of one evaluation) and sums the residuals of the refined model in a third pass.  The second slice of a cell
+    // still holds the system that the first one solved in place.  Per cell; every other cell keeps its numbers bit for bit.
+    bool refine = false;
+    if (ty == 1 && live && second) {
+        double dl[kMaxF], dg = 0.0;
+        sdlsq::clear_unresolved(F, A, raw, n);
+#pragma unroll
+        for (int f = 0; f < F; ++f) A[f][F] = g[f];
+        sdlsq::minnorm_solve(F, A, dl);
+#pragma unroll
+        for (int f = 0; f < F; ++f) dg += dl[f] * g[f];
+        refine = dg > 1e-7 * ss;
+        if (refine) {
+            double ic = ym;
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                const double c1 = cf[f] + dl[f];
+                ic -= xm[f] * c1;
+                model[f * kCells + cx] = c1;
+            }
+            model[F * kCells + cx] = ic;
+            rss1[cx] = -2.0;
+        }
+    }
+    if (__syncthreads_or(refine)) {
+        const bool third = rss1[cx] == -2.0;
+#pragma unroll
+        for (int f = 0; f < F; ++f) cf[f] = model[f * kCells + cx];
+        icpt = model[F * kCells + cx];
+        double s3 = 0.0;
+        if (live && third)
+            for (int64_t t = ty; t < T; t += kSlices) {
+                const double w = y[t * ld + c];
+                if (has_thresh && !(w > thresh)) continue;
+                double yh = icpt;
+#pragma unroll
+                for (int f = 0; f < F; ++f) yh += X[(t * F + f) * ld + c] * cf[f];
+                const double r = w - yh;
+                s3 += r * r;
+            }
+        s3 = slice_sum(s3, part, cx, ty);
+        if (third) ss = s3;
+    }
     if (live && ty == 0) {
 #pragma unroll
         for (int f = 0; f < F; ++f) coef_out[(int64_t)f * C + c] = cf[f];
