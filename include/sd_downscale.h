@@ -150,6 +150,11 @@ extern "C" {
 #define SD_SKILL_RMSE 4       /* sqrt(sq / n) */
 #define SD_SKILL_CORR 5       /* qab / (sqrt(qaa) * sqrt(qbb)), clamped to [-1, 1] */
 #define SD_SKILL_STD_RATIO 6  /* sqrt(qaa / qbb) */
+/* sd_twosample: statistics of a bin of two fields a and b, from each field's own sorted non-NaN samples */
+#define SD_TWOSAMPLE_KS 0       /* the two-sample Kolmogorov-Smirnov distance */
+#define SD_TWOSAMPLE_PERKINS 1  /* the Perkins skill score: the overlap of the two histograms */
+#define SD_TWOSAMPLE_NA 2       /* na: the non-NaN samples of a */
+#define SD_TWOSAMPLE_NB 3       /* nb: the non-NaN samples of b */
 
 #define SD_SYNTH_GAUSS 0
 #define SD_SYNTH_PRECIP 1
@@ -666,6 +671,46 @@ int sd_skill_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, con
 /* host buffers: a, b [T, C], out [nstat * M, C]; upload, run, download */
 int sd_skill(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
              const int64_t* offsets, int64_t M, const int* stats, int nstat, double* out_host);
+
+/* ---- distribution scores per period: GridArray.compare(other).ks() / .perkins(width) / .distribution(names) ----
+ * a and b are [T, C] fields (cells fastest, rows ld_a, ld_b >= C elements apart; each float64, or float32 with its is_f32 != 0); they
+ * may be the same pointer.  The bins are those of sd_skill: offsets, a host array of M + 1 entries that starts at 0, never decreases
+ * and ends at T.
+ *
+ * The rule, per cell and bin.  A float32 sample is widened to double first.  Unlike sd_skill, which drops a step where either sample
+ * is NaN, each field contributes its OWN non-NaN samples: na and nb may differ, and a NaN in a does not remove the sample of b at
+ * that step (the two-sample definition: scipy.stats.ks_2samp on the two series with NaN dropped).  +-inf are ordinary values.  With
+ * a_0 <= ... <= a_{na-1} the sorted samples of a, le(x) the number of samples of b <= x and lt(x) the number < x:
+ *   SD_TWOSAMPLE_KS       num = max over i of max((i + 1) * nb - le(a_i) * na, lt(a_i) * na - i * nb) in int64;
+ *                         D = (double)num / ((double)na * (double)nb), one division.  Evaluating at the points of a alone is enough
+ *                         (Fa - Fb takes its maximum at a jump of Fa and its minimum just before one); ties need no special case;
+ *                         the value is symmetric in a and b.
+ *   SD_TWOSAMPLE_PERKINS  the histogram bin of a sample is k(x) = floor((x - origin) / width) in double: one subtraction, one
+ *                         division, one floor; k is monotone in x and +-inf fall in bins of their own.  With ca_k, cb_k the
+ *                         samples of a and b in bin k:  num = sum over the distinct k present in a of min(ca_k * nb, cb_k * na)
+ *                         in int64;  PSS = (double)num / ((double)na * (double)nb).  width > 0 and origin are finite doubles,
+ *                         read only where this code is asked for.
+ *   SD_TWOSAMPLE_NA, SD_TWOSAMPLE_NB  the two counts; 0 for an empty or all-NaN bin.
+ * KS and Perkins are NaN where na == 0 or nb == 0.  out holds nstat float64 fields [M, C] (rows ld_out >= C apart, the fields
+ * stride_out >= M * ld_out elements apart): field s is the statistic stats[s] (a host array of nstat codes, 1 <= nstat <= 4; a code
+ * may repeat).  Everything is integer arithmetic followed by one division: the result is the same bit for bit whatever the layout,
+ * the leading dimensions, the path or the launch geometry.
+ *
+ * Bins of up to 1 216 rows are sorted one wave per (bin, cell) on chip, both fields side by side; longer ones, up to 19 456 rows, go
+ * through sorted runs in 16 * C * (sum of the bins' lengths, each rounded up to whole runs) bytes of device scratch (SD_ERR_NOMEM
+ * where that fails); a longer bin is SD_ERR_UNSUPPORTED.  Both fields are whole in device memory for the call: one bin over the whole
+ * axis needs both whole [T, C] fields there.
+ *
+ * An unknown statistic code, nstat outside 1 .. 4; with Perkins a width that is not finite or <= 0 or an origin that is not finite;
+ * sizes <= 0, T >= 2^31; a leading dimension below C, stride_out < M * ld_out; a field too large; a table of bins that breaks the
+ * rules above are SD_ERR_INVALID, in this order, then the bin beyond 19 456 rows (SD_ERR_UNSUPPORTED), then the LDS and grid limits
+ * and ld >= 2^29: all refused before anything is allocated or launched. */
+int sd_twosample_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, const void* b_dev, int b_is_f32, int64_t ld_b, int64_t T,
+                     int64_t C, const int64_t* offsets, int64_t M, const int* stats, int nstat, double width, double origin,
+                     double* out_dev, int64_t ld_out, int64_t stride_out);
+/* host buffers: a, b [T, C], out [nstat * M, C]; upload, run, download */
+int sd_twosample(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
+                 const int64_t* offsets, int64_t M, const int* stats, int nstat, double width, double origin, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

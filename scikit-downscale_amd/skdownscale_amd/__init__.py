@@ -18,6 +18,7 @@ from .rolling import GridRolling, RolledGridArray
 from .order_stats import TimeQuantileGridArray
 from .spells import GridCondition, SpellGridArray
 from .skill import GridComparison, SkillGridArray
+from .distribution import DistributionGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -74,5 +75,6 @@ __all__ = [
     "SpellGridArray",
     "GridComparison",
     "SkillGridArray",
+    "DistributionGridArray",
 ]
 __version__ = "0.1.0"

@@ -33,6 +33,7 @@ QUANTILE_METHODS = {"linear": 0, "lower": 1, "higher": 2, "nearest": 3, "midpoin
 SPELL_OPS = {">": 0, ">=": 1, "<": 2, "<=": 3}  # SD_SPELL_GT .. _LE
 SPELL_STATS = {"valid": 0, "count": 1, "fraction": 2, "longest_spell": 3, "spell_days": 4, "spell_count": 5}  # SD_SPELL_VALID .. _SPELL_COUNT
 SKILL_STATS = {"count": 0, "bias": 1, "ratio": 2, "mae": 3, "rmse": 4, "corr": 5, "std_ratio": 6}  # SD_SKILL_COUNT .. _STD_RATIO
+TWOSAMPLE_STATS = {"ks": 0, "perkins": 1, "na": 2, "nb": 3}  # SD_TWOSAMPLE_KS .. _NB
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -158,6 +159,8 @@ SIGNATURES = {
     "sd_spells": [_p, _p, _int, _i64, _i64, _int, _dbl, _p, _p, _i64, _p, _i64, _i64, _p, _int, _p],
     "sd_skill_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _i64],
     "sd_skill": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _p],
+    "sd_twosample_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p, _i64, _i64],
+    "sd_twosample": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -1192,6 +1192,79 @@ class Context:
                                 ptr(codes), len(codes), ptr(out)))
         return out
 
+    # ---- distribution scores per bin of the time axis (GridArray.compare(...).ks() / .perkins()) ----
+    @staticmethod
+    def _twosample_args(a, b, offsets, stats, width, origin):
+        stats = [stats] if isinstance(stats, str) else list(stats)
+        for s in stats:
+            if s not in _lib.TWOSAMPLE_STATS:
+                raise ValueError(f"distribution statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.TWOSAMPLE_STATS)}")
+        if not 1 <= len(stats) <= len(_lib.TWOSAMPLE_STATS):
+            raise ValueError(f"sd_downscale: sd_twosample: nstat = {len(stats)}, expected 1 to {len(_lib.TWOSAMPLE_STATS)} statistics")
+        if "perkins" in stats:
+            if width is None:
+                raise ValueError("perkins needs the width of the histogram bins (width=...)")
+            number = (int, float, np.integer, np.floating)
+            if not (isinstance(width, number) and not isinstance(width, bool) and np.isfinite(width) and width > 0):
+                raise ValueError(f"width: expected a positive finite number, got {width!r}")
+            if not (isinstance(origin, number) and not isinstance(origin, bool) and np.isfinite(origin)):
+                raise ValueError(f"origin: expected a finite number, got {origin!r}")
+        a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
+        T, Cc = a.shape
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
+        M = len(offsets) - 1
+        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: sd_twosample: bad sizes (T={T}, C={Cc}, M={M})")
+        codes = np.ascontiguousarray([_lib.TWOSAMPLE_STATS[s] for s in stats], dtype=np.intc)
+        perkins = "perkins" in stats
+        return a, b, offsets, codes, float(width) if perkins else 0.0, float(origin) if perkins else 0.0
+
+    def twosample(self, a, b, offsets, stats, width=None, origin=0.0, out=None, plane_rows=None):
+        """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
+        may be the same array); offsets: host int64 [M + 1], bin m = rows offsets[m] .. offsets[m + 1] - 1; stats: one name or a list
+        of 'ks' | 'perkins' | 'na' | 'nb' -> [nstat * M, C] float64 DeviceArray, row ``s * M + m`` the statistic s of bin m
+        (sd_twosample_dev; the rule is in include/sd_downscale.h).  Unlike ``skill``, each field contributes its own non-NaN samples of
+        a bin: a NaN in ``a`` does not remove the sample of ``b`` at that step.  ``width`` (> 0) and ``origin``: the histogram bins
+        floor((x - origin) / width) of 'perkins', read only where it is asked for.  A bin holds at most 19 456 rows
+        (NotImplementedError beyond).  ``out`` and ``plane_rows``: as for ``spells``."""
+        a, b, offsets, codes, width, origin = self._twosample_args(a, b, offsets, stats, width, origin)
+        T, Cc = a.shape
+        M, nstat = len(offsets) - 1, len(codes)
+        if plane_rows is None:
+            out = self._result_buffer(out, (nstat * M, Cc), True)
+            stride = M * out.ld
+        else:
+            out = self._result_buffer(out, (M, Cc), True)
+            base = out.base
+            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
+            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
+                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
+            stride = int(plane_rows) * out.ld
+        with self._uploads() as up:
+            same = b is a
+            a = up(a, a.dtype)
+            b = a if same else up(b, b.dtype)
+            self._same_context("sd_twosample", a=a, b=b, out=out)
+            check(self.lib.sd_twosample_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T,
+                                            Cc, ptr(offsets), M, ptr(codes), nstat, width, origin, out.vptr, out.ld, stride))
+        return out
+
+    def twosample_host(self, a, b, offsets, stats, width=None, origin=0.0):
+        """host [T, C] twice -> host [nstat * M, C] through sd_twosample (upload, run, download in one call)"""
+        a, b, offsets, codes, width, origin = self._twosample_args(a, b, offsets, stats, width, origin)
+        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
+            raise ValueError("twosample_host: expected host arrays")
+        T, Cc = a.shape
+        M = len(offsets) - 1
+        out = np.empty((len(codes) * M, Cc))
+        check(self.lib.sd_twosample(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(offsets), M,
+                                    ptr(codes), len(codes), width, origin, ptr(out)))
+        return out
+
     # ---- temporal disaggregation (GridArray.disaggregate) ----
     @staticmethod
     def _disagg_args(target, obs, src_row, offsets, op, climo, group):

@@ -23,8 +23,10 @@ block by block --, or, where one of them is a lazy ``resample`` / ``groupby`` / 
 taken whole from HBM, both whole.  A bin always lies within one block of both; one bin over the whole axis therefore needs both whole
 [T, C] fields in HBM.
 
-Out of scope: ``by=`` groups of non-consecutive steps, alignment of differing time axes, distribution scores (KS, Perkins), weighted
-statistics.
+The distribution scores of the same comparison -- ``ks()``, ``perkins(width)``, ``distribution(names)`` -- are in ``distribution.py``;
+they do not go through ``indices`` and, unlike the statistics here, take each field's own non-NaN samples.
+
+Out of scope: ``by=`` groups of non-consecutive steps, alignment of differing time axes, weighted statistics.
 """
 from __future__ import annotations
 
@@ -157,6 +159,26 @@ class GridComparison:
 
     def std_ratio(self):
         return self._one("std_ratio")
+
+    # ---- the distribution scores (distribution.py) ----
+    def distribution(self, names, width=None, origin=0.0):
+        """several of ``'ks'``, ``'perkins'``, ``'na'``, ``'nb'`` from one call: a leading ``"index"`` dim whose coordinate is
+        ``names``; both fields are sorted once.  ``width`` (> 0) and ``origin``: the histogram bins of ``'perkins'``"""
+        from .distribution import DistributionGridArray
+
+        return DistributionGridArray(self, names, width, origin, indexed=True)
+
+    def ks(self):
+        """the two-sample Kolmogorov-Smirnov distance of the two fields per bin and cell, each field's own non-NaN samples"""
+        from .distribution import DistributionGridArray
+
+        return DistributionGridArray(self, ("ks",))
+
+    def perkins(self, width, origin=0.0):
+        """the Perkins skill score per bin and cell: the overlap of the two histograms with bins floor((x - origin) / width)"""
+        from .distribution import DistributionGridArray
+
+        return DistributionGridArray(self, ("perkins",), width, origin)
 
     def __repr__(self):
         over = "the whole axis" if self._bins is None else f"{self._dim}={self._rule!r}: {len(self._bins[0])} bins"

@@ -659,9 +659,81 @@ def bench_skill(ctx, args):
     return res
 
 
+def bench_twosample(ctx, args):
+    """the two-sample kernels on 14 600 daily steps x 100 000 cells, float64 against float64 (the fields of the skill workload): 'YS'
+    bins -- the segment path -- and one whole-axis bin -- the series path --, ["ks", "perkins"] from one call, timed through ctx.prof()
+    (the sum over the kernels of a call; median and [min, max] of 7 profiled calls after a warm-up) beside sd_memcpy_d2d of the same source
+    bytes (both fields), beside skill_kernel (bias, rmse) over the same bins, and beside two sd_quantile_dev calls with Q = 1 on the two
+    fields over the same groups: the same gathers and sorts with a quantile evaluation as the last step.  GB/s by algorithmic bytes
+    (16 * T * C read + 8 * nstat * M * C written); the first 64 cells compared bit for bit with the oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _twosample_oracle as ts
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    labels, yearly = time_bins(index, "YS")
+    tabs = synth.tas_tables(index)
+
+    def fill(cells, tab):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(call, repeats):
+        call()
+        ctx.prof_enable(True)
+        times, kernels = [], {}
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            prof = ctx.prof()
+            times.append(sum(v["ms"] for v in prof.values()))
+            for k, v in prof.items():
+                kernels.setdefault(k, []).append(v["ms"])
+        ctx.prof_enable(False)
+        return {"kernel_ms": float(np.median(times)), "kernel_ms_min_max": [min(times), max(times)],
+                "kernels_ms": {k: float(np.median(v)) for k, v in kernels.items()}}
+
+    a, b = fill(C, tabs["X_hist"]), fill(C, tabs["y_obs"])
+    first_a, first_b = fill(64, tabs["X_hist"]).to_host(), fill(64, tabs["y_obs"]).to_host()
+    repeats = 7
+    src_bytes = 2 * 8 * T * C
+    spare = ctx.empty((T, C))
+    one_ms, one_min_max = device_copy_ms(ctx, spare, a, src_bytes // 2, repeats)  # (two copies of one field's bytes: the same bytes moved)
+    spare.free()
+    copy_ms = 2 * one_ms
+    stats, width, origin = ["ks", "perkins"], 1.0, 0.0
+    res = {"workload": f"twosample {T} daily steps x {C} cells float64 against float64: {len(labels)} 'YS' bins (segment path) and one whole-axis bin (series path); ks, perkins(width=1)",
+           "repeats": repeats, "device_copy": {"ms": copy_ms, "ms_of_one_field_min_max": one_min_max, "bytes": src_bytes, "GBps_of_bytes_copied": src_bytes / copy_ms / 1e6}}
+    year = (np.searchsorted(np.asarray(yearly), np.arange(T), side="right") - 1).astype(np.int32)
+    for bins_name, offsets, group in (("YS", np.asarray(yearly, dtype=np.int64), year), ("whole_axis", np.array([0, T], dtype=np.int64), None)):
+        M = len(offsets) - 1
+        two = ctx.empty((2 * M, C))
+        sk_r = timed(lambda: ctx.skill(a, b, offsets, ["bias", "rmse"], out=two), repeats)
+        res[f"{bins_name}_skill_kernel_bias_rmse"] = sk_r
+        med = ctx.empty((M, C))
+        q_a = timed(lambda: ctx.quantile(a, [0.5], group, None if group is None else M, out=med), repeats)
+        q_b = timed(lambda: ctx.quantile(b, [0.5], group, None if group is None else M, out=med), repeats)
+        med.free()
+        res[f"{bins_name}_quantile_q1_a"], res[f"{bins_name}_quantile_q1_b"] = q_a, q_b
+        quantile_ms = q_a["kernel_ms"] + q_b["kernel_ms"]
+        r = timed(lambda: ctx.twosample(a, b, offsets, stats, width, origin, out=two), repeats)
+        ms = r["kernel_ms"]
+        nbytes = src_bytes + 8 * len(stats) * M * C
+        got, want = two.cells(0, 64).to_host(), ts.twosample(first_a, first_b, offsets, stats, width, origin)
+        r.update({"statistics": stats, "bins": M, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6, "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0,
+                  "bit_identical_to_oracle_first_64_cells": bool(np.array_equal(got, want, equal_nan=True)), "kernel_over_copy_ms": ms / copy_ms,
+                  "kernel_over_skill_ms": ms / sk_r["kernel_ms"], "two_quantile_calls_ms": quantile_ms, "kernel_over_two_quantile_calls": ms / quantile_ms})
+        res[f"{bins_name}_ks_perkins"] = r
+        ks_only = timed(lambda: ctx.twosample(a, b, offsets, ["ks"], out=two.rows(0, M)), repeats)
+        ks_only["kernel_over_two_quantile_calls"] = ks_only["kernel_ms"] / quantile_ms
+        res[f"{bins_name}_ks"] = ks_only
+        two.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -680,9 +752,10 @@ def main():
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
         return
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells", "skill"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells", "skill", "twosample"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
-                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells, "skill": bench_skill}[args.workload](ctx, args))
+                           "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells, "skill": bench_skill,
+                           "twosample": bench_twosample}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
