@@ -672,6 +672,26 @@ int sd_skill_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, con
 int sd_skill(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
              const int64_t* offsets, int64_t M, const int* stats, int nstat, double* out_host);
 
+/* ---- paired skill statistics per group of steps: GridArray.compare(other).groupby("time.month").bias() / .rmse() / .corr() ... ----
+ * The fields, the statistics and the output are those of sd_skill, with groups in place of bins: group is a host int32 [T] with every
+ * id in [0, G), as for sd_groupby_reduce and sd_quantile, and out holds nstat float64 fields [G, C]: row s * G + g (for a contiguous
+ * output) is statistic stats[s] of group g.  Both fields are whole in device memory for the call.
+ *
+ * The rule: group g is evaluated exactly as sd_skill evaluates one bin whose steps are the rows t with group[t] == g in ascending t.
+ * So the call on (a, b) equals sd_skill on the fields gathered group by group, (a[rows], b[rows], offsets) with rows / offsets the
+ * stable counting sort of the ids, bit for bit; where the groups are runs of consecutive rows it equals sd_skill with those offsets.
+ * A group id that never occurs is an empty bin: SD_SKILL_COUNT is 0, everything else NaN.
+ *
+ * The refusals of sd_skill that depend on codes and sizes (T, C; G takes the place of M in the stride and size checks), then G <= 0,
+ * then a group id outside [0, G) are SD_ERR_INVALID, in this order, refused before anything is allocated or launched.  One launch of
+ * skill_groups_kernel; the row table costs 8 * T bytes per tile of cells beside the bytes of sd_skill. */
+int sd_skill_groups_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, const void* b_dev, int b_is_f32, int64_t ld_b, int64_t T,
+                        int64_t C, const int32_t* group, int64_t G, const int* stats, int nstat, double* out_dev, int64_t ld_out,
+                        int64_t stride_out);
+/* host buffers: a, b [T, C], out [nstat * G, C]; upload, run, download */
+int sd_skill_groups(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
+                    const int32_t* group, int64_t G, const int* stats, int nstat, double* out_host);
+
 /* ---- distribution scores per period: GridArray.compare(other).ks() / .perkins(width) / .distribution(names) ----
  * a and b are [T, C] fields (cells fastest, rows ld_a, ld_b >= C elements apart; each float64, or float32 with its is_f32 != 0); they
  * may be the same pointer.  The bins are those of sd_skill: offsets, a host array of M + 1 entries that starts at 0, never decreases
@@ -711,6 +731,26 @@ int sd_twosample_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a,
 /* host buffers: a, b [T, C], out [nstat * M, C]; upload, run, download */
 int sd_twosample(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
                  const int64_t* offsets, int64_t M, const int* stats, int nstat, double width, double origin, double* out_host);
+
+/* ---- distribution scores per group of steps: GridArray.compare(other).groupby("time.season").ks() / .perkins(width) ----
+ * sd_twosample with groups in place of bins: group is a host int32 [T] with every id in [0, G), out holds nstat float64 fields [G, C].
+ *
+ * The rule: group g is evaluated exactly as sd_twosample evaluates one bin whose steps are the rows t with group[t] == g in ascending
+ * t; the call equals sd_twosample on the gathered fields (a[rows], b[rows], offsets), bit for bit, and sd_twosample itself where the
+ * groups are runs of consecutive rows.  A group id that never occurs is an empty bin: na and nb are 0, KS and Perkins NaN.  The same
+ * kernels serve it, reading their rows through the group-sorted row table: groups of up to 1 216 rows on chip, longer ones, up to
+ * 19 456 rows, through 16 * C * (sum of the groups' lengths, each rounded up to whole runs) bytes of sorted runs in device scratch.
+ * Both fields are whole in device memory for the call.
+ *
+ * The refusals of sd_twosample that depend on codes and sizes, then G <= 0, then a group id outside [0, G) are SD_ERR_INVALID; then a
+ * group of more than 19 456 rows is SD_ERR_UNSUPPORTED; then the LDS and grid limits and ld >= 2^29: in this order, all refused
+ * before anything is allocated or launched. */
+int sd_twosample_groups_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, const void* b_dev, int b_is_f32, int64_t ld_b,
+                            int64_t T, int64_t C, const int32_t* group, int64_t G, const int* stats, int nstat, double width,
+                            double origin, double* out_dev, int64_t ld_out, int64_t stride_out);
+/* host buffers: a, b [T, C], out [nstat * G, C]; upload, run, download */
+int sd_twosample_groups(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
+                        const int32_t* group, int64_t G, const int* stats, int nstat, double width, double origin, double* out_host);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

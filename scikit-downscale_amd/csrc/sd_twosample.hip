@@ -20,6 +20,11 @@
 // are (a in its scratch slots, b in LDS); the count ca_k of a bin's first sample is a search in a's scratch slots: one chain of global
 // loads per occupied histogram bin, not per sample.
 //
+// Groups (sd_twosample_groups: compare(other).groupby("time.season").ks()): the same kernels under the same profiler names.  Every kernel
+// reads its rows through the row table only -- gather_tile(rows + beg) in the segment kernel, rows + ch.start in quantile_runs_kernel;
+// twosample_select_kernel sees runs and counts, no rows -- so the group-sorted table of groupby_tables takes the place of the identity
+// and the offsets over it the place of the bins; the plan (twosample_groups_plan) chooses the path by the longest group.
+//
 // Algorithmic bytes: sizeof(SA) * T * C + sizeof(SB) * T * C read, 8 * nstat * M * C written; the series path adds a write and two
 // reads of 8 * C * run_slots bytes of scratch per field (three reads of a's).  Everything after the sorts is integer arithmetic and
 // one division: the bits depend neither on the layout, nor on the path, nor on the launch geometry.
@@ -245,7 +250,7 @@ constexpr const char* select_name() {
 
 struct TwosampleArgs {
     const void *a, *b;
-    const int32_t* rows;     // device [T]: the identity, the row table of gather_tile
+    const int32_t* rows;     // device [T]: the row table of gather_tile (the identity for bins, the group-sorted rows for groups)
     const int32_t* offsets;  // device [M + 1]
     int stats;               // the codes, four bits each
     double* out;
@@ -318,6 +323,44 @@ TwosampleCall call_of(const sd_ctx* ctx, int a_is_f32, int64_t ld_a, int b_is_f3
     return c;
 }
 
+// a planned call over the bins offsets [M + 1] (host) of the row table rows [T] (host): the identity for bins of consecutive rows, the
+// group-sorted rows of groupby_tables for groups.  Every kernel reads its rows through the table only.
+int run_planned(sd_ctx* ctx, const TwosampleCall& c, const TwosamplePlan& pl, const std::vector<int32_t>& rows, const int64_t* offsets, const void* a,
+                const void* b, double* out) {
+    const std::vector<int32_t> offsets32(offsets, offsets + c.M + 1);
+    SD_HIP(hipSetDevice(ctx->device));
+    sd_scratch drows, doffsets;
+    SD_TRY(upload(ctx, drows, rows));
+    SD_TRY(upload(ctx, doffsets, offsets32));
+    TwosampleArgs g = {a, b, drows.as<int32_t>(), doffsets.as<int32_t>(), 0, out};
+    for (int s = 0; s < c.nstat; ++s) g.stats |= c.stats[s] << (4 * s);
+    if (pl.path == sdts::kSegment) {
+        int rc;
+        if (c.a_is_f32)
+            rc = c.b_is_f32 ? launch_segment<float, float>(ctx, c, pl, g) : launch_segment<float, double>(ctx, c, pl, g);
+        else
+            rc = c.b_is_f32 ? launch_segment<double, float>(ctx, c, pl, g) : launch_segment<double, double>(ctx, c, pl, g);
+        SD_TRY(rc);
+    } else {
+        std::vector<QuantileChunk> chunks;
+        std::vector<QuantileGroup> groups;
+        quantile_series_tables(offsets, c.M, pl.K, &chunks, &groups, c.C);
+        sd_scratch dchunks, dgroups, runs_a, runs_b, counts_a, counts_b;
+        SD_TRY(upload(ctx, dchunks, chunks));
+        SD_TRY(upload(ctx, dgroups, groups));
+        SD_HIP(runs_a.alloc(ctx, sizeof(double) * (size_t)pl.run_slots * (size_t)c.C));
+        SD_HIP(runs_b.alloc(ctx, sizeof(double) * (size_t)pl.run_slots * (size_t)c.C));
+        SD_HIP(counts_a.alloc(ctx, sizeof(int32_t) * (size_t)pl.chunks * (size_t)c.C));
+        SD_HIP(counts_b.alloc(ctx, sizeof(int32_t) * (size_t)pl.chunks * (size_t)c.C));
+        const int rc = launch_series(ctx, c, pl, g, dchunks.as<QuantileChunk>(), dgroups.as<QuantileGroup>(), runs_a.as<double>(), runs_b.as<double>(),
+                                     counts_a.as<int32_t>(), counts_b.as<int32_t>());
+        SD_HIP(hipStreamSynchronize(ctx->stream));  // (the scratch goes back to the pool)
+        SD_TRY(rc);
+    }
+    SD_HIP(hipStreamSynchronize(ctx->stream));
+    return SD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,38 +374,7 @@ int sd_twosample_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a,
     if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
     std::vector<int32_t> rows((size_t)T);
     for (int64_t t = 0; t < T; ++t) rows[t] = (int32_t)t;
-    const std::vector<int32_t> offsets32(offsets, offsets + M + 1);
-    SD_HIP(hipSetDevice(ctx->device));
-    sd_scratch drows, doffsets;
-    SD_TRY(upload(ctx, drows, rows));
-    SD_TRY(upload(ctx, doffsets, offsets32));
-    TwosampleArgs g = {a_dev, b_dev, drows.as<int32_t>(), doffsets.as<int32_t>(), 0, out_dev};
-    for (int s = 0; s < c.nstat; ++s) g.stats |= c.stats[s] << (4 * s);
-    if (pl.path == sdts::kSegment) {
-        int rc;
-        if (c.a_is_f32)
-            rc = c.b_is_f32 ? launch_segment<float, float>(ctx, c, pl, g) : launch_segment<float, double>(ctx, c, pl, g);
-        else
-            rc = c.b_is_f32 ? launch_segment<double, float>(ctx, c, pl, g) : launch_segment<double, double>(ctx, c, pl, g);
-        SD_TRY(rc);
-    } else {
-        std::vector<QuantileChunk> chunks;
-        std::vector<QuantileGroup> groups;
-        quantile_series_tables(offsets, M, pl.K, &chunks, &groups, C);
-        sd_scratch dchunks, dgroups, runs_a, runs_b, counts_a, counts_b;
-        SD_TRY(upload(ctx, dchunks, chunks));
-        SD_TRY(upload(ctx, dgroups, groups));
-        SD_HIP(runs_a.alloc(ctx, sizeof(double) * (size_t)pl.run_slots * (size_t)C));
-        SD_HIP(runs_b.alloc(ctx, sizeof(double) * (size_t)pl.run_slots * (size_t)C));
-        SD_HIP(counts_a.alloc(ctx, sizeof(int32_t) * (size_t)pl.chunks * (size_t)C));
-        SD_HIP(counts_b.alloc(ctx, sizeof(int32_t) * (size_t)pl.chunks * (size_t)C));
-        const int rc = launch_series(ctx, c, pl, g, dchunks.as<QuantileChunk>(), dgroups.as<QuantileGroup>(), runs_a.as<double>(), runs_b.as<double>(),
-                                     counts_a.as<int32_t>(), counts_b.as<int32_t>());
-        SD_HIP(hipStreamSynchronize(ctx->stream));  // (the scratch goes back to the pool)
-        SD_TRY(rc);
-    }
-    SD_HIP(hipStreamSynchronize(ctx->stream));
-    return SD_OK;
+    return run_planned(ctx, c, pl, rows, offsets, a_dev, b_dev, out_dev);
 }
 
 int sd_twosample(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C, const int64_t* offsets,
@@ -377,6 +389,34 @@ int sd_twosample(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_ho
     const sd_host_field f[] = {sd_in(a_host, a_bytes), sd_in(b_host, b_bytes), sd_out(out_host, sizeof(double) * (size_t)nstat * M * C)};
     return with_device_copies(ctx, f, [&](void* const* d) {
         return sd_twosample_dev(ctx, d[0], a_is_f32, C, d[1], b_is_f32, C, T, C, offsets, M, stats, nstat, width, origin, (double*)d[2], C, stride);
+    });
+}
+
+int sd_twosample_groups_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_t ld_a, const void* b_dev, int b_is_f32, int64_t ld_b, int64_t T,
+                            int64_t C, const int32_t* group, int64_t G, const int* stats, int nstat, double width, double origin, double* out_dev,
+                            int64_t ld_out, int64_t stride_out) {
+    SD_CHECK_ARG(ctx && a_dev && b_dev && group && stats && out_dev, "sd_twosample_groups: NULL argument");
+    const TwosampleCall c = call_of(ctx, a_is_f32, ld_a, b_is_f32, ld_b, T, C, G, stats, nstat, width, origin, ld_out, stride_out, a_dev, b_dev);
+    std::vector<int64_t> rows64, offsets;
+    const TwosamplePlan pl = twosample_groups_plan(c, group, &rows64, &offsets);
+    if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
+    const std::vector<int32_t> rows(rows64.begin(), rows64.end());  // (T < 2^31)
+    return run_planned(ctx, c, pl, rows, offsets.data(), a_dev, b_dev, out_dev);
+}
+
+int sd_twosample_groups(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C, const int32_t* group,
+                        int64_t G, const int* stats, int nstat, double width, double origin, double* out_host) {
+    SD_CHECK_ARG(ctx && a_host && b_host && group && stats && out_host, "sd_twosample_groups: NULL argument");
+    const int64_t stride = G > 0 && C > 0 && G <= INT64_MAX / 8 / C ? G * C : 0;
+    const TwosampleCall c = call_of(ctx, a_is_f32, C, b_is_f32, C, T, C, G, stats, nstat, width, origin, C, stride, nullptr, nullptr);  // (before the upload)
+    std::vector<int64_t> rows64, offsets;
+    const TwosamplePlan pl = twosample_groups_plan(c, group, &rows64, &offsets);
+    if (pl.error != SD_OK) return sd_set_error(pl.error, "%s", pl.message);
+    const size_t a_bytes = (a_is_f32 ? sizeof(float) : sizeof(double)) * (size_t)T * C;
+    const size_t b_bytes = (b_is_f32 ? sizeof(float) : sizeof(double)) * (size_t)T * C;
+    const sd_host_field f[] = {sd_in(a_host, a_bytes), sd_in(b_host, b_bytes), sd_out(out_host, sizeof(double) * (size_t)nstat * G * C)};
+    return with_device_copies(ctx, f, [&](void* const* d) {
+        return sd_twosample_groups_dev(ctx, d[0], a_is_f32, C, d[1], b_is_f32, C, T, C, group, G, stats, nstat, width, origin, (double*)d[2], C, stride);
     });
 }
 

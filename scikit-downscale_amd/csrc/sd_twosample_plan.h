@@ -79,11 +79,11 @@ struct TwosamplePlan {
     int64_t select_blocks = 0;
 };
 
-// offsets [M + 1]: a host array
-inline TwosamplePlan twosample_plan(const TwosampleCall& c, const int64_t* offsets) {
-    using namespace sdts;
+namespace sdts {
+// the refusals that depend on codes and sizes alone; binned: M counts bins and belongs to the sizes (a grouped call refuses its G after
+// these, in the words of the groupby plans)
+inline TwosamplePlan twosample_check(const TwosampleCall& c, const char* who, bool binned) {
     using sdbn::fail;
-    const char* const who = "sd_twosample";
     TwosamplePlan pl;
     bool perkins = false;
     for (int s = 0; s < c.nstat && s < kMaxStats; ++s) {
@@ -95,8 +95,9 @@ inline TwosamplePlan twosample_plan(const TwosampleCall& c, const int64_t* offse
     if (perkins && !(std::isfinite(c.width) && c.width > 0.0))
         return fail(pl, SD_ERR_INVALID, "%s: width = %g, expected a positive finite bin width", who, c.width);
     if (perkins && !std::isfinite(c.origin)) return fail(pl, SD_ERR_INVALID, "%s: origin = %g, expected a finite number", who, c.origin);
-    if (!(c.T > 0 && c.C > 0 && c.M > 0))
+    if (binned && !(c.T > 0 && c.C > 0 && c.M > 0))
         return fail(pl, SD_ERR_INVALID, "%s: bad sizes (T=%lld, C=%lld, M=%lld)", who, (long long)c.T, (long long)c.C, (long long)c.M);
+    if (!(c.T > 0 && c.C > 0)) return fail(pl, SD_ERR_INVALID, "%s: bad sizes (T=%lld, C=%lld)", who, (long long)c.T, (long long)c.C);
     if (c.T >= (int64_t)1 << 31) return fail(pl, SD_ERR_INVALID, "%s: T = %lld steps, the counts are int32 (T < 2^31)", who, (long long)c.T);
     if (c.ld_a < c.C) return fail(pl, SD_ERR_INVALID, "%s: ld_a = %lld is less than the %lld cells of a row", who, (long long)c.ld_a, (long long)c.C);
     if (c.ld_b < c.C) return fail(pl, SD_ERR_INVALID, "%s: ld_b = %lld is less than the %lld cells of a row", who, (long long)c.ld_b, (long long)c.C);
@@ -104,16 +105,22 @@ inline TwosamplePlan twosample_plan(const TwosampleCall& c, const int64_t* offse
         return fail(pl, SD_ERR_INVALID, "%s: ld_out = %lld is less than the %lld cells of a row", who, (long long)c.ld_out, (long long)c.C);
     const int64_t most = INT64_MAX / 8;  // (element indices of every field stay far from the end of int64_t)
     if (c.M <= most / c.ld_out && c.stride_out < c.M * c.ld_out)
-        return fail(pl, SD_ERR_INVALID, "%s: stride_out = %lld is less than the %lld elements of one statistic (M * ld_out)", who,
-                    (long long)c.stride_out, (long long)(c.M * c.ld_out));
+        return fail(pl, SD_ERR_INVALID, "%s: stride_out = %lld is less than the %lld elements of one statistic (%s * ld_out)", who,
+                    (long long)c.stride_out, (long long)(c.M * c.ld_out), binned ? "M" : "G");
     if (c.T > most / c.ld_a || c.T > most / c.ld_b || c.M > most / c.ld_out || c.stride_out > most / c.nstat)
         return fail(pl, SD_ERR_INVALID, "%s: field too large", who);
-    const sdbn::BinsPlan table = sdbn::check_offsets(sdbn::BinsPlan(), who, offsets, c.M, "T", c.T);
-    if (table.error != SD_OK) return fail(pl, table.error, "%s", table.message);
+    return pl;
+}
+
+// offsets [M + 1] of a call that twosample_check accepted, a table that starts at 0, never decreases and ends at T: the longest bin (what:
+// "bin" or "group" in the refusal) chooses the path and its width, then the refusals that depend on them
+inline TwosamplePlan twosample_geometry(TwosamplePlan pl, const TwosampleCall& c, const int64_t* offsets, const char* who, const char* what) {
+    using sdbn::fail;
+    if (pl.error != SD_OK) return pl;
     for (int64_t m = 0; m < c.M; ++m)
         if (offsets[m + 1] - offsets[m] > pl.n_max) pl.n_max = offsets[m + 1] - offsets[m];
     if (pl.n_max > kSeriesLimit)
-        return fail(pl, SD_ERR_UNSUPPORTED, "%s: a bin of %lld samples exceeds the workgroup merge (%lld)", who, (long long)pl.n_max,
+        return fail(pl, SD_ERR_UNSUPPORTED, "%s: a %s of %lld samples exceeds the workgroup merge (%lld)", who, what, (long long)pl.n_max,
                     (long long)kSeriesLimit);
     pl.vec_a = c.ld_a % 2 == 0 && c.a_aligned16;
     pl.vec_b = c.ld_b % 2 == 0 && c.b_aligned16;
@@ -157,6 +164,35 @@ inline TwosamplePlan twosample_plan(const TwosampleCall& c, const int64_t* offse
         return fail(pl, SD_ERR_INVALID, "%s: rows of %lld and %lld elements exceed the 32-bit row addressing", who, (long long)c.ld_a,
                     (long long)c.ld_b);
     return pl;
+}
+}  // namespace sdts
+
+// offsets [M + 1]: a host array
+inline TwosamplePlan twosample_plan(const TwosampleCall& c, const int64_t* offsets) {
+    using namespace sdts;
+    using sdbn::fail;
+    const char* const who = "sd_twosample";
+    TwosamplePlan pl = twosample_check(c, who, true);
+    if (pl.error != SD_OK) return pl;
+    const sdbn::BinsPlan table = sdbn::check_offsets(sdbn::BinsPlan(), who, offsets, c.M, "T", c.T);
+    if (table.error != SD_OK) return fail(pl, table.error, "%s", table.message);
+    return twosample_geometry(pl, c, offsets, who, "bin");
+}
+
+// group [T]: a host array; c.M is the number of groups G.  rows [T] and offsets [G + 1] receive the tables of groupby_tables (the row
+// table of gather_tile and the bins over it) once the ids have passed; they are not written by a refused call before that.
+inline TwosamplePlan twosample_groups_plan(const TwosampleCall& c, const int32_t* group, std::vector<int64_t>* rows, std::vector<int64_t>* offsets) {
+    using namespace sdts;
+    using sdbn::fail;
+    const char* const who = "sd_twosample_groups";
+    TwosamplePlan pl = twosample_check(c, who, false);
+    if (pl.error != SD_OK) return pl;
+    if (c.M <= 0) return fail(pl, SD_ERR_INVALID, "%s: bad sizes (G=%lld)", who, (long long)c.M);
+    const GroupbyPlan ids = groupby_check_groups(GroupbyPlan(), who, group, c.T, c.M);
+    if (ids.error != SD_OK) return fail(pl, ids.error, "%s", ids.message);
+    rows->assign((size_t)c.T, 0), offsets->assign((size_t)c.M + 1, 0);
+    groupby_tables(group, c.T, c.M, rows->data(), offsets->data());
+    return twosample_geometry(pl, c, offsets->data(), who, "group");
 }
 
 // what the plan chose, in words (tests/twosample_plan_check.cpp prints it)

@@ -161,6 +161,10 @@ SIGNATURES = {
     "sd_skill": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _p],
     "sd_twosample_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p, _i64, _i64],
     "sd_twosample": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p],
+    "sd_skill_groups_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _i64],
+    "sd_skill_groups": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _p],
+    "sd_twosample_groups_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p, _i64, _i64],
+    "sd_twosample_groups": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -16,7 +16,12 @@ depend on the layout or on ``scratch_bytes``, bit for bit.
 bins).  Limits: a bin holds at most 19 456 steps (``NotImplementedError`` beyond: 53 years of daily data in one bin), and one bin over
 the whole axis needs both whole [T, C] fields in HBM.
 
-Out of scope: p-values, ``by=`` groups of non-consecutive steps, CRPS and the Wasserstein distance, weighted samples.
+On a grouped comparison (``compare(obs).groupby("time.season").ks()``, ``skill.py``) a group -- the steps that carry one label, anywhere
+on the axis -- is evaluated exactly as one bin of its steps (sd_twosample_groups; tests/_grouped_pair_oracle.py): the same kernels read
+their rows through the group-sorted row table.  Both sources come into HBM whole: ``2 * T * C * itemsize`` bytes, plus ``16 * C * T``
+bytes of sorted runs where a group exceeds 1 216 steps; a group holds at most 19 456 steps.
+
+Out of scope: p-values, CRPS and the Wasserstein distance, weighted samples, cftime calendars.
 """
 from __future__ import annotations
 
@@ -52,35 +57,22 @@ def check_statistics(names, width=None, origin=0.0):
 
 class DistributionGridArray(DeferredGridArray):
     """Distribution scores of a ``GridComparison`` per bin and cell.  Dims: the first source's, with the compared dim at the number of
-    bins and the bin labels as its coordinate -- or dropped where the comparison was not resampled: the whole axis is one bin --, and
-    behind a leading ``"index"`` dim for ``distribution``."""
+    bins and the bin labels as its coordinate -- or replaced in place by the group dim with the sorted labels where the comparison was
+    grouped, or dropped where it was neither: the whole axis is one bin --, and behind a leading ``"index"`` dim for
+    ``distribution``."""
 
     def __init__(self, cmp, stats, width=None, origin=0.0, indexed=False, ctx=None):
         self._cmp, self._indexed, self._ctx = cmp, indexed, ctx
         self._stats, self._width, self._origin = check_statistics(stats, width, origin)
-        src, dim = cmp._a, cmp._dim
-        base = tuple(src.dims) if cmp._bins is not None else cmp._rest
-        if indexed and INDEX_DIM in base:
-            raise ValueError(f"the dim {INDEX_DIM!r} of distribution() is already a dim of this array {src.dims}")
-        self.dims = ((INDEX_DIM,) if indexed else ()) + base
-        self.coords = {k: v for k, v in src.coords.items() if k != dim}
-        if cmp._bins is not None:
-            self.coords[dim] = cmp._bins[0]
+        self.dims, self.coords, self._sizes, self._order = cmp._result_layout(indexed, "distribution")
         if indexed:
             self.coords[INDEX_DIM] = np.array(self._stats)
-        self.name = src.name
+        self.name = cmp._a.name
 
     # ---- the GridArray surface ----
     @property
     def sizes(self):
-        c = self._cmp
-        s = {INDEX_DIM: len(self._stats)} if self._indexed else {}
-        for d, n in c._a.sizes.items():
-            if d != c._dim:
-                s[d] = n
-            elif c._bins is not None:
-                s[d] = len(c._bins[0])
-        return s
+        return dict({INDEX_DIM: len(self._stats)} if self._indexed else {}, **self._sizes)
 
     @property
     def comparison(self):
@@ -112,7 +104,7 @@ class DistributionGridArray(DeferredGridArray):
     def isel(self, **indexers):
         """slices along the sources' other dims select from both sources (the result stays lazy); a selection along the compared dim
         or the index dim is made on the computed field"""
-        if any(d in indexers for d in (self._cmp._dim, INDEX_DIM)):
+        if any(d in indexers for d in (self._cmp._dim, self._cmp.group_dim, INDEX_DIM)):
             return self.compute().isel(**indexers)
         return DistributionGridArray(self._cmp._isel(**indexers), self._stats, self._width, self._origin, self._indexed, self._ctx)
 
@@ -122,11 +114,20 @@ class DistributionGridArray(DeferredGridArray):
         comparison was not resampled; C = cells of the other dims in the first source's order, the last fastest).  Both sources are
         walked in the same blocks of whole bins, together at most ``scratch_bytes`` (``timesource.walk_pair``); where one is a lazy
         source that gives its field through ``device_field``, both are taken whole.  A bin is always evaluated within one block: the
-        result does not depend on the block size, and one bin over the whole axis needs both whole fields in HBM."""
+        result does not depend on the block size, and one bin over the whole axis needs both whole fields in HBM.  A grouped
+        comparison gives [nstat * G, C], row ``s * G + g``, from one call on both whole fields: ``2 * T * C * itemsize`` bytes of HBM,
+        plus ``16 * C * T`` bytes of sorted runs where a group exceeds 1 216 steps."""
         ctx = self._context(ctx)
         c = self._cmp
         off = np.asarray(c.offsets, dtype=np.int64)
         M = len(off) - 1
+        if c._groups is not None:  # one block of both: the whole axis (off is its one bin)
+            G = len(c.group_labels)
+            with walk_pair(c._a, c._b, c._dim, ctx, c._scratch_bytes, "any", bins=off) as w:
+                out = w.result((len(self._stats) * G, w.cells))
+                for _, _, block_a, block_b, _ in w:
+                    ctx.twosample_groups(block_a, block_b, c.group, G, self._stats, width=self._width, origin=self._origin, out=out)
+            return out
         with walk_pair(c._a, c._b, c._dim, ctx, c._scratch_bytes, "any", bins=off) as w:
             out = w.result((len(self._stats) * M, w.cells))
             for i0, i1, block_a, block_b, r0 in w:
@@ -135,8 +136,7 @@ class DistributionGridArray(DeferredGridArray):
         return out
 
     def _field_order(self):
-        c = self._cmp
-        return ((INDEX_DIM,) if self._indexed else ()) + ((c._dim,) if c._bins is not None else ()) + c._rest
+        return self._order
 
     def __repr__(self):
         return f"<DistributionGridArray {self.sizes} {', '.join(self._stats)} of {self._cmp!r} computed={self.computed}>"

@@ -1016,6 +1016,21 @@ class Context:
             for a in mine:
                 a.free()
 
+    def _stat_planes(self, out, nstat, M, Cc, plane_rows):
+        """the output of a call that gives nstat statistics of M bins -> (out, elements between two statistics): the [nstat * M, C]
+        result, or with ``plane_rows`` the [M, C] view of this call's bins inside the first of nstat planes of a longer DeviceArray"""
+        if plane_rows is None:
+            out = self._result_buffer(out, (nstat * M, Cc), True)
+            stride = M * out.ld
+        else:
+            out = self._result_buffer(out, (M, Cc), True)
+            base = out.base
+            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
+            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
+                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
+            stride = int(plane_rows) * out.ld
+        return out, stride
+
     # ---- resampling of the time axis (GridArray.resample) ----
     @staticmethod
     def _resample_args(field, offsets, op):
@@ -1100,16 +1115,7 @@ class Context:
         field, code, thr, table, group, offsets, codes, L, f32 = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
         T, Cc = field.shape
         M, nstat = len(offsets) - 1, len(codes)
-        if plane_rows is None:
-            out = self._result_buffer(out, (nstat * M, Cc), True)
-            stride = M * out.ld
-        else:
-            out = self._result_buffer(out, (M, Cc), True)
-            base = out.base
-            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
-            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
-                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
-            stride = int(plane_rows) * out.ld
+        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
         with self._uploads() as up:
             field, table = up(field, field.dtype), up(table)
             self._same_context("sd_spells", field=field, threshold=table, out=out)
@@ -1132,25 +1138,48 @@ class Context:
 
     # ---- paired skill statistics per bin of the time axis (GridArray.compare) ----
     @staticmethod
-    def _skill_args(a, b, offsets, stats):
+    def _skill_fields(who, a, b, stats):
+        """the statistics and the two fields of a paired call -> (a, b, codes)"""
         stats = [stats] if isinstance(stats, str) else list(stats)
         for s in stats:
             if s not in _lib.SKILL_STATS:
                 raise ValueError(f"skill statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SKILL_STATS)}")
         if not 1 <= len(stats) <= len(_lib.SKILL_STATS):
-            raise ValueError(f"sd_downscale: sd_skill: nstat = {len(stats)}, expected 1 to {len(_lib.SKILL_STATS)} statistics")
+            raise ValueError(f"sd_downscale: {who}: nstat = {len(stats)}, expected 1 to {len(_lib.SKILL_STATS)} statistics")
         a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
         if tuple(a.shape) != tuple(b.shape):
             raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
+        return a, b, np.ascontiguousarray([_lib.SKILL_STATS[s] for s in stats], dtype=np.intc)
+
+    @staticmethod
+    def _bins_of_pair(who, a, offsets):
+        """offsets [M + 1] of a paired call on fields like ``a``"""
         T, Cc = a.shape
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if offsets.ndim != 1 or len(offsets) < 1:
             raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
         M = len(offsets) - 1
         if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_skill: bad sizes (T={T}, C={Cc}, M={M})")
-        codes = np.ascontiguousarray([_lib.SKILL_STATS[s] for s in stats], dtype=np.intc)
-        return a, b, offsets, codes
+            raise ValueError(f"sd_downscale: {who}: bad sizes (T={T}, C={Cc}, M={M})")
+        return offsets
+
+    @staticmethod
+    def _groups_of_pair(who, a, group, G):
+        """group [T] and G of a grouped paired call on fields like ``a``: the checks of ``_groupby_args``"""
+        T, Cc = a.shape
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (T,):
+            raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
+            raise ValueError(f"sd_downscale: {who}: bad sizes (T={T}, C={Cc})")
+        if int(G) < 1:
+            raise ValueError(f"sd_downscale: {who}: bad sizes (G={int(G)})")
+        return group, int(G)
+
+    @staticmethod
+    def _skill_args(a, b, offsets, stats):
+        a, b, codes = Context._skill_fields("sd_skill", a, b, stats)
+        return a, b, Context._bins_of_pair("sd_skill", a, offsets), codes
 
     def skill(self, a, b, offsets, stats, out=None, plane_rows=None):
         """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
@@ -1161,16 +1190,7 @@ class Context:
         a, b, offsets, codes = self._skill_args(a, b, offsets, stats)
         T, Cc = a.shape
         M, nstat = len(offsets) - 1, len(codes)
-        if plane_rows is None:
-            out = self._result_buffer(out, (nstat * M, Cc), True)
-            stride = M * out.ld
-        else:
-            out = self._result_buffer(out, (M, Cc), True)
-            base = out.base
-            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
-            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
-                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
-            stride = int(plane_rows) * out.ld
+        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
         with self._uploads() as up:
             same = b is a
             a = up(a, a.dtype)
@@ -1192,15 +1212,48 @@ class Context:
                                 ptr(codes), len(codes), ptr(out)))
         return out
 
+    def skill_groups(self, a, b, group, G, stats, out=None, plane_rows=None):
+        """``skill`` over groups of steps in place of bins: group: host int32 [T], every id in [0, G) -> [nstat * G, C] float64
+        DeviceArray, row ``s * G + g`` the statistic s of group g, evaluated as ``skill`` evaluates one bin whose steps are the rows
+        with ``group == g`` in ascending order: the bits of ``skill`` on the fields gathered group by group.  An id that never occurs
+        gives count 0 and NaN.  Both fields are whole on the device for the call (sd_skill_groups_dev).  ``out`` and ``plane_rows``:
+        as for ``spells``."""
+        a, b, codes = self._skill_fields("sd_skill_groups", a, b, stats)
+        group, G = self._groups_of_pair("sd_skill_groups", a, group, G)
+        T, Cc = a.shape
+        nstat = len(codes)
+        out, stride = self._stat_planes(out, nstat, G, Cc, plane_rows)
+        with self._uploads() as up:
+            same = b is a
+            a = up(a, a.dtype)
+            b = a if same else up(b, b.dtype)
+            self._same_context("sd_skill_groups", a=a, b=b, out=out)
+            check(self.lib.sd_skill_groups_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T,
+                                               Cc, ptr(group), G, ptr(codes), nstat, out.vptr, out.ld, stride))
+        return out
+
+    def skill_groups_host(self, a, b, group, G, stats):
+        """host [T, C] twice -> host [nstat * G, C] through sd_skill_groups (upload, run, download in one call)"""
+        a, b, codes = self._skill_fields("sd_skill_groups", a, b, stats)
+        group, G = self._groups_of_pair("sd_skill_groups", a, group, G)
+        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
+            raise ValueError("skill_groups_host: expected host arrays")
+        T, Cc = a.shape
+        out = np.empty((len(codes) * G, Cc))
+        check(self.lib.sd_skill_groups(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(group), G,
+                                       ptr(codes), len(codes), ptr(out)))
+        return out
+
     # ---- distribution scores per bin of the time axis (GridArray.compare(...).ks() / .perkins()) ----
     @staticmethod
-    def _twosample_args(a, b, offsets, stats, width, origin):
+    def _twosample_fields(who, a, b, stats, width, origin):
+        """the statistics, the histogram and the two fields of a two-sample call -> (a, b, codes, width, origin)"""
         stats = [stats] if isinstance(stats, str) else list(stats)
         for s in stats:
             if s not in _lib.TWOSAMPLE_STATS:
                 raise ValueError(f"distribution statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.TWOSAMPLE_STATS)}")
         if not 1 <= len(stats) <= len(_lib.TWOSAMPLE_STATS):
-            raise ValueError(f"sd_downscale: sd_twosample: nstat = {len(stats)}, expected 1 to {len(_lib.TWOSAMPLE_STATS)} statistics")
+            raise ValueError(f"sd_downscale: {who}: nstat = {len(stats)}, expected 1 to {len(_lib.TWOSAMPLE_STATS)} statistics")
         if "perkins" in stats:
             if width is None:
                 raise ValueError("perkins needs the width of the histogram bins (width=...)")
@@ -1212,16 +1265,14 @@ class Context:
         a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
         if tuple(a.shape) != tuple(b.shape):
             raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
-        T, Cc = a.shape
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
-        M = len(offsets) - 1
-        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_twosample: bad sizes (T={T}, C={Cc}, M={M})")
         codes = np.ascontiguousarray([_lib.TWOSAMPLE_STATS[s] for s in stats], dtype=np.intc)
         perkins = "perkins" in stats
-        return a, b, offsets, codes, float(width) if perkins else 0.0, float(origin) if perkins else 0.0
+        return a, b, codes, float(width) if perkins else 0.0, float(origin) if perkins else 0.0
+
+    @staticmethod
+    def _twosample_args(a, b, offsets, stats, width, origin):
+        a, b, codes, width, origin = Context._twosample_fields("sd_twosample", a, b, stats, width, origin)
+        return a, b, Context._bins_of_pair("sd_twosample", a, offsets), codes, width, origin
 
     def twosample(self, a, b, offsets, stats, width=None, origin=0.0, out=None, plane_rows=None):
         """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
@@ -1234,16 +1285,7 @@ class Context:
         a, b, offsets, codes, width, origin = self._twosample_args(a, b, offsets, stats, width, origin)
         T, Cc = a.shape
         M, nstat = len(offsets) - 1, len(codes)
-        if plane_rows is None:
-            out = self._result_buffer(out, (nstat * M, Cc), True)
-            stride = M * out.ld
-        else:
-            out = self._result_buffer(out, (M, Cc), True)
-            base = out.base
-            first = None if base is None or out.ld != base.ld else (out.ptr - base.ptr) // (base.ld * 8)
-            if first is None or plane_rows < M or first + (nstat - 1) * plane_rows + M > base.shape[0]:
-                raise ValueError(f"out: expected the rows of {M} bins inside the first of {nstat} planes of {plane_rows} rows of a DeviceArray")
-            stride = int(plane_rows) * out.ld
+        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
         with self._uploads() as up:
             same = b is a
             a = up(a, a.dtype)
@@ -1263,6 +1305,38 @@ class Context:
         out = np.empty((len(codes) * M, Cc))
         check(self.lib.sd_twosample(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(offsets), M,
                                     ptr(codes), len(codes), width, origin, ptr(out)))
+        return out
+
+    def twosample_groups(self, a, b, group, G, stats, width=None, origin=0.0, out=None, plane_rows=None):
+        """``twosample`` over groups of steps in place of bins: group: host int32 [T], every id in [0, G) -> [nstat * G, C] float64
+        DeviceArray, row ``s * G + g`` the statistic s of group g, evaluated as ``twosample`` evaluates one bin whose steps are the
+        rows with ``group == g``: the bits of ``twosample`` on the fields gathered group by group.  An id that never occurs gives na =
+        nb = 0 and NaN.  A group holds at most 19 456 rows (NotImplementedError beyond); both fields are whole on the device for the
+        call (sd_twosample_groups_dev).  ``out`` and ``plane_rows``: as for ``spells``."""
+        a, b, codes, width, origin = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
+        group, G = self._groups_of_pair("sd_twosample_groups", a, group, G)
+        T, Cc = a.shape
+        nstat = len(codes)
+        out, stride = self._stat_planes(out, nstat, G, Cc, plane_rows)
+        with self._uploads() as up:
+            same = b is a
+            a = up(a, a.dtype)
+            b = a if same else up(b, b.dtype)
+            self._same_context("sd_twosample_groups", a=a, b=b, out=out)
+            check(self.lib.sd_twosample_groups_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld,
+                                                   T, Cc, ptr(group), G, ptr(codes), nstat, width, origin, out.vptr, out.ld, stride))
+        return out
+
+    def twosample_groups_host(self, a, b, group, G, stats, width=None, origin=0.0):
+        """host [T, C] twice -> host [nstat * G, C] through sd_twosample_groups (upload, run, download in one call)"""
+        a, b, codes, width, origin = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
+        group, G = self._groups_of_pair("sd_twosample_groups", a, group, G)
+        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
+            raise ValueError("twosample_groups_host: expected host arrays")
+        T, Cc = a.shape
+        out = np.empty((len(codes) * G, Cc))
+        check(self.lib.sd_twosample_groups(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(group), G,
+                                           ptr(codes), len(codes), width, origin, ptr(out)))
         return out
 
     # ---- temporal disaggregation (GridArray.disaggregate) ----

@@ -731,9 +731,102 @@ def bench_twosample(ctx, args):
     return res
 
 
+def bench_skill_groups(ctx, args):
+    """compare(...).groupby(...) on the fields of the skill workload (14 600 daily steps x 100 000 cells, float64 against float64):
+    skill_groups_kernel for ["bias", "rmse"] (one pass) and ["bias", "rmse", "corr"] (two passes) by month (12 groups), by season (4)
+    and by day of year (366), each beside skill_kernel over the 40 'YS' bins with the same statistics in the same run (the same bytes
+    of both fields; GB/s by algorithmic bytes: 16 * T * C read per pass + 8 * T of row table per tile of cells + 8 * nstat * G * C
+    written); then sd_twosample_groups for ["ks"] and ["ks", "perkins"] (width 1) by month (the series path) and by day of year (the
+    segment path), beside two sd_quantile_dev(by=) calls with Q = 1 on the two fields over the same groups.  Timed through ctx.prof()
+    (the sum over the kernels of a call; median and [min, max] of 7 profiled calls after a warm-up); the first 256 (paired) and 64
+    (two-sample) cells compared bit for bit with the grouped oracle"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _grouped_pair_oracle as gp
+    from skdownscale_amd.groupby import group_labels
+    from skdownscale_amd.resample import time_bins
+
+    T, C = args.times, 100_000
+    index = synth.daily_calendar(T)
+    labels, yearly = time_bins(index, "YS")
+    yearly = np.asarray(yearly, dtype=np.int64)
+    tabs = synth.tas_tables(index)
+
+    def fill(cells, tab):  # (a cell shard of the synthetic field holds the same values as those cells of the whole field)
+        return ctx.synth_fill(ctx.empty((T, cells)), synth.GAUSS, 0, tab["stream"], c_full=C, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+
+    def timed(call, repeats):
+        call()
+        ctx.prof_enable(True)
+        times, kernels = [], {}
+        for _ in range(repeats):
+            ctx.prof_reset()
+            call()
+            prof = ctx.prof()
+            times.append(sum(v["ms"] for v in prof.values()))
+            for k, v in prof.items():
+                kernels.setdefault(k, []).append(v["ms"])
+        ctx.prof_enable(False)
+        return {"kernel_ms": float(np.median(times)), "kernel_ms_min_max": [min(times), max(times)],
+                "kernels_ms": {k: float(np.median(v)) for k, v in kernels.items()}}
+
+    def ids_of(field):
+        found, ids = np.unique(group_labels(index, field), return_inverse=True)
+        return ids.astype(np.int32), len(found)
+
+    a, b = fill(C, tabs["X_hist"]), fill(C, tabs["y_obs"])
+    first_a, first_b = fill(256, tabs["X_hist"]).to_host(), fill(256, tabs["y_obs"]).to_host()
+    repeats = 7
+    src_bytes = 2 * 8 * T * C
+    res = {"workload": f"skill_groups {T} daily steps x {C} cells float64 against float64: bias, rmse (one pass) and bias, rmse, corr (two passes) by month, "
+                       f"season and day of year beside {len(labels)} 'YS' bins; ks and ks, perkins(width=1) by month and day of year", "repeats": repeats}
+    groupings = {name: ids_of(name) for name in ("month", "season", "dayofyear")}
+    M = len(yearly) - 1
+    for stats, passes in ((["bias", "rmse"], 1), (["bias", "rmse", "corr"], 2)):
+        key = "_".join(stats)
+        out = ctx.empty((len(stats) * M, C))
+        ys = timed(lambda: ctx.skill(a, b, yearly, stats, out=out), repeats)
+        out.free()
+        ys.update({"statistics": stats, "bins": M, "algorithmic_bytes": passes * src_bytes + 8 * len(stats) * M * C})
+        ys["GBps"] = ys["algorithmic_bytes"] / ys["kernel_ms"] / 1e6
+        res[f"YS_skill_kernel_{key}"] = ys
+        for name, (ids, G) in groupings.items():
+            out = ctx.empty((len(stats) * G, C))
+            r = timed(lambda: ctx.skill_groups(a, b, ids, G, stats, out=out), repeats)
+            ms = r["kernel_ms"]
+            ctiles = -(-C // 128)  # two cells per lane
+            nbytes = passes * (src_bytes + 8 * T * ctiles) + 8 * len(stats) * G * C
+            got, want = out.cells(0, 256).to_host(), gp.skill(first_a, first_b, ids, G, stats)
+            r.update({"statistics": stats, "passes": passes, "groups": G, "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                      "frac_of_8TBps": nbytes / ms / 1e6 / 8000.0, "bit_identical_to_oracle_first_256_cells": bool(np.array_equal(got, want, equal_nan=True)),
+                      "kernel_over_YS_skill_kernel_ms": ms / ys["kernel_ms"]})
+            res[f"{name}_{key}"] = r
+            out.free()
+    width, origin = 1.0, 0.0
+    for name in ("month", "dayofyear"):
+        ids, G = groupings[name]
+        med = ctx.empty((G, C))
+        q_a = timed(lambda: ctx.quantile(a, [0.5], ids, G, out=med), repeats)
+        q_b = timed(lambda: ctx.quantile(b, [0.5], ids, G, out=med), repeats)
+        med.free()
+        res[f"{name}_quantile_q1_a"], res[f"{name}_quantile_q1_b"] = q_a, q_b
+        quantile_ms = q_a["kernel_ms"] + q_b["kernel_ms"]
+        for stats in (["ks"], ["ks", "perkins"]):
+            two = ctx.empty((len(stats) * G, C))
+            r = timed(lambda: ctx.twosample_groups(a, b, ids, G, stats, width, origin, out=two), repeats)
+            ms = r["kernel_ms"]
+            nbytes = src_bytes + 8 * len(stats) * G * C
+            got, want = two.cells(0, 64).to_host(), gp.twosample(first_a[:, :64], first_b[:, :64], ids, G, stats, width, origin)
+            r.update({"statistics": stats, "groups": G, "longest_group": int(np.bincount(ids).max()), "algorithmic_bytes": nbytes, "GBps": nbytes / ms / 1e6,
+                      "bit_identical_to_oracle_first_64_cells": bool(np.array_equal(got, want, equal_nan=True)), "two_quantile_calls_ms": quantile_ms,
+                      "kernel_over_two_quantile_calls": ms / quantile_ms})
+            res[f"{name}_{'_'.join(stats)}"] = r
+            two.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample", "skill_groups"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -752,10 +845,10 @@ def main():
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
         return
-    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells", "skill", "twosample"):
+    if args.workload in ("regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "quantile", "spells", "skill", "twosample", "skill_groups"):
         line = json.dumps({"regrid": bench_regrid, "regrid_e2e": bench_regrid_e2e, "resample": bench_resample, "disagg": bench_disagg,
                            "groupby": bench_groupby, "rolling": bench_rolling, "quantile": bench_quantile, "spells": bench_spells, "skill": bench_skill,
-                           "twosample": bench_twosample}[args.workload](ctx, args))
+                           "twosample": bench_twosample, "skill_groups": bench_skill_groups}[args.workload](ctx, args))
         print(line)
         if args.out:
             with open(args.out, "a") as f:
