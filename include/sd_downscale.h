@@ -752,6 +752,68 @@ int sd_twosample_groups_dev(sd_ctx* ctx, const void* a_dev, int a_is_f32, int64_
 int sd_twosample_groups(sd_ctx* ctx, const void* a_host, int a_is_f32, const void* b_host, int b_is_f32, int64_t T, int64_t C,
                         const int32_t* group, int64_t G, const int* stats, int nstat, double width, double origin, double* out_host);
 
+/* ---- constructed analogs: ConstructedAnalogs (Hidalgo et al. 2008; Maurer et al. 2010), the operation under BCCA, MACA and LOCA ----
+ * For each target day: the k library days whose coarse pattern is closest (sd_ca_select_dev), the regression of the target pattern on
+ * those k patterns (sd_ca_weights_dev), and the k weights applied to the fine fields of the same days (sd_ca_apply_dev).
+ *
+ * Inputs.  L [Tl, Cc] float64 the coarse library, Q [Tq, Cc] float64 the coarse targets, F [Tl, Cf] the fine library (float64, or
+ * float32 with f_is_f32 != 0, widened to double per sample): device buffers, row-major, rows ld_l / ld_q / ld_f elements apart.
+ * wc [Cc] float64 column weights, finite and >= 0; key_l [Tl], key_q [Tq] int32 candidate keys; excl_l [Tl], excl_q [Tq] int32
+ * exclusion ids: small tables in HOST memory, like the group ids of the other calls.  k in [1, 32] analogs; ridge >= 0; kind
+ * SD_CA_REGRESSION or SD_CA_MEAN; period and window integers.
+ *
+ * The rule.  No contraction (-ffp-contract=off): a product and the addition of it are two operations.
+ *  1. Valid columns.  Column c is used when L[:, c] is finite in every row and wc[c] > 0.  The used columns keep their ascending
+ *     order.  If no column is used the call fails with SD_ERR_INVALID.
+ *  2. Candidates.  Library day t is a candidate of target q when both hold: window < 0, or min(|a - b|, period - |a - b|) <= window
+ *     with a = key_q[q], b = key_l[t] (in int64); and excl_q[q] < 0, or excl_l[t] != excl_q[q].
+ *  3. Distance.  d(q, t) = ((+0.0 + wc[c0] * (e0 * e0)) + wc[c1] * (e1 * e1)) + ... over the used columns in ascending order, with
+ *     e = Q[q, c] - L[t, c].  The expansion |q|^2 + |l|^2 - 2 q.l is excluded on purpose: on fields near 280 K its cancellation would
+ *     decide which of two near-equal days is picked.
+ *  4. Selection.  The analogs of q are the k candidates smallest by (d, t) in lexicographic order, listed in that order: ties go to
+ *     the lower t, so the result cannot depend on how the library is tiled.
+ *  5. kind = SD_CA_MEAN: every weight is 1.0 / k.
+ *  6. kind = SD_CA_REGRESSION: with a_i the library row of analog i,
+ *       G[i][j] = sum_c wc[c] * (a_i[c] * a_j[c]),  b[i] = sum_c wc[c] * (a_i[c] * Q[q, c]),
+ *     both over the used columns in ascending order from +0.0; lambda = ridge * ((G[0][0] + G[1][1] + ...) / k) (the trace summed from
+ *     G[0][0] in ascending order), G[i][i] += lambda.  Lower Cholesky factor row by row: for i, for j <= i:
+ *       s = G[i][j]; for p < j in ascending order: s -= C[i][p] * C[j][p];  j < i: C[i][j] = s / C[j][j];  j == i: the pivot s must be
+ *       > 0 (NaN is not), C[i][i] = sqrt(s).
+ *     Forward: for i ascending: s = b[i]; for p < i ascending: s -= C[i][p] * y[p]; y[i] = s / C[i][i].
+ *     Back: for i descending: s = y[i]; for p = i + 1 .. k - 1 ascending: s -= C[p][i] * w[p]; w[i] = s / C[i][i].
+ *     tests/_constructed_oracle.py is normative for the order of every operation.
+ *  7. Status per target, the first that applies: SD_CA_QUERY_NONFINITE a used column of Q[q] is not finite; SD_CA_FEW_CANDIDATES
+ *     there are fewer than k candidates; SD_CA_SINGULAR a pivot is not > 0; else SD_CA_OK.  Any status other than OK gives indices -1,
+ *     NaN distances and weights, and a NaN output row.
+ *  8. Synthesis.  out[q, f] = ((+0.0 + w_0 * F[i_0, f]) + w_1 * F[i_1, f]) + ... in analog order.  NaN in F propagates by IEEE
+ *     arithmetic with no special case; -0.0 becomes +0.0.  A row whose first index lies outside [0, Tl) is a NaN row.
+ * Every value is one fixed sequence of IEEE operations: the result is the same bit for bit whatever the leading dimensions, the tiling
+ * of the library or of the targets, and the cut [q0, q1) of an apply call.
+ *
+ * sd_ca_select_dev: steps 1 to 4 -> idx int32 [Tq, k], dist float64 [Tq, k], status int32 [Tq] (device, contiguous).
+ * sd_ca_weights_dev: steps 5 to 7 from idx -> weights float64 [Tq, k]; updates status, and idx / dist of a singular target.
+ * sd_ca_apply_dev: step 8 for the target rows [q0, q1): idx and weights are the whole [Tq, k] tables, out_dev points at row q0, rows
+ * ld_out >= Cf apart.
+ *
+ * NULL pointers, sizes <= 0, k outside [1, 32], a leading dimension below the row length, wc negative or not finite, period <= 0 with
+ * window >= 0, an unknown kind, ridge negative or not finite, rows outside [0, Tq) are SD_ERR_INVALID; Tl > 2^24 or Cc > 2^16 are
+ * SD_ERR_UNSUPPORTED: all refused before anything is allocated or launched.  Out of scope: MACA's epoch adjustment and multivariate
+ * patterns, LOCA's per-cell analog choice, k > 32. */
+#define SD_CA_REGRESSION 0
+#define SD_CA_MEAN 1
+#define SD_CA_OK 0
+#define SD_CA_QUERY_NONFINITE 1
+#define SD_CA_FEW_CANDIDATES 2
+#define SD_CA_SINGULAR 3
+int sd_ca_select_dev(sd_ctx* ctx, const double* L_dev, int64_t ld_l, int64_t Tl, const double* Q_dev, int64_t ld_q, int64_t Tq, int64_t Cc,
+                     const double* wc, int k, const int32_t* key_l, const int32_t* key_q, int64_t period, int64_t window,
+                     const int32_t* excl_l, const int32_t* excl_q, int32_t* idx_dev, double* dist_dev, int32_t* status_dev);
+int sd_ca_weights_dev(sd_ctx* ctx, const double* L_dev, int64_t ld_l, int64_t Tl, const double* Q_dev, int64_t ld_q, int64_t Tq, int64_t Cc,
+                      const double* wc, int k, int kind, double ridge, int32_t* idx_dev, double* dist_dev, double* weights_dev,
+                      int32_t* status_dev);
+int sd_ca_apply_dev(sd_ctx* ctx, const void* F_dev, int f_is_f32, int64_t ld_f, int64_t Tl, int64_t Cf, const int32_t* idx_dev,
+                    const double* weights_dev, int64_t Tq, int k, int64_t q0, int64_t q1, double* out_dev, int64_t ld_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side
  * collection of the result; here cells are block-partitioned over the ranks of one node, fit / predict need no exchange

@@ -19,6 +19,7 @@ from .order_stats import TimeQuantileGridArray
 from .spells import GridCondition, SpellGridArray
 from .skill import GridComparison, SkillGridArray
 from .distribution import DistributionGridArray
+from .constructed import ConstructedAnalogs, ConstructedGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -76,5 +77,7 @@ __all__ = [
     "GridComparison",
     "SkillGridArray",
     "DistributionGridArray",
+    "ConstructedAnalogs",
+    "ConstructedGridArray",
 ]
 __version__ = "0.1.0"

@@ -34,6 +34,9 @@ SPELL_OPS = {">": 0, ">=": 1, "<": 2, "<=": 3}  # SD_SPELL_GT .. _LE
 SPELL_STATS = {"valid": 0, "count": 1, "fraction": 2, "longest_spell": 3, "spell_days": 4, "spell_count": 5}  # SD_SPELL_VALID .. _SPELL_COUNT
 SKILL_STATS = {"count": 0, "bias": 1, "ratio": 2, "mae": 3, "rmse": 4, "corr": 5, "std_ratio": 6}  # SD_SKILL_COUNT .. _STD_RATIO
 TWOSAMPLE_STATS = {"ks": 0, "perkins": 1, "na": 2, "nb": 3}  # SD_TWOSAMPLE_KS .. _NB
+CA_KINDS = {"regression": 0, "mean": 1}  # SD_CA_REGRESSION, SD_CA_MEAN
+CA_OK, CA_QUERY_NONFINITE, CA_FEW_CANDIDATES, CA_SINGULAR = 0, 1, 2, 3  # SD_CA_*: status per target
+CA_MAX_ANALOGS = 32
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -165,6 +168,9 @@ SIGNATURES = {
     "sd_skill_groups": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _p],
     "sd_twosample_groups_dev": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p, _i64, _i64],
     "sd_twosample_groups": [_p, _p, _int, _p, _int, _i64, _i64, _p, _i64, _p, _int, _dbl, _dbl, _p],
+    "sd_ca_select_dev": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _int, _p, _p, _i64, _i64, _p, _p, _p, _p, _p],
+    "sd_ca_weights_dev": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _int, _int, _dbl, _p, _p, _p, _p],
+    "sd_ca_apply_dev": [_p, _p, _int, _i64, _i64, _i64, _p, _p, _i64, _int, _i64, _i64, _p, _i64],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -1574,6 +1574,107 @@ class Context:
                                   int(bool(wrap)), ptr(out)))
         return out
 
+    # ---- constructed analogs (ConstructedAnalogs) ----
+    @staticmethod
+    def _ca_coarse(who, L, Q, wc, k):
+        """the coarse side of a constructed-analog call: L [Tl, Cc] and Q [Tq, Cc] float64, wc [Cc] on the host, k"""
+        L, Q = Context._field("L", L, "Tl", "Cc"), Context._field("Q", Q, "Tq", "Cc")
+        if Q.shape[1] != L.shape[1]:
+            raise ValueError(f"Q: expected a [Tq, {L.shape[1]}] field like L, got shape {tuple(Q.shape)}")
+        if min(L.shape + Q.shape) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
+            raise ValueError(f"sd_downscale: {who}: bad sizes (Tl={L.shape[0]}, Tq={Q.shape[0]}, Cc={L.shape[1]})")
+        wc = _lib.as_f64(wc)
+        if wc.shape != (L.shape[1],):
+            raise ValueError(f"wc: expected {L.shape[1]} column weights, got shape {wc.shape}")
+        k = int(k)
+        if not 1 <= k <= _lib.CA_MAX_ANALOGS:
+            raise ValueError(f"sd_downscale: {who}: k = {k} lies outside [1, {_lib.CA_MAX_ANALOGS}]")
+        return L, Q, wc, k
+
+    @staticmethod
+    def _ca_ids(name, ids, n):
+        """one int32 per day (keys, exclusion ids); None: -1 for every day"""
+        ids = np.full(n, -1, dtype=np.int32) if ids is None else _lib.as_i32(ids)
+        if ids.shape != (n,):
+            raise ValueError(f"{name}: expected one id per day ({n}), got shape {ids.shape}")
+        return ids
+
+    def _ca_table(self, name, a, Tq, k, dtype):
+        if not isinstance(a, DeviceArray) or tuple(a.shape) != (Tq, k) or a.dtype != dtype or a.ld != k:
+            raise ValueError(f"{name}: expected a contiguous {np.dtype(dtype).name} DeviceArray of shape ({Tq}, {k})")
+        return a
+
+    def ca_select(self, L, Q, wc, k, key_l=None, key_q=None, period=1, window=-1, excl_l=None, excl_q=None):
+        """L [Tl, Cc], Q [Tq, Cc]: float64 host arrays or DeviceArrays (rows ``ld`` apart); wc [Cc] host column weights; key_*, excl_*:
+        host int32 per day (None: key 0 / no exclusion) -> (idx int32 [Tq, k], dist float64 [Tq, k], status int32 [Tq]) DeviceArrays:
+        the k candidates of each target smallest by (distance, day) (sd_ca_select_dev; the rule is in include/sd_downscale.h).
+        ``window`` < 0: every day is inside the window."""
+        L, Q, wc, k = self._ca_coarse("sd_ca_select", L, Q, wc, k)
+        Tl, Tq = L.shape[0], Q.shape[0]
+        key_l = np.zeros(Tl, np.int32) if key_l is None else self._ca_ids("key_l", key_l, Tl)
+        key_q = np.zeros(Tq, np.int32) if key_q is None else self._ca_ids("key_q", key_q, Tq)
+        excl_l, excl_q = self._ca_ids("excl_l", excl_l, Tl), self._ca_ids("excl_q", excl_q, Tq)
+        with self._uploads() as up:
+            L, Q = up(L), up(Q)
+            self._same_context("sd_ca_select", L=L, Q=Q)
+            idx, dist, status = self.empty((Tq, k), np.int32), self.empty((Tq, k)), self.empty((Tq,), np.int32)
+            try:
+                check(self.lib.sd_ca_select_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, L.shape[1], ptr(wc), k, ptr(key_l), ptr(key_q),
+                                                int(period), int(window), ptr(excl_l), ptr(excl_q), idx.vptr, dist.vptr, status.vptr))
+            except BaseException:
+                for a in (idx, dist, status):
+                    a.free()
+                raise
+        return idx, dist, status
+
+    def ca_weights(self, L, Q, wc, idx, dist, status, kind="regression", ridge=1e-6):
+        """the weights of the analogs ``idx`` of ``ca_select`` -> float64 [Tq, k] DeviceArray; ``status`` is updated, and ``idx`` /
+        ``dist`` of a target with a singular Gram matrix are cleared.  kind 'regression' (ridge-regularised least squares of the target
+        pattern on the k library patterns) | 'mean' (1 / k) (sd_ca_weights_dev)."""
+        if kind not in _lib.CA_KINDS:
+            raise ValueError(f"kind={kind!r}: expected one of {', '.join(repr(s) for s in _lib.CA_KINDS)}")
+        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
+            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
+        L, Q, wc, k = self._ca_coarse("sd_ca_weights", L, Q, wc, idx.shape[1])
+        Tl, Tq = L.shape[0], Q.shape[0]
+        idx, dist = self._ca_table("idx", idx, Tq, k, np.int32), self._ca_table("dist", dist, Tq, k, np.float64)
+        if not isinstance(status, DeviceArray) or tuple(status.shape) != (Tq,) or status.dtype != np.int32:
+            raise ValueError(f"status: expected an int32 DeviceArray of shape ({Tq},)")
+        ridge = float(ridge)
+        if not (ridge >= 0.0 and np.isfinite(ridge)):
+            raise ValueError(f"sd_downscale: sd_ca_weights: ridge = {ridge:g}, expected a finite factor >= 0")
+        with self._uploads() as up:
+            L, Q = up(L), up(Q)
+            self._same_context("sd_ca_weights", L=L, Q=Q, idx=idx, dist=dist, status=status)
+            weights = self.empty((Tq, k))
+            try:
+                check(self.lib.sd_ca_weights_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, L.shape[1], ptr(wc), k, _lib.CA_KINDS[kind], ridge,
+                                                 idx.vptr, dist.vptr, weights.vptr, status.vptr))
+            except BaseException:
+                weights.free()
+                raise
+        return weights
+
+    def ca_apply(self, F, idx, weights, q0=0, q1=None, out=None):
+        """F [Tl, Cf]: the fine library, a float32 / float64 DeviceArray (rows ``ld`` apart); idx, weights: the [Tq, k] tables ->
+        float64 [q1 - q0, Cf] DeviceArray: rows [q0, q1) of ``out[q] = sum_i weights[q, i] * F[idx[q, i]]`` in analog order
+        (sd_ca_apply_dev).  ``out``: that DeviceArray, possibly a view of a wider or longer one."""
+        if not isinstance(F, DeviceArray) or len(F.shape) != 2 or F.dtype not in (np.float32, np.float64):
+            raise ValueError("F: expected a float32 or float64 [Tl, Cf] DeviceArray")
+        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
+            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
+        Tq, k = idx.shape
+        idx, weights = self._ca_table("idx", idx, Tq, k, np.int32), self._ca_table("weights", weights, Tq, k, np.float64)
+        q0, q1 = int(q0), Tq if q1 is None else int(q1)
+        if not 0 <= q0 < q1 <= Tq:
+            raise ValueError(f"sd_downscale: sd_ca_apply: rows [{q0}, {q1}) lie outside the {Tq} targets")
+        Tl, Cf = F.shape
+        out = self._result_buffer(out, (q1 - q0, Cf), True)
+        self._same_context("sd_ca_apply", F=F, idx=idx, weights=weights, out=out)
+        check(self.lib.sd_ca_apply_dev(self.handle, F.vptr, int(F.dtype == np.float32), F.ld, Tl, Cf, idx.vptr, weights.vptr, Tq, k, q0, q1,
+                                       out.vptr, out.ld))
+        return out
+
 
 _default_ctx = None
 

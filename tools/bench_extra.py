@@ -824,9 +824,97 @@ def bench_skill_groups(ctx, args):
     return res
 
 
+def bench_constructed(ctx, args):
+    """The three constructed-analog kernels, each alone (ctx.prof(): an event pair around the launch; median and [min, max] of the
+    repeats after a warm-up), at Tl = 14 600 library days, Tq = 3 650 targets, Cc = 400 (20 x 20) coarse and Cf = 100 000 fine cells,
+    k = 30, window 45, with the fine library as float32 and as float64, beside sd_memcpy_d2d of the output bytes.  ca_select_kernel:
+    achieved float64 operations per second (3 per target, day and used column beside the square) against the vector peak;
+    ca_apply_kernel: time against the floor Tl * Cf * itemsize + 8 * Tq * Cf bytes at 8 TB/s.  ``--part apply`` runs the apply kernel
+    only (for a counter pass of its own).  -> one result per type of the fine library"""
+    Tl, Tq, Cc, Cf, k, window = args.times, max(1, args.times // 4), 400, args.cells if args.cells != 8192 else 100_000, args.k, 45
+    index = synth.daily_calendar(Tl + Tq)
+    doy = np.asarray(index.dayofyear).astype(np.int32)
+    tab = synth.tas_tables(index[:Tl])["y_obs"]
+    L = ctx.synth_fill(ctx.empty((Tl, Cc)), synth.GAUSS, 0, tab["stream"], c_full=Cc, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+    tq = synth.tas_tables(index[Tl:])["X_fut"]
+    Q = ctx.synth_fill(ctx.empty((Tq, Cc)), synth.GAUSS, 0, tq["stream"], c_full=Cc, base=tq["base"], amp=tq["amp"], cell_scale=tq["cell_scale"])
+    wc = np.repeat(np.cos(np.deg2rad(np.linspace(30.0, 50.0, 20))), 20)
+    F64 = ctx.synth_fill(ctx.empty((Tl, Cf)), synth.GAUSS, 0, tab["stream"], c_full=Cf, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+    out, spare = ctx.empty((Tq, Cf)), ctx.empty((Tq, Cf))
+    repeats = max(args.steps, 5)
+
+    def timed(kernel, call, free=False):
+        times = []
+        for i in range(repeats + 1):  # (the first one warms up)
+            ctx.prof_enable(True)
+            ctx.prof_reset()
+            made = call()
+            ctx.synchronize()
+            times.append(ctx.prof()[kernel]["ms"])
+            ctx.prof_enable(False)
+            if free and i < repeats:
+                for a in made if isinstance(made, tuple) else (made,):
+                    a.free()
+        return float(np.median(times[1:])), [min(times[1:]), max(times[1:])], made
+
+    select = lambda: ctx.ca_select(L, Q, wc, k, doy[:Tl], doy[Tl:], 366, window)  # noqa: E731
+    if args.part == "apply":
+        idx, dist, status = select()
+        sel = wgt = None
+    else:
+        sel_ms, sel_mm, (idx, dist, status) = timed("ca_select_kernel", select, free=True)
+        flops = 3.0 * Tq * Tl * Cc
+        sel = {"kernel_ms": sel_ms, "kernel_ms_min_max": sel_mm, "float64_ops": flops, "TFLOPs": flops / sel_ms / 1e9,
+               "frac_of_vector_peak_78.6_TFLOPs": flops / sel_ms / 1e9 / 78.6}
+    first = lambda: ctx.ca_weights(L, Q, wc, idx, dist, status, "regression", 1e-6)  # noqa: E731
+    if args.part == "apply":
+        weights = first()
+    else:
+        wgt_ms, wgt_mm, weights = timed("ca_weights_kernel", first, free=True)
+        wgt = {"kernel_ms": wgt_ms, "kernel_ms_min_max": wgt_mm}
+    st = status.to_host()
+    # three targets against the rule restated with plain loops (tests/_constructed_oracle.py), bit for bit
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _constructed_oracle as co
+
+    picks = [0, 1, Tq - 1]
+    Lh, Qh = L.to_host(), Q.to_host()[picks]
+    none_l, none_q = np.full(Tl, -1, np.int32), np.full(len(picks), -1, np.int32)
+    eidx, edist, est = co.select(Lh, Qh, wc, k, doy[:Tl], doy[Tl:][picks], 366, window, none_l, none_q)
+    ew, eidx, edist, est = co.weights(Lh, Qh, wc, eidx, edist, est, co.REGRESSION, 1e-6)
+    same = bool(np.array_equal(idx.to_host()[picks], eidx) and np.array_equal(dist.to_host()[picks], edist, equal_nan=True)
+                and np.array_equal(weights.to_host()[picks], ew, equal_nan=True) and np.array_equal(st[picks], est))
+    copy_ms, copy_mm = device_copy_ms(ctx, spare, out, 8 * Tq * Cf, repeats)
+    results = []
+    for name, dtype in (("f32", np.float32), ("f64", np.float64)):
+        if dtype == np.float32:
+            F = ctx.empty((Tl, Cf), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, F64.vptr, Tl * Cf, F.vptr))
+            ctx.synchronize()
+        else:
+            F = F64
+        ms, mm, _ = timed("ca_apply_kernel", lambda: ctx.ca_apply(F, idx, weights, out=out))
+        used = np.unique(eidx[eidx >= 0])  # the library rows of the three targets: the synthesis against the rule, whole rows
+        Fs = np.stack([F.rows(int(t), int(t) + 1).to_host()[0] for t in used])
+        got = np.stack([out.rows(q, q + 1).to_host()[0] for q in picks])
+        same_out = bool(np.array_equal(got, co.apply(Fs, np.where(eidx >= 0, np.searchsorted(used, eidx), -1), ew), equal_nan=True))
+        floor = Tl * Cf * np.dtype(dtype).itemsize + 8 * Tq * Cf
+        naive = Tq * k * Cf * np.dtype(dtype).itemsize + 8 * Tq * Cf
+        results.append({"workload": f"constructed analogs: Tl={Tl}, Tq={Tq}, Cc={Cc}, Cf={Cf}, k={k}, window={window}, {name} fine library",
+                        "repeats": repeats, "fine": name, "targets_ok": int((st == 0).sum()),
+                        "tables_bit_identical_to_oracle_targets_0_1_last": same, "ca_select_kernel": sel, "ca_weights_kernel": wgt,
+                        "ca_apply_kernel": {"kernel_ms": ms, "kernel_ms_min_max": mm, "floor_bytes": floor, "floor_ms_at_8TBps": floor / 8e9,
+                                            "time_over_floor": ms / (floor / 8e9), "gathered_bytes": naive, "gathered_GBps": naive / ms / 1e6,
+                                            "bit_identical_to_oracle_targets_0_1_last": same_out},
+                        "device_copy_of_output": {"ms": copy_ms, "ms_min_max": copy_mm, "bytes": 8 * Tq * Cf}})
+        if F is not F64:
+            F.free()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample", "skill_groups"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample", "skill_groups", "constructed"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -834,11 +922,12 @@ def main():
     ap.add_argument("--k", type=int, default=30)
     ap.add_argument("--kind", default="mean_analogs")
     ap.add_argument("--features", type=int, default=1)
+    ap.add_argument("--part", default="all", choices=["all", "apply"], help="constructed: time every kernel, or run ca_apply_kernel only")
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload == "remap":  # one JSON line per source type
-        for res in bench_remap(ctx, args):
+    if args.workload in ("remap", "constructed"):  # one JSON line per source type
+        for res in (bench_remap if args.workload == "remap" else bench_constructed)(ctx, args):
             line = json.dumps(res)
             print(line)
             if args.out:
