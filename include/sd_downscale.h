@@ -798,7 +798,7 @@ int sd_twosample_groups(sd_ctx* ctx, const void* a_host, int a_is_f32, const voi
  * NULL pointers, sizes <= 0, k outside [1, 32], a leading dimension below the row length, wc negative or not finite, period <= 0 with
  * window >= 0, an unknown kind, ridge negative or not finite, rows outside [0, Tq) are SD_ERR_INVALID; Tl > 2^24 or Cc > 2^16 are
  * SD_ERR_UNSUPPORTED: all refused before anything is allocated or launched.  Out of scope: MACA's epoch adjustment and multivariate
- * patterns, LOCA's per-cell analog choice, k > 32. */
+ * patterns, k > 32.  (LOCA's per-cell choice of analogs is the section below.) */
 #define SD_CA_REGRESSION 0
 #define SD_CA_MEAN 1
 #define SD_CA_OK 0
@@ -813,6 +813,56 @@ int sd_ca_weights_dev(sd_ctx* ctx, const double* L_dev, int64_t ld_l, int64_t Tl
                       int32_t* status_dev);
 int sd_ca_apply_dev(sd_ctx* ctx, const void* F_dev, int f_is_f32, int64_t ld_f, int64_t Tl, int64_t Cf, const int32_t* idx_dev,
                     const double* weights_dev, int64_t Tq, int k, int64_t q0, int64_t q1, double* out_dev, int64_t ld_out);
+
+/* ---- localized analogs: LocalizedAnalogs (LOCA, Pierce et al. 2014): one library day per coarse cell instead of one blend per day ----
+ * From the k regional analogs of a target day (sd_ca_select_dev) every coarse cell keeps the one that matches the target best in the
+ * neighbourhood of that cell (sd_ca_local_dev); the fine field copies, cell by cell, the fine library of the day chosen for the coarse
+ * cell it lies in, shifted or scaled to the coarse target (sd_ca_local_apply_dev).
+ *
+ * Inputs.  L [Tl, Cc], Q [Tq, Cc], wc [Cc], k and idx [Tq, k] as sd_ca_select_dev left them.  The coarse grid is ny x nx with
+ * Cc == ny * nx, column c = i * nx + j (row-major).  Radii ry >= 0 and rx >= 0 in coarse cells.  cell_of [Cf] int32 (device): the
+ * coarse column of every fine cell.
+ *
+ * The rule.  No contraction, as above.  tests/_localized_oracle.py is normative for the order of every operation.
+ *  L1. Used columns: step 1 of the constructed rule (no used column: SD_ERR_INVALID).
+ *  L2. Local distance of target q, analog slot a in 0 .. k - 1 with t = idx[q, a], and coarse cell (i, j):
+ *        dl = +0.0; for i' ascending over max(0, i - ry) .. min(ny - 1, i + ry): for j' ascending over max(0, j - rx) ..
+ *        min(nx - 1, j + rx): with c' = i' * nx + j': if c' is used: e = Q[q, c'] - L[t, c'], dl = dl + wc[c'] * (e * e).
+ *      A column that is not used is skipped, not weighted 0: its e may be NaN.
+ *  L3. Choice.  slot[q, c] is the lowest a at which dl is smallest (a ascending, replaced on strict <: ties go to the regionally
+ *      closer day); local_idx[q, c] = idx[q, slot] (int32), local_dist[q, c] that dl.  Every coarse cell gets a choice, the unused
+ *      ones too; a neighbourhood without a used column gives +0.0 for every slot, hence slot 0.  A target with idx[q, 0] < 0 (any
+ *      status other than OK) -- or, for a table that sd_ca_select_dev did not make, with any index outside [0, Tl) -- gives
+ *      local_idx = -1 and local_dist = NaN for the whole row.
+ *  L4. Synthesis.  With c = cell_of[f]: out[q, f] = NaN where c lies outside [0, Cc) or local_idx[q, c] outside [0, Tl).
+ *      Otherwise t = local_idx[q, c], v = (double) F[t, f], and
+ *        SD_CA_ADJUST_NONE:  out = v;
+ *        SD_CA_ADJUST_SHIFT: out = v + (Q[q, c] - L[t, c]);
+ *        SD_CA_ADJUST_SCALE: r = Q[q, c] / L[t, c] if L[t, c] > 0, else 1.0; if max_scale > 0 and r > max_scale: r = max_scale;
+ *                            out = v * r.
+ *      NaN in F, Q or L propagates by IEEE arithmetic with no special case (an unused coarse column under SHIFT / SCALE).
+ * Every value is one fixed sequence of IEEE operations: the result is the same bit for bit whatever the leading dimensions, the tiling
+ * and the cut [q0, q1) of an apply call.
+ *
+ * sd_ca_local_dev: L1 to L3 -> local_idx int32 [Tq, ny * nx], local_dist float64 [Tq, ny * nx] (device, contiguous).
+ * sd_ca_local_apply_dev: L4 for the target rows [q0, q1): local_idx is the whole [Tq, Cc] table, out_dev points at row q0, rows
+ * ld_out >= Cf apart.  L_dev and Q_dev may be NULL with SD_CA_ADJUST_NONE only.
+ *
+ * NULL pointers, sizes <= 0, k outside [1, 32], a negative radius, a leading dimension below the row length, wc negative or not
+ * finite, an unknown adjust, max_scale NaN or negative (0: no limit), rows outside [0, Tq) are SD_ERR_INVALID; Tl > 2^24 or a coarse
+ * grid of more than SD_CA_LOCAL_MAX_CELLS cells (what the local kernel stages of one target must fit the LDS of a workgroup) are
+ * SD_ERR_UNSUPPORTED: all refused before anything is allocated or launched.  Out of scope: LOCA's smoothing across the boundaries
+ * between different analog days, its multivariate and bias-correction steps, curvilinear grids. */
+#define SD_CA_ADJUST_NONE 0
+#define SD_CA_ADJUST_SHIFT 1
+#define SD_CA_ADJUST_SCALE 2
+#define SD_CA_LOCAL_MAX_CELLS 4096
+int sd_ca_local_dev(sd_ctx* ctx, const double* L_dev, int64_t ld_l, int64_t Tl, const double* Q_dev, int64_t ld_q, int64_t Tq, int64_t ny,
+                    int64_t nx, const double* wc /* host [ny * nx] */, int k, int64_t ry, int64_t rx, const int32_t* idx_dev /* [Tq, k] */,
+                    int32_t* local_idx_dev /* [Tq, ny * nx] */, double* local_dist_dev /* [Tq, ny * nx] */);
+int sd_ca_local_apply_dev(sd_ctx* ctx, const void* F_dev, int f_is_f32, int64_t ld_f, int64_t Tl, int64_t Cf, const int32_t* cell_of_dev,
+                          const int32_t* local_idx_dev, int64_t Cc, const double* L_dev, int64_t ld_l, const double* Q_dev, int64_t ld_q,
+                          int adjust, double max_scale, int64_t Tq, int64_t q0, int64_t q1, double* out_dev, int64_t ld_out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no PyTorch) -----------------------------------
  * The reference's only parallelism is dask's map_blocks over spatial chunks (core.py:256-262, 300-336) and a client-side

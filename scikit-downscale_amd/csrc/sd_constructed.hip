@@ -3,8 +3,8 @@
 // days.  The rule is stated in include/sd_downscale.h and restated by tests/_constructed_oracle.py; the launch plans and the tile
 // constants are in sd_constructed_plan.h.
 //
-// ca_columns_kernel: one thread per coarse column walks the library rows and says whether the column is used (finite throughout and
-// wc > 0).  The flags come back to the host, which makes the ascending list of used columns (at most 2^16 ints; the only host round trip).
+// ca_columns_kernel (sd_constructed_cols.h, shared with sd_localized.hip): one thread per coarse column says whether the column is used.
+// The flags come back to the host, which makes the ascending list of used columns (at most 2^16 ints; the only host round trip).
 //
 // ca_select_kernel: a workgroup of 256 threads owns kSelQ = 8 targets and sweeps the library in tiles of kSelL = 128 days.  The used
 // columns of both are staged kSelCols = 32 at a time in LDS, column-major, so that a thread reads its 4 library days as two 16-byte LDS
@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "sd_constructed_cols.h"
 #include "sd_constructed_plan.h"
 #include "sd_internal.h"
 #include "sd_state.h"
@@ -35,20 +36,8 @@
 namespace {
 using namespace sdca;
 
-__device__ __forceinline__ double ca_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ __forceinline__ double ca_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-__device__ __forceinline__ bool ca_finite(double v) { return fabs(v) < ca_inf(); }  // (false for NaN)
 // (d, t) < (e, u) in lexicographic order
 __device__ __forceinline__ bool ca_less(double d, int32_t t, double e, int32_t u) { return d < e || (d == e && t < u); }
-
-__global__ void __launch_bounds__(256) ca_columns_kernel(const double* __restrict__ L, int64_t ld_l, int64_t Tl, int Cc,
-                                                         const double* __restrict__ wc, int32_t* __restrict__ used) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= Cc) return;
-    bool ok = wc[c] > 0.0;
-    for (int64_t t = 0; t < Tl; ++t) ok = ok && ca_finite(L[t * ld_l + c]);
-    used[c] = ok ? 1 : 0;
-}
 
 __global__ void __launch_bounds__(kSelBlock) ca_select_kernel(const double* __restrict__ L, int64_t ld_l, int Tl, const double* __restrict__ Q,
                                                              int64_t ld_q, int64_t Tq, const int32_t* __restrict__ cols,
@@ -335,20 +324,12 @@ struct CaColumns {
 };
 
 int ca_used_columns(sd_ctx* ctx, const char* who, const double* L_dev, int64_t ld_l, int64_t Tl, int64_t Cc, const double* wc, CaColumns& u) {
-    sd_scratch wc_dev, flags;
-    SD_TRY(upload(ctx, wc_dev, std::vector<double>(wc, wc + Cc)));
-    SD_HIP(flags.alloc(ctx, sizeof(int32_t) * Cc));
-    const dim3 grid((unsigned)((Cc + 255) / 256)), block(256);
-    SD_LAUNCH(ctx, "ca_columns_kernel", ca_columns_kernel, grid, block, 0, L_dev, ld_l, Tl, (int)Cc, (const double*)wc_dev.p, flags.as<int32_t>());
-    std::vector<int32_t> used((size_t)Cc);
-    SD_HIP(hipMemcpyAsync(used.data(), flags.p, sizeof(int32_t) * Cc, hipMemcpyDeviceToHost, ctx->stream));
-    SD_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> used;
+    SD_TRY(ca_column_flags(ctx, who, L_dev, ld_l, Tl, Cc, wc, used));
     std::vector<int32_t> cols;
     std::vector<double> wcu;
     for (int64_t c = 0; c < Cc; ++c)
         if (used[(size_t)c] != 0) cols.push_back((int32_t)c), wcu.push_back(wc[c]);
-    if (cols.empty())
-        return sd_set_error(SD_ERR_INVALID, "%s: no column is used (a column needs a library that is finite in every row and wc > 0)", who);
     u.nu = (int)cols.size();
     SD_TRY(upload(ctx, u.cols, cols));
     SD_TRY(upload(ctx, u.wcu, wcu));

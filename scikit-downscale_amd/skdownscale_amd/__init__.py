@@ -20,6 +20,7 @@ from .spells import GridCondition, SpellGridArray
 from .skill import GridComparison, SkillGridArray
 from .distribution import DistributionGridArray
 from .constructed import ConstructedAnalogs, ConstructedGridArray
+from .localized import LocalizedAnalogs, LocalizedGridArray
 from .quantile import (CunnaneGridModel, CunnaneTransformer, EquidistantCdfMatcher, QmGridModel, QuantileMapper,
                        QuantileMapperGridModel, QuantileMappingReressor, TrendAwareQuantileMappingRegressor)
 from .trend import LinearTrendTransformer
@@ -79,5 +80,7 @@ __all__ = [
     "DistributionGridArray",
     "ConstructedAnalogs",
     "ConstructedGridArray",
+    "LocalizedAnalogs",
+    "LocalizedGridArray",
 ]
 __version__ = "0.1.0"

@@ -37,6 +37,8 @@ TWOSAMPLE_STATS = {"ks": 0, "perkins": 1, "na": 2, "nb": 3}  # SD_TWOSAMPLE_KS .
 CA_KINDS = {"regression": 0, "mean": 1}  # SD_CA_REGRESSION, SD_CA_MEAN
 CA_OK, CA_QUERY_NONFINITE, CA_FEW_CANDIDATES, CA_SINGULAR = 0, 1, 2, 3  # SD_CA_*: status per target
 CA_MAX_ANALOGS = 32
+CA_ADJUST = {"none": 0, "shift": 1, "scale": 2}  # SD_CA_ADJUST_NONE, _SHIFT, _SCALE
+CA_LOCAL_MAX_CELLS = 4096  # SD_CA_LOCAL_MAX_CELLS: coarse cells of a localized-analog grid
 SYNTH_GAUSS, SYNTH_PRECIP = 0, 1
 
 _p = C.c_void_p
@@ -171,6 +173,8 @@ SIGNATURES = {
     "sd_ca_select_dev": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _int, _p, _p, _i64, _i64, _p, _p, _p, _p, _p],
     "sd_ca_weights_dev": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _int, _int, _dbl, _p, _p, _p, _p],
     "sd_ca_apply_dev": [_p, _p, _int, _i64, _i64, _i64, _p, _p, _i64, _int, _i64, _i64, _p, _i64],
+    "sd_ca_local_dev": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _int, _i64, _i64, _p, _p, _p],
+    "sd_ca_local_apply_dev": [_p, _p, _int, _i64, _i64, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _int, _dbl, _i64, _i64, _i64, _p, _i64],
     "sd_comm_unique_id": [_p],
     "sd_comm_create": [_p, _p, _int, _int, C.POINTER(_p)],
     "sd_comm_destroy": [_p],

@@ -9,9 +9,9 @@ a ``ConstructedGridArray``, is lazy: the fine field is synthesised in HBM when i
 (``resample``, ``groupby``, ``rolling``), so that neither the fine library nor the fine result crosses PCIe more than once.
 
 The rule -- fixed-order float64 sums, ties to the earlier day -- is stated in include/sd_downscale.h and restated by
-tests/_constructed_oracle.py.  Out of scope: MACA's epoch adjustment and multivariate patterns, LOCA's per-cell choice of analogs, the
-bias-correction step of BCCA (``BcsdTemperature`` on the coarse grid does it), cftime calendars, more than 32 analogs and the sharded
-path.
+tests/_constructed_oracle.py.  LOCA's per-cell choice of analogs is ``LocalizedAnalogs`` (localized.py).  Out of scope: MACA's epoch
+adjustment and multivariate patterns, the bias-correction step of BCCA (``BcsdTemperature`` on the coarse grid does it), cftime
+calendars, more than 32 analogs and the sharded path.
 """
 from __future__ import annotations
 
@@ -131,10 +131,11 @@ class ConstructedAnalogs:
         return self
 
     # ---- predict ----
-    def predict(self, target, ctx=None):
+    def _coarse_target(self, target):
+        """the checks of a target -> (its time index, Q [Tq, Cc] in the library's column order, key_l, key_q, excl_l, excl_q)"""
         if self._coarse is None:
-            raise ValueError("this ConstructedAnalogs is not fitted: call fit(coarse_library, fine_library) first")
-        dim, spatial, k = self.dim, self._coarse["dims"], self.n_analogs
+            raise ValueError(f"this {type(self).__name__} is not fitted: call fit(coarse_library, fine_library) first")
+        dim, spatial = self.dim, self._coarse["dims"]
         if not isinstance(target, GridArray):
             raise ValueError(f"the target: expected a GridArray, got {type(target).__name__}")
         if set(target.dims) != {dim, *spatial} or len(target.dims) != len(spatial) + 1:
@@ -154,6 +155,18 @@ class ConstructedAnalogs:
         key_l, key_q = self._time.dayofyear.to_numpy().astype(np.int32), tq.dayofyear.to_numpy().astype(np.int32)
         excl_l = self._time.year.to_numpy().astype(np.int32) if self.exclude_same_year else None
         excl_q = tq.year.to_numpy().astype(np.int32) if self.exclude_same_year else None
+        return tq, Q, key_l, key_q, excl_l, excl_q
+
+    def _few_candidates(self, status, tq):
+        few = np.flatnonzero(status == _lib.CA_FEW_CANDIDATES)
+        if len(few):
+            q = int(few[0])
+            raise ValueError(f"step {q} of the target ({tq[q]}) has fewer than n_analogs={self.n_analogs} candidate days in the library "
+                             f"(window={self.window}, exclude_same_year={self.exclude_same_year})")
+
+    def predict(self, target, ctx=None):
+        tq, Q, key_l, key_q, excl_l, excl_q = self._coarse_target(target)
+        dim, k = self.dim, self.n_analogs
         if ctx is None:
             from .engine import default_context
 
@@ -171,11 +184,8 @@ class ConstructedAnalogs:
             for a in made:
                 a.free()
         self.analog_index_, self.analog_distance_, self.weights_, self.status_ = idx, dist, weights, status
-        few, singular = np.flatnonzero(status == _lib.CA_FEW_CANDIDATES), np.flatnonzero(status == _lib.CA_SINGULAR)
-        if len(few):
-            q = int(few[0])
-            raise ValueError(f"step {q} of the target ({tq[q]}) has fewer than n_analogs={k} candidate days in the library "
-                             f"(window={self.window}, exclude_same_year={self.exclude_same_year})")
+        self._few_candidates(status, tq)
+        singular = np.flatnonzero(status == _lib.CA_SINGULAR)
         if len(singular):
             q = int(singular[0])
             raise ArithmeticError(f"step {q} of the target ({tq[q]}): the Gram matrix of its {k} analogs is not positive definite "

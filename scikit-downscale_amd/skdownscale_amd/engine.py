@@ -1675,6 +1675,73 @@ class Context:
                                        out.vptr, out.ld))
         return out
 
+    # ---- localized analogs (LocalizedAnalogs) ----
+    def ca_local(self, L, Q, wc, grid, radius, idx):
+        """L [Tl, ny * nx], Q [Tq, ny * nx], wc: as for ``ca_select``; grid (ny, nx) of the coarse cells, radius (ry, rx) in coarse
+        cells; idx: the int32 [Tq, k] DeviceArray of ``ca_select`` -> (local_idx int32 [Tq, ny * nx], local_dist float64
+        [Tq, ny * nx]) DeviceArrays: per coarse cell the analog whose distance over the cell's neighbourhood is smallest, ties to the
+        lower slot (sd_ca_local_dev; the rule is in include/sd_downscale.h)."""
+        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
+            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
+        L, Q, wc, k = self._ca_coarse("sd_ca_local", L, Q, wc, idx.shape[1])
+        Tl, Tq, Cc = L.shape[0], Q.shape[0], L.shape[1]
+        try:
+            (ny, nx), (ry, rx) = (int(n) for n in grid), (int(r) for r in radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"grid={grid!r}, radius={radius!r}: expected (ny, nx) and (ry, rx)") from None
+        if ny < 1 or nx < 1 or ny * nx != Cc:
+            raise ValueError(f"grid: expected (ny, nx) with ny * nx = {Cc} columns, got ({ny}, {nx})")
+        if ry < 0 or rx < 0:
+            raise ValueError(f"sd_downscale: sd_ca_local: radii ({ry}, {rx}), expected two numbers of coarse cells >= 0")
+        idx = self._ca_table("idx", idx, Tq, k, np.int32)
+        with self._uploads() as up:
+            L, Q = up(L), up(Q)
+            self._same_context("sd_ca_local", L=L, Q=Q, idx=idx)
+            local_idx, local_dist = self.empty((Tq, Cc), np.int32), self.empty((Tq, Cc))
+            try:
+                check(self.lib.sd_ca_local_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, ny, nx, ptr(wc), k, ry, rx, idx.vptr,
+                                               local_idx.vptr, local_dist.vptr))
+            except BaseException:
+                local_idx.free(), local_dist.free()
+                raise
+        return local_idx, local_dist
+
+    def ca_local_apply(self, F, cell_of, local_idx, L=None, Q=None, adjust="none", max_scale=0.0, q0=0, q1=None, out=None):
+        """F [Tl, Cf]: the fine library, a float32 / float64 DeviceArray (rows ``ld`` apart); cell_of: int32 [Cf] DeviceArray, the
+        coarse column of every fine cell; local_idx: the int32 [Tq, Cc] table of ``ca_local``; L [Tl, Cc], Q [Tq, Cc]: float64
+        DeviceArrays, needed unless adjust is 'none' -> float64 [q1 - q0, Cf] DeviceArray: rows [q0, q1) of
+        ``out[q, f] = F[local_idx[q, cell_of[f]], f]``, shifted by Q - L or scaled by Q / L (at most ``max_scale``; 0: no limit) of
+        that day and coarse cell (sd_ca_local_apply_dev).  ``out``: that DeviceArray, possibly a view of a wider or longer one."""
+        if not isinstance(F, DeviceArray) or len(F.shape) != 2 or F.dtype not in (np.float32, np.float64):
+            raise ValueError("F: expected a float32 or float64 [Tl, Cf] DeviceArray")
+        Tl, Cf = F.shape
+        if not isinstance(cell_of, DeviceArray) or tuple(cell_of.shape) != (Cf,) or cell_of.dtype != np.int32:
+            raise ValueError(f"cell_of: expected an int32 DeviceArray of shape ({Cf},)")
+        if not isinstance(local_idx, DeviceArray) or len(local_idx.shape) != 2:
+            raise ValueError("local_idx: expected the int32 [Tq, Cc] DeviceArray of ca_local")
+        Tq, Cc = local_idx.shape
+        local_idx = self._ca_table("local_idx", local_idx, Tq, Cc, np.int32)
+        if adjust not in _lib.CA_ADJUST:
+            raise ValueError(f"adjust={adjust!r}: expected one of {', '.join(repr(s) for s in _lib.CA_ADJUST)}")
+        max_scale = float(max_scale)
+        if not max_scale >= 0.0:
+            raise ValueError(f"sd_downscale: sd_ca_local_apply: max_scale = {max_scale:g}, expected 0 (no limit) or a limit > 0")
+        if adjust == "none":
+            L = Q = None  # (not read)
+        else:
+            for name, a, rows, what in (("L", L, Tl, "Tl"), ("Q", Q, Tq, "Tq")):
+                if not isinstance(a, DeviceArray) or tuple(a.shape) != (rows, Cc) or a.dtype != np.float64:
+                    raise ValueError(f"{name}: adjust={adjust!r} needs a float64 DeviceArray of shape ({rows}, {Cc}) [{what}, Cc]")
+        q0, q1 = int(q0), Tq if q1 is None else int(q1)
+        if not 0 <= q0 < q1 <= Tq:
+            raise ValueError(f"sd_downscale: sd_ca_local_apply: rows [{q0}, {q1}) lie outside the {Tq} targets")
+        out = self._result_buffer(out, (q1 - q0, Cf), True)
+        self._same_context("sd_ca_local_apply", F=F, cell_of=cell_of, local_idx=local_idx, L=L, Q=Q, out=out)
+        check(self.lib.sd_ca_local_apply_dev(self.handle, F.vptr, int(F.dtype == np.float32), F.ld, Tl, Cf, cell_of.vptr, local_idx.vptr, Cc,
+                                             vptr(L), 0 if L is None else L.ld, vptr(Q), 0 if Q is None else Q.ld, _lib.CA_ADJUST[adjust],
+                                             max_scale, Tq, q0, q1, out.vptr, out.ld))
+        return out
+
 
 _default_ctx = None
 

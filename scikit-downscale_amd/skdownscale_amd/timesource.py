@@ -24,7 +24,7 @@ TAKEN_WHOLE = {
     "resample": frozenset(),
     "groupby": _REDUCED,  # the source of GroupReducedGridArray and GroupAppliedGridArray
     "rolling": _TABLES,
-    "any": _TABLES | {"disagg", "remap", "constructed"},  # TimeQuantileGridArray, SpellGridArray, SkillGridArray (both sources)
+    "any": _TABLES | {"disagg", "remap", "constructed", "localized"},  # TimeQuantileGridArray, SpellGridArray, SkillGridArray (both sources)
     "remap": _TABLES | {"disagg"},  # dims must be (lead, *spatial)
     "table": frozenset({"group_reduced", "rolling", "quantile"}),  # GroupAppliedGridArray's other: dims must be in order
     "target": frozenset({"resample"}),  # DisaggregatedGridArray's monthly field: dims must be in order

@@ -912,9 +912,97 @@ def bench_constructed(ctx, args):
     return results
 
 
+def bench_localized(ctx, args):
+    """The two localized-analog kernels, each alone (ctx.prof(): an event pair around the launch; median and [min, max] of the repeats
+    after a warm-up), at the constructed workload's shape: Tl = 14 600 library days, Tq = 3 650 targets, 20 x 20 coarse cells,
+    Cf = 100 000 fine cells (250 x 400: a coarse cell is 20 fine cells wide), k = 30, radius 2, with the fine library as float32 and as
+    float64 and adjust 'none' and 'shift'; beside ca_select_kernel, sd_memcpy_d2d of the output bytes and ca_apply_kernel of the same
+    run.  ca_local_apply_kernel: time against the floor Tq * Cf * (itemsize + 8) bytes at 8 TB/s.  Three targets are compared with the
+    rule restated with plain loops (tests/_localized_oracle.py), bit for bit.  -> one result per type of the fine library"""
+    Tl, Tq, ny, nx, Cf, k, window, radius = args.times, max(1, args.times // 4), 20, 20, args.cells if args.cells != 8192 else 100_000, args.k, 45, (2, 2)
+    Cc = ny * nx
+    index = synth.daily_calendar(Tl + Tq)
+    doy = np.asarray(index.dayofyear).astype(np.int32)
+    tab = synth.tas_tables(index[:Tl])["y_obs"]
+    L = ctx.synth_fill(ctx.empty((Tl, Cc)), synth.GAUSS, 0, tab["stream"], c_full=Cc, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+    tq = synth.tas_tables(index[Tl:])["X_fut"]
+    Q = ctx.synth_fill(ctx.empty((Tq, Cc)), synth.GAUSS, 0, tq["stream"], c_full=Cc, base=tq["base"], amp=tq["amp"], cell_scale=tq["cell_scale"])
+    wc = np.repeat(np.cos(np.deg2rad(np.linspace(30.0, 50.0, ny))), nx)
+    F64 = ctx.synth_fill(ctx.empty((Tl, Cf)), synth.GAUSS, 0, tab["stream"], c_full=Cf, base=tab["base"], amp=tab["amp"], cell_scale=tab["cell_scale"])
+    fx = 400 if Cf % 400 == 0 else Cf  # the fine grid: rows of fx cells
+    fy = Cf // fx
+    f = np.arange(Cf)
+    cell_of_host = ((f // fx) * ny // fy * nx + (f % fx) * nx // fx).astype(np.int32)
+    cell_of = ctx.to_device(cell_of_host, np.int32)
+    out, spare = ctx.empty((Tq, Cf)), ctx.empty((Tq, Cf))
+    repeats = max(args.steps, 5)
+
+    def timed(kernel, call, free=False):
+        times = []
+        for i in range(repeats + 1):  # (the first one warms up)
+            ctx.prof_enable(True)
+            ctx.prof_reset()
+            made = call()
+            ctx.synchronize()
+            times.append(ctx.prof()[kernel]["ms"])
+            ctx.prof_enable(False)
+            if free and i < repeats:
+                for a in made if isinstance(made, tuple) else (made,):
+                    a.free()
+        return float(np.median(times[1:])), [min(times[1:]), max(times[1:])], made
+
+    sel_ms, sel_mm, (idx, dist, status) = timed("ca_select_kernel", lambda: ctx.ca_select(L, Q, wc, k, doy[:Tl], doy[Tl:], 366, window), free=True)
+    loc_ms, loc_mm, (lidx, ldist) = timed("ca_local_kernel", lambda: ctx.ca_local(L, Q, wc, (ny, nx), radius, idx), free=True)
+    weights = ctx.ca_weights(L, Q, wc, idx, dist, status, "regression", 1e-6)
+    st = status.to_host()
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _localized_oracle as lo
+
+    picks = [0, 1, Tq - 1]
+    Lh, Qh, lidx_h = L.to_host(), Q.to_host()[picks], lidx.to_host()
+    eslot, elidx, eldist = lo.local(Lh, Qh, wc, idx.to_host()[picks], ny, nx, *radius)
+    same = bool(np.array_equal(lidx_h[picks], elidx) and np.array_equal(ldist.to_host()[picks], eldist, equal_nan=True))
+    sample = lidx_h[::37]  # (every 37th target)
+    runs = len(sample) + int((np.diff(sample[:, cell_of_host], axis=1) != 0).sum())  # stretches of consecutive fine cells that copy one library day
+    copy_ms, copy_mm = device_copy_ms(ctx, spare, out, 8 * Tq * Cf, repeats)
+    results = []
+    for name, dtype in (("f32", np.float32), ("f64", np.float64)):
+        if dtype == np.float32:
+            F = ctx.empty((Tl, Cf), np.float32)
+            _lib.check(ctx.lib.sd_convert_f64_to_f32_dev(ctx.handle, F64.vptr, Tl * Cf, F.vptr))
+            ctx.synchronize()
+        else:
+            F = F64
+        blend_ms, blend_mm, _ = timed("ca_apply_kernel", lambda: ctx.ca_apply(F, idx, weights, out=out))
+        used = np.unique(elidx[elidx >= 0])  # the library rows of the three targets: the synthesis against the rule, whole rows
+        Fs = np.stack([F.rows(int(t), int(t) + 1).to_host()[0] for t in used])
+        floor = Tq * Cf * (np.dtype(dtype).itemsize + 8)
+        res = {"workload": f"localized analogs: Tl={Tl}, Tq={Tq}, coarse {ny} x {nx}, Cf={Cf}, k={k}, window={window}, radius={radius[0]}, "
+                           f"{name} fine library", "repeats": repeats, "fine": name, "targets_ok": int((st == 0).sum()),
+               "distinct_days_per_target_mean": float(np.mean([len(np.unique(r)) for r in sample])),
+               "mean_run_of_one_library_day_in_fine_cells": len(sample) * Cf / runs, "choice_bit_identical_to_oracle_targets_0_1_last": same,
+               "ca_select_kernel": {"kernel_ms": sel_ms, "kernel_ms_min_max": sel_mm},
+               "ca_local_kernel": {"kernel_ms": loc_ms, "kernel_ms_min_max": loc_mm, "over_ca_select_kernel": loc_ms / sel_ms},
+               "ca_apply_kernel": {"kernel_ms": blend_ms, "kernel_ms_min_max": blend_mm},
+               "device_copy_of_output": {"ms": copy_ms, "ms_min_max": copy_mm, "bytes": 8 * Tq * Cf}}
+        for adjust in ("none", "shift"):
+            ms, mm, _ = timed("ca_local_apply_kernel", lambda: ctx.ca_local_apply(F, cell_of, lidx, L, Q, adjust=adjust, out=out))
+            got = np.stack([out.rows(q, q + 1).to_host()[0] for q in picks])
+            want = lo.local_apply(Fs, cell_of_host, np.where(elidx >= 0, np.searchsorted(used, elidx), -1).astype(np.int32), Lh[used], Qh,
+                                  getattr(lo, "ADJUST_" + adjust.upper()))
+            res[f"ca_local_apply_kernel_{adjust}"] = {"kernel_ms": ms, "kernel_ms_min_max": mm, "floor_bytes": floor, "floor_ms_at_8TBps": floor / 8e9,
+                                                      "time_over_floor": ms / (floor / 8e9), "floor_GBps": floor / ms / 1e6,
+                                                      "over_ca_apply_kernel": ms / blend_ms, "over_device_copy": ms / copy_ms,
+                                                      "bit_identical_to_oracle_targets_0_1_last": bool(np.array_equal(got, want, equal_nan=True))}
+        results.append(res)
+        if F is not F64:
+            F.free()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample", "skill_groups", "constructed"],
+    ap.add_argument("--workload", choices=["bcsd_pr", "analog", "analogreg", "qmr", "ecm", "pure_regression", "zscore", "grouped", "arrm", "regrid", "regrid_e2e", "resample", "disagg", "groupby", "rolling", "remap", "quantile", "spells", "skill", "twosample", "skill_groups", "constructed", "localized"],
                     default="analog")
     ap.add_argument("--cells", type=int, default=8192)
     ap.add_argument("--times", type=int, default=14600)
@@ -926,8 +1014,8 @@ def main():
     ap.add_argument("--out", default=None, help="append the JSON line to this file")
     args = ap.parse_args()
     ctx = Context(0)
-    if args.workload in ("remap", "constructed"):  # one JSON line per source type
-        for res in (bench_remap if args.workload == "remap" else bench_constructed)(ctx, args):
+    if args.workload in ("remap", "constructed", "localized"):  # one JSON line per source type
+        for res in {"remap": bench_remap, "constructed": bench_constructed, "localized": bench_localized}[args.workload](ctx, args):
             line = json.dumps(res)
             print(line)
             if args.out:
