@@ -87,6 +87,11 @@ def vptr(a):
     return None if a is None else a.vptr
 
 
+def _f32(a):
+    """the flag the ABI takes beside a float32 / float64 field: 1 for float32"""
+    return int(a.dtype == np.float32)
+
+
 class _State:
     """A handle of the library.  ``ABI`` is the prefix of the family's entry points (``ABI_info``, ``ABI_destroy``), ``INFO`` the
     (key, ctype) of what ``ABI_info`` gives, in the order of its arguments."""
@@ -262,23 +267,21 @@ class RegridState(_State):
         float64 DeviceArray, cells fastest (``out``: a [T, C] DeviceArray, possibly a cells() view of a wider one).  float32 goes to
         the device as float32 and is widened in the kernel."""
         i = self.info()
-        src, f32 = self._source(src, i)
+        src = self._source(src, i)
         T = src.shape[0]
-        if not isinstance(src, DeviceArray):
-            src = self.ctx.to_device(src, src.dtype)
-        out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
-        check(self.ctx.lib.sd_regrid_apply_dev(self.ctx.handle, self.vptr, src.vptr, f32, T, out.vptr, out.ld))
+        with self.ctx._uploads() as up:
+            src = up(src)
+            out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
+            self.ctx._same_context("sd_regrid", src=src, out=out)
+            check(self.ctx.lib.sd_regrid_apply_dev(self.ctx.handle, self.vptr, src.vptr, _f32(src), T, out.vptr, out.ld))
         return out
 
     def apply_host(self, src):
         """host [T, ny, nx] -> host [T, Ny * Nx] through sd_regrid_apply (upload, run, download in one call)"""
         i = self.info()
-        src, f32 = self._source(src, i)
-        if isinstance(src, DeviceArray):
-            raise ValueError("apply_host: expected a host array")
-        out = np.empty((src.shape[0], i["Ny"] * i["Nx"]))
-        check(self.ctx.lib.sd_regrid_apply(self.ctx.handle, self.vptr, ptr(src), f32, src.shape[0], ptr(out)))
-        return out
+        src = self._source(src, i)
+        T = src.shape[0]
+        return self.ctx._on_host("apply", self.ctx.lib.sd_regrid_apply, (T, i["Ny"] * i["Nx"]), self.vptr, src, _f32(src), T)
 
     @staticmethod
     def _source(src, i):
@@ -288,7 +291,7 @@ class RegridState(_State):
             raise ValueError(f"src: expected a [T, {i['ny']}, {i['nx']}] field, got shape {tuple(src.shape)}")
         if isinstance(src, DeviceArray) and (src.dtype not in (np.float32, np.float64) or src.ld != src.shape[-1]):
             raise ValueError("src: expected a contiguous float32 or float64 DeviceArray")
-        return src, int(src.dtype == np.float32)
+        return src
 
 
 class RemapState(_State):
@@ -301,18 +304,13 @@ class RemapState(_State):
         [T, ny * nx] (rows ``ld`` apart) -> [T, Ny * Nx] float64 DeviceArray, cells fastest (``out``: a [T, C] DeviceArray, possibly a
         view of a wider or longer one).  float32 goes to the device as float32 and is widened in the kernel."""
         i = self.info()
-        field, f32, min_valid = self._args(field, i, min_valid)
+        field, min_valid = self._args(field, i, min_valid)
         T = field.shape[0]
-        mine = None
-        if not isinstance(field, DeviceArray):
-            field = mine = self.ctx.to_device(field, field.dtype)
-        try:
+        with self.ctx._uploads() as up:
+            field = up(field)
             out = self.ctx._result_buffer(out, (T, i["Ny"] * i["Nx"]), True)
             self.ctx._same_context("sd_remap", field=field, out=out)
-            check(self.ctx.lib.sd_remap_apply_dev(self.ctx.handle, self.vptr, field.vptr, f32, field.ld, T, min_valid, out.vptr, out.ld))
-        finally:
-            if mine is not None:
-                mine.free()
+            check(self.ctx.lib.sd_remap_apply_dev(self.ctx.handle, self.vptr, field.vptr, _f32(field), field.ld, T, min_valid, out.vptr, out.ld))
         return out
 
     def apply_host(self, field, min_valid=0.5):
@@ -320,9 +318,9 @@ class RemapState(_State):
         i = self.info()
         if isinstance(field, DeviceArray):
             raise ValueError("apply_host: expected a host array")
-        field, f32, min_valid = self._args(field, i, min_valid)
+        field, min_valid = self._args(field, i, min_valid)
         out = np.empty((field.shape[0], i["Ny"] * i["Nx"]))
-        check(self.ctx.lib.sd_remap_apply(self.ctx.handle, self.vptr, ptr(field), f32, field.shape[0], min_valid, ptr(out)))
+        check(self.ctx.lib.sd_remap_apply(self.ctx.handle, self.vptr, ptr(field), _f32(field), field.shape[0], min_valid, ptr(out)))
         return out
 
     @staticmethod
@@ -338,7 +336,7 @@ class RemapState(_State):
         min_valid = float(min_valid)
         if not 0.0 <= min_valid <= 1.0:
             raise ValueError(f"min_valid={min_valid!r}: expected a share of the covered area in [0, 1]")
-        return field, int(field.dtype == np.float32), min_valid
+        return field, min_valid
 
 
 class Context:
@@ -988,7 +986,8 @@ class Context:
         finally:
             state.close()
 
-    # ---- what the wrappers of the time-axis kernels share ----
+    # ---- the argument layer of the time-axis and analog-library wrappers, on top of the one above (_field, _result_buffer,
+    # _same_context) ----
     @staticmethod
     def _time_field(field, name="field", rows="T"):
         """a [T, C] field as the time-axis kernels take it: a DeviceArray, or a host array as float32 / float64"""
@@ -998,16 +997,72 @@ class Context:
             raise ValueError(f"{name}: expected a float32 or float64 [{rows}, C] field, got shape {tuple(field.shape)} of {field.dtype}")
         return field
 
+    @staticmethod
+    def _pair(a, b):
+        """the two fields of a paired call, checked alike"""
+        a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
+        return a, b
+
+    @staticmethod
+    def _stat_codes(who, stats, table, noun):
+        """one name or a list of names of ``table`` -> their codes [nstat] as the ABI reads them"""
+        stats = [stats] if isinstance(stats, str) else list(stats)
+        for s in stats:
+            if s not in table:
+                raise ValueError(f"{noun} {s!r}: expected one of {', '.join(repr(k) for k in table)}")
+        if not 1 <= len(stats) <= len(table):
+            raise ValueError(f"sd_downscale: {who}: nstat = {len(stats)}, expected 1 to {len(table)} statistics")
+        return np.ascontiguousarray([table[s] for s in stats], dtype=np.intc)
+
+    @staticmethod
+    def _sizes(who, **sizes):
+        """a size below 1 leaves nothing to allocate a result for: refused here, in the words of the plan's refusal"""
+        if min(sizes.values()) < 1:
+            raise ValueError(f"sd_downscale: {who}: bad sizes ({', '.join(f'{name}={n}' for name, n in sizes.items())})")
+
+    @staticmethod
+    def _offsets(offsets):
+        """the bin table [M + 1] -> (offsets as host int64, M)"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
+        return offsets, len(offsets) - 1
+
+    @staticmethod
+    def _bins(who, offsets, T, Cc):
+        """the bin table [M + 1] of a [T, C] field that gives a result per bin -> (offsets, M)"""
+        offsets, M = Context._offsets(offsets)
+        Context._sizes(who, T=T, C=Cc, M=M)
+        return offsets, M
+
+    @staticmethod
+    def _row_groups(group, T):
+        """one group id per row of a [T, C] field, as host int32"""
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        if group.shape != (T,):
+            raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+        return group
+
+    @staticmethod
+    def _groups(who, group, G, T, Cc):
+        """the group ids [T] and G of a [T, C] field that gives a result per group -> (group, G)"""
+        group = Context._row_groups(group, T)
+        Context._sizes(who, T=T, C=Cc)
+        Context._sizes(who, G=int(G))
+        return group, int(G)
+
     @contextlib.contextmanager
     def _uploads(self):
-        """``up(a, dtype)``: ``a`` on the device -- a DeviceArray (or None) as it is, a host array uploaded for the length of the
+        """``up(a)``: ``a`` on the device -- a DeviceArray (or None) as it is, a host array uploaded as it is for the length of the
         ``with`` block and freed when it ends"""
         mine = []
 
-        def up(a, dtype=np.float64):
+        def up(a):
             if a is None or isinstance(a, DeviceArray):
                 return a
-            mine.append(self.to_device(a, dtype))
+            mine.append(self.to_device(a, a.dtype))
             return mine[-1]
 
         try:
@@ -1015,6 +1070,18 @@ class Context:
         finally:
             for a in mine:
                 a.free()
+
+    @contextlib.contextmanager
+    def _fresh(self, *kinds):
+        """fresh DeviceArrays, one per (shape, dtype), for the results of the call made in the ``with`` block: freed if it raises, the
+        caller's otherwise"""
+        made = [self.empty(shape, dtype) for shape, dtype in kinds]
+        try:
+            yield made
+        except BaseException:
+            for a in made:
+                a.free()
+            raise
 
     def _stat_planes(self, out, nstat, M, Cc, plane_rows):
         """the output of a call that gives nstat statistics of M bins -> (out, elements between two statistics): the [nstat * M, C]
@@ -1031,63 +1098,75 @@ class Context:
             stride = int(plane_rows) * out.ld
         return out, stride
 
+    def _on_host(self, name, fn, shape, *args, fields="a host array"):
+        """the tail of the ``_host`` twin ``name``: none of ``args`` may be resident; ``fn(ctx, *args, out)``, every host array as its
+        pointer, fills a fresh host result of ``shape`` (upload, run, download in one call of the library)"""
+        if any(isinstance(a, DeviceArray) for a in args):
+            raise ValueError(f"{name}_host: expected {fields}")
+        out = np.empty(shape)
+        check(fn(self.handle, *[ptr(a) if isinstance(a, np.ndarray) else a for a in args], ptr(out)))
+        return out
+
+    def _paired(self, who, a, b, bins, out, plane_rows):
+        """the resident form of the paired call ``who``.  ``bins``: what its ABI takes between C and the result -- the table of the bins
+        (offsets [M + 1] or group ids [T]), their number, the codes of the statistics and, after nstat, what the family adds"""
+        table, n, codes, *more = bins
+        T, Cc = a.shape
+        out, stride = self._stat_planes(out, len(codes), n, Cc, plane_rows)
+        with self._uploads() as up:
+            same = b is a
+            a = up(a)
+            b = a if same else up(b)
+            self._same_context(who, a=a, b=b, out=out)
+            check(getattr(self.lib, who + "_dev")(self.handle, a.vptr, _f32(a), a.ld, b.vptr, _f32(b), b.ld, T, Cc, ptr(table), n, ptr(codes),
+                                                  len(codes), *more, out.vptr, out.ld, stride))
+        return out
+
+    def _paired_host(self, who, a, b, bins):
+        """the host form of the paired call ``who``; ``bins`` as for ``_paired``"""
+        table, n, codes, *more = bins
+        T, Cc = a.shape
+        return self._on_host(who[len("sd_"):], getattr(self.lib, who), (len(codes) * n, Cc), a, _f32(a), b, _f32(b), T, Cc, table, n, codes,
+                             len(codes), *more, fields="host arrays")
+
     # ---- resampling of the time axis (GridArray.resample) ----
     @staticmethod
     def _resample_args(field, offsets, op):
         if op not in _lib.RESAMPLE_OPS:
             raise NotImplementedError(f"resample reduction {op!r}: only 'mean' and 'sum' are implemented")
         field = Context._time_field(field)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
-        return field, offsets, _lib.RESAMPLE_OPS[op], int(field.dtype == np.float32)
+        return (field, *Context._offsets(offsets), _lib.RESAMPLE_OPS[op])
 
     def resample(self, field, offsets, op="mean", out=None):
         """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart);
         offsets: host int64 [M + 1], bin m = rows offsets[m] .. offsets[m + 1] - 1 -> [M, C] float64 DeviceArray (``out``: a [M, C]
         DeviceArray, possibly a view of a wider or longer one).  op 'mean' | 'sum', NaN samples skipped (sd_resample_dev)."""
-        field, offsets, code, f32 = self._resample_args(field, offsets, op)
+        field, offsets, M, code = self._resample_args(field, offsets, op)
         T, Cc = field.shape
-        M = len(offsets) - 1
-        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_resample: bad sizes (T={T}, C={Cc}, M={M})")
+        self._sizes("sd_resample", T=T, C=Cc, M=M)
         out = self._result_buffer(out, (M, Cc), True)
         with self._uploads() as up:
-            field = up(field, field.dtype)
+            field = up(field)
             self._same_context("sd_resample", field=field, out=out)
-            check(self.lib.sd_resample_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(offsets), M, out.vptr, out.ld))
+            check(self.lib.sd_resample_dev(self.handle, code, field.vptr, _f32(field), field.ld, T, Cc, ptr(offsets), M, out.vptr, out.ld))
         return out
 
     def resample_host(self, field, offsets, op="mean"):
         """host [T, C] -> host [M, C] through sd_resample (upload, run, download in one call)"""
-        field, offsets, code, f32 = self._resample_args(field, offsets, op)
-        if isinstance(field, DeviceArray):
-            raise ValueError("resample_host: expected a host array")
+        field, offsets, M, code = self._resample_args(field, offsets, op)
         T, Cc = field.shape
-        M = len(offsets) - 1
-        out = np.empty((max(M, 0), Cc))
-        check(self.lib.sd_resample(self.handle, code, ptr(field), f32, T, Cc, ptr(offsets), M, ptr(out)))
-        return out
+        return self._on_host("resample", self.lib.sd_resample, (M, Cc), code, field, _f32(field), T, Cc, offsets, M)
 
     # ---- threshold and spell indices per bin of the time axis (GridArray.where) ----
     @staticmethod
     def _spells_args(field, op, threshold, offsets, stats, min_length, group):
+        """-> the field and, in the order of the ABI, what follows its sizes"""
         if op not in _lib.SPELL_OPS:
             raise ValueError(f"where op {op!r}: expected one of {', '.join(repr(k) for k in _lib.SPELL_OPS)}")
-        stats = [stats] if isinstance(stats, str) else list(stats)
-        for s in stats:
-            if s not in _lib.SPELL_STATS:
-                raise ValueError(f"spell statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SPELL_STATS)}")
-        if not 1 <= len(stats) <= len(_lib.SPELL_STATS):
-            raise ValueError(f"sd_downscale: sd_spells: nstat = {len(stats)}, expected 1 to {len(_lib.SPELL_STATS)} statistics")
+        codes = Context._stat_codes("sd_spells", stats, _lib.SPELL_STATS, "spell statistic")
         field = Context._time_field(field)
         T, Cc = field.shape
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
-        M = len(offsets) - 1
-        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_spells: bad sizes (T={T}, C={Cc}, M={M})")
+        offsets, M = Context._bins("sd_spells", offsets, T, Cc)
         table = None
         if isinstance(threshold, DeviceArray) or np.ndim(threshold) > 0:
             table = threshold if isinstance(threshold, DeviceArray) else np.ascontiguousarray(threshold, dtype=np.float64)
@@ -1095,13 +1174,11 @@ class Context:
                 raise ValueError(f"threshold: expected a number or a float64 [G, {Cc}] table, got shape {tuple(table.shape)} of {table.dtype}")
             threshold = 0.0
             if group is not None:
-                group = np.ascontiguousarray(group, dtype=np.int32)
-                if group.shape != (T,):
-                    raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+                group = Context._row_groups(group, T)
         elif group is not None:
             raise ValueError("group: a scalar threshold takes no group ids")
-        codes = np.ascontiguousarray([_lib.SPELL_STATS[s] for s in stats], dtype=np.intc)
-        return field, _lib.SPELL_OPS[op], float(threshold), table, group, offsets, codes, int(min_length), int(field.dtype == np.float32)
+        G = 1 if table is None else table.shape[0]
+        return field, _lib.SPELL_OPS[op], float(threshold), table, group, G, offsets, M, int(min_length), codes
 
     def spells(self, field, op, threshold, offsets, stats, min_length=1, group=None, out=None, plane_rows=None):
         """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); op
@@ -1112,74 +1189,30 @@ class Context:
         pass over the field (sd_spells_dev; the rule is in include/sd_downscale.h).  ``out``: that DeviceArray, possibly a view of a
         wider one.  With ``plane_rows`` ``out`` is instead the [M, C] view of this call's bins inside the first of nstat planes of
         ``plane_rows`` rows each of a longer DeviceArray (how a caller fills the bins block by block)."""
-        field, code, thr, table, group, offsets, codes, L, f32 = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
+        field, code, thr, table, group, G, offsets, M, L, codes = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
         T, Cc = field.shape
-        M, nstat = len(offsets) - 1, len(codes)
-        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
+        out, stride = self._stat_planes(out, len(codes), M, Cc, plane_rows)
         with self._uploads() as up:
-            field, table = up(field, field.dtype), up(table)
+            field, table = up(field), up(table)
             self._same_context("sd_spells", field=field, threshold=table, out=out)
-            check(self.lib.sd_spells_dev(self.handle, field.vptr, f32, field.ld, T, Cc, code, thr, None if table is None else table.vptr,
-                                         0 if table is None else table.ld, None if group is None else ptr(group),
-                                         1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), nstat, out.vptr, out.ld, stride))
+            check(self.lib.sd_spells_dev(self.handle, field.vptr, _f32(field), field.ld, T, Cc, code, thr, vptr(table),
+                                         0 if table is None else table.ld, ptr(group), G, ptr(offsets), M, L, ptr(codes), len(codes), out.vptr,
+                                         out.ld, stride))
         return out
 
     def spells_host(self, field, op, threshold, offsets, stats, min_length=1, group=None):
         """host [T, C] -> host [nstat * M, C] through sd_spells (upload, run, download in one call)"""
-        field, code, thr, table, group, offsets, codes, L, f32 = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
-        if isinstance(field, DeviceArray) or isinstance(table, DeviceArray):
-            raise ValueError("spells_host: expected host arrays")
+        field, code, thr, table, group, G, offsets, M, L, codes = self._spells_args(field, op, threshold, offsets, stats, min_length, group)
         T, Cc = field.shape
-        M = len(offsets) - 1
-        out = np.empty((len(codes) * M, Cc))
-        check(self.lib.sd_spells(self.handle, ptr(field), f32, T, Cc, code, thr, ptr(table), None if group is None else ptr(group),
-                                 1 if table is None else table.shape[0], ptr(offsets), M, L, ptr(codes), len(codes), ptr(out)))
-        return out
+        return self._on_host("spells", self.lib.sd_spells, (len(codes) * M, Cc), field, _f32(field), T, Cc, code, thr, table, group, G, offsets, M,
+                             L, codes, len(codes), fields="host arrays")
 
     # ---- paired skill statistics per bin of the time axis (GridArray.compare) ----
     @staticmethod
     def _skill_fields(who, a, b, stats):
         """the statistics and the two fields of a paired call -> (a, b, codes)"""
-        stats = [stats] if isinstance(stats, str) else list(stats)
-        for s in stats:
-            if s not in _lib.SKILL_STATS:
-                raise ValueError(f"skill statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.SKILL_STATS)}")
-        if not 1 <= len(stats) <= len(_lib.SKILL_STATS):
-            raise ValueError(f"sd_downscale: {who}: nstat = {len(stats)}, expected 1 to {len(_lib.SKILL_STATS)} statistics")
-        a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
-        if tuple(a.shape) != tuple(b.shape):
-            raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
-        return a, b, np.ascontiguousarray([_lib.SKILL_STATS[s] for s in stats], dtype=np.intc)
-
-    @staticmethod
-    def _bins_of_pair(who, a, offsets):
-        """offsets [M + 1] of a paired call on fields like ``a``"""
-        T, Cc = a.shape
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offsets.ndim != 1 or len(offsets) < 1:
-            raise ValueError(f"offsets: expected a table of M + 1 entries, got shape {offsets.shape}")
-        M = len(offsets) - 1
-        if min(T, Cc, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: {who}: bad sizes (T={T}, C={Cc}, M={M})")
-        return offsets
-
-    @staticmethod
-    def _groups_of_pair(who, a, group, G):
-        """group [T] and G of a grouped paired call on fields like ``a``: the checks of ``_groupby_args``"""
-        T, Cc = a.shape
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (T,):
-            raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
-        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
-            raise ValueError(f"sd_downscale: {who}: bad sizes (T={T}, C={Cc})")
-        if int(G) < 1:
-            raise ValueError(f"sd_downscale: {who}: bad sizes (G={int(G)})")
-        return group, int(G)
-
-    @staticmethod
-    def _skill_args(a, b, offsets, stats):
-        a, b, codes = Context._skill_fields("sd_skill", a, b, stats)
-        return a, b, Context._bins_of_pair("sd_skill", a, offsets), codes
+        codes = Context._stat_codes(who, stats, _lib.SKILL_STATS, "skill statistic")
+        return (*Context._pair(a, b), codes)
 
     def skill(self, a, b, offsets, stats, out=None, plane_rows=None):
         """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
@@ -1187,30 +1220,13 @@ class Context:
         one name or a list of 'count' | 'bias' | 'ratio' | 'mae' | 'rmse' | 'corr' | 'std_ratio' -> [nstat * M, C] float64 DeviceArray,
         row ``s * M + m`` the statistic s of bin m; both fields are read once, or twice where 'corr' or 'std_ratio' is among them
         (sd_skill_dev; the rule is in include/sd_downscale.h).  ``out`` and ``plane_rows``: as for ``spells``."""
-        a, b, offsets, codes = self._skill_args(a, b, offsets, stats)
-        T, Cc = a.shape
-        M, nstat = len(offsets) - 1, len(codes)
-        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
-        with self._uploads() as up:
-            same = b is a
-            a = up(a, a.dtype)
-            b = a if same else up(b, b.dtype)
-            self._same_context("sd_skill", a=a, b=b, out=out)
-            check(self.lib.sd_skill_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T, Cc,
-                                        ptr(offsets), M, ptr(codes), nstat, out.vptr, out.ld, stride))
-        return out
+        a, b, codes = self._skill_fields("sd_skill", a, b, stats)
+        return self._paired("sd_skill", a, b, (*self._bins("sd_skill", offsets, *a.shape), codes), out, plane_rows)
 
     def skill_host(self, a, b, offsets, stats):
         """host [T, C] twice -> host [nstat * M, C] through sd_skill (upload, run, download in one call)"""
-        a, b, offsets, codes = self._skill_args(a, b, offsets, stats)
-        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
-            raise ValueError("skill_host: expected host arrays")
-        T, Cc = a.shape
-        M = len(offsets) - 1
-        out = np.empty((len(codes) * M, Cc))
-        check(self.lib.sd_skill(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(offsets), M,
-                                ptr(codes), len(codes), ptr(out)))
-        return out
+        a, b, codes = self._skill_fields("sd_skill", a, b, stats)
+        return self._paired_host("sd_skill", a, b, (*self._bins("sd_skill", offsets, *a.shape), codes))
 
     def skill_groups(self, a, b, group, G, stats, out=None, plane_rows=None):
         """``skill`` over groups of steps in place of bins: group: host int32 [T], every id in [0, G) -> [nstat * G, C] float64
@@ -1219,42 +1235,20 @@ class Context:
         gives count 0 and NaN.  Both fields are whole on the device for the call (sd_skill_groups_dev).  ``out`` and ``plane_rows``:
         as for ``spells``."""
         a, b, codes = self._skill_fields("sd_skill_groups", a, b, stats)
-        group, G = self._groups_of_pair("sd_skill_groups", a, group, G)
-        T, Cc = a.shape
-        nstat = len(codes)
-        out, stride = self._stat_planes(out, nstat, G, Cc, plane_rows)
-        with self._uploads() as up:
-            same = b is a
-            a = up(a, a.dtype)
-            b = a if same else up(b, b.dtype)
-            self._same_context("sd_skill_groups", a=a, b=b, out=out)
-            check(self.lib.sd_skill_groups_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T,
-                                               Cc, ptr(group), G, ptr(codes), nstat, out.vptr, out.ld, stride))
-        return out
+        return self._paired("sd_skill_groups", a, b, (*self._groups("sd_skill_groups", group, G, *a.shape), codes), out, plane_rows)
 
     def skill_groups_host(self, a, b, group, G, stats):
         """host [T, C] twice -> host [nstat * G, C] through sd_skill_groups (upload, run, download in one call)"""
         a, b, codes = self._skill_fields("sd_skill_groups", a, b, stats)
-        group, G = self._groups_of_pair("sd_skill_groups", a, group, G)
-        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
-            raise ValueError("skill_groups_host: expected host arrays")
-        T, Cc = a.shape
-        out = np.empty((len(codes) * G, Cc))
-        check(self.lib.sd_skill_groups(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(group), G,
-                                       ptr(codes), len(codes), ptr(out)))
-        return out
+        return self._paired_host("sd_skill_groups", a, b, (*self._groups("sd_skill_groups", group, G, *a.shape), codes))
 
     # ---- distribution scores per bin of the time axis (GridArray.compare(...).ks() / .perkins()) ----
     @staticmethod
     def _twosample_fields(who, a, b, stats, width, origin):
-        """the statistics, the histogram and the two fields of a two-sample call -> (a, b, codes, width, origin)"""
-        stats = [stats] if isinstance(stats, str) else list(stats)
-        for s in stats:
-            if s not in _lib.TWOSAMPLE_STATS:
-                raise ValueError(f"distribution statistic {s!r}: expected one of {', '.join(repr(k) for k in _lib.TWOSAMPLE_STATS)}")
-        if not 1 <= len(stats) <= len(_lib.TWOSAMPLE_STATS):
-            raise ValueError(f"sd_downscale: {who}: nstat = {len(stats)}, expected 1 to {len(_lib.TWOSAMPLE_STATS)} statistics")
-        if "perkins" in stats:
+        """the statistics, the histogram and the two fields of a two-sample call -> (a, b, (codes, width, origin))"""
+        codes = Context._stat_codes(who, stats, _lib.TWOSAMPLE_STATS, "distribution statistic")
+        perkins = _lib.TWOSAMPLE_STATS["perkins"] in codes
+        if perkins:
             if width is None:
                 raise ValueError("perkins needs the width of the histogram bins (width=...)")
             number = (int, float, np.integer, np.floating)
@@ -1262,17 +1256,7 @@ class Context:
                 raise ValueError(f"width: expected a positive finite number, got {width!r}")
             if not (isinstance(origin, number) and not isinstance(origin, bool) and np.isfinite(origin)):
                 raise ValueError(f"origin: expected a finite number, got {origin!r}")
-        a, b = Context._time_field(a, "a"), Context._time_field(b, "b")
-        if tuple(a.shape) != tuple(b.shape):
-            raise ValueError(f"b: expected a [T, C] field of shape {tuple(a.shape)} like a, got shape {tuple(b.shape)}")
-        codes = np.ascontiguousarray([_lib.TWOSAMPLE_STATS[s] for s in stats], dtype=np.intc)
-        perkins = "perkins" in stats
-        return a, b, codes, float(width) if perkins else 0.0, float(origin) if perkins else 0.0
-
-    @staticmethod
-    def _twosample_args(a, b, offsets, stats, width, origin):
-        a, b, codes, width, origin = Context._twosample_fields("sd_twosample", a, b, stats, width, origin)
-        return a, b, Context._bins_of_pair("sd_twosample", a, offsets), codes, width, origin
+        return (*Context._pair(a, b), (codes, float(width) if perkins else 0.0, float(origin) if perkins else 0.0))
 
     def twosample(self, a, b, offsets, stats, width=None, origin=0.0, out=None, plane_rows=None):
         """a, b [T, C]: float32 / float64 host arrays (any other dtype is taken as float64) or DeviceArrays (rows ``ld`` apart; they
@@ -1282,30 +1266,13 @@ class Context:
         a bin: a NaN in ``a`` does not remove the sample of ``b`` at that step.  ``width`` (> 0) and ``origin``: the histogram bins
         floor((x - origin) / width) of 'perkins', read only where it is asked for.  A bin holds at most 19 456 rows
         (NotImplementedError beyond).  ``out`` and ``plane_rows``: as for ``spells``."""
-        a, b, offsets, codes, width, origin = self._twosample_args(a, b, offsets, stats, width, origin)
-        T, Cc = a.shape
-        M, nstat = len(offsets) - 1, len(codes)
-        out, stride = self._stat_planes(out, nstat, M, Cc, plane_rows)
-        with self._uploads() as up:
-            same = b is a
-            a = up(a, a.dtype)
-            b = a if same else up(b, b.dtype)
-            self._same_context("sd_twosample", a=a, b=b, out=out)
-            check(self.lib.sd_twosample_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld, T,
-                                            Cc, ptr(offsets), M, ptr(codes), nstat, width, origin, out.vptr, out.ld, stride))
-        return out
+        a, b, scores = self._twosample_fields("sd_twosample", a, b, stats, width, origin)
+        return self._paired("sd_twosample", a, b, (*self._bins("sd_twosample", offsets, *a.shape), *scores), out, plane_rows)
 
     def twosample_host(self, a, b, offsets, stats, width=None, origin=0.0):
         """host [T, C] twice -> host [nstat * M, C] through sd_twosample (upload, run, download in one call)"""
-        a, b, offsets, codes, width, origin = self._twosample_args(a, b, offsets, stats, width, origin)
-        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
-            raise ValueError("twosample_host: expected host arrays")
-        T, Cc = a.shape
-        M = len(offsets) - 1
-        out = np.empty((len(codes) * M, Cc))
-        check(self.lib.sd_twosample(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(offsets), M,
-                                    ptr(codes), len(codes), width, origin, ptr(out)))
-        return out
+        a, b, scores = self._twosample_fields("sd_twosample", a, b, stats, width, origin)
+        return self._paired_host("sd_twosample", a, b, (*self._bins("sd_twosample", offsets, *a.shape), *scores))
 
     def twosample_groups(self, a, b, group, G, stats, width=None, origin=0.0, out=None, plane_rows=None):
         """``twosample`` over groups of steps in place of bins: group: host int32 [T], every id in [0, G) -> [nstat * G, C] float64
@@ -1313,31 +1280,13 @@ class Context:
         rows with ``group == g``: the bits of ``twosample`` on the fields gathered group by group.  An id that never occurs gives na =
         nb = 0 and NaN.  A group holds at most 19 456 rows (NotImplementedError beyond); both fields are whole on the device for the
         call (sd_twosample_groups_dev).  ``out`` and ``plane_rows``: as for ``spells``."""
-        a, b, codes, width, origin = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
-        group, G = self._groups_of_pair("sd_twosample_groups", a, group, G)
-        T, Cc = a.shape
-        nstat = len(codes)
-        out, stride = self._stat_planes(out, nstat, G, Cc, plane_rows)
-        with self._uploads() as up:
-            same = b is a
-            a = up(a, a.dtype)
-            b = a if same else up(b, b.dtype)
-            self._same_context("sd_twosample_groups", a=a, b=b, out=out)
-            check(self.lib.sd_twosample_groups_dev(self.handle, a.vptr, int(a.dtype == np.float32), a.ld, b.vptr, int(b.dtype == np.float32), b.ld,
-                                                   T, Cc, ptr(group), G, ptr(codes), nstat, width, origin, out.vptr, out.ld, stride))
-        return out
+        a, b, scores = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
+        return self._paired("sd_twosample_groups", a, b, (*self._groups("sd_twosample_groups", group, G, *a.shape), *scores), out, plane_rows)
 
     def twosample_groups_host(self, a, b, group, G, stats, width=None, origin=0.0):
         """host [T, C] twice -> host [nstat * G, C] through sd_twosample_groups (upload, run, download in one call)"""
-        a, b, codes, width, origin = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
-        group, G = self._groups_of_pair("sd_twosample_groups", a, group, G)
-        if isinstance(a, DeviceArray) or isinstance(b, DeviceArray):
-            raise ValueError("twosample_groups_host: expected host arrays")
-        T, Cc = a.shape
-        out = np.empty((len(codes) * G, Cc))
-        check(self.lib.sd_twosample_groups(self.handle, ptr(a), int(a.dtype == np.float32), ptr(b), int(b.dtype == np.float32), T, Cc, ptr(group), G,
-                                           ptr(codes), len(codes), width, origin, ptr(out)))
-        return out
+        a, b, scores = self._twosample_fields("sd_twosample_groups", a, b, stats, width, origin)
+        return self._paired_host("sd_twosample_groups", a, b, (*self._groups("sd_twosample_groups", group, G, *a.shape), *scores))
 
     # ---- temporal disaggregation (GridArray.disaggregate) ----
     @staticmethod
@@ -1354,51 +1303,46 @@ class Context:
             if len(a.shape) != 2 or a.dtype != np.float64 or a.shape[1] != obs.shape[1]:
                 raise ValueError(f"{name}: expected a float64 [{'M' if name == 'target' else 'G'}, {obs.shape[1]}] field, got shape "
                                  f"{tuple(a.shape)} of {a.dtype}")
+        target, climo = fields["target"], fields["climo"]
         src_row = np.ascontiguousarray(src_row, dtype=np.int64)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if src_row.ndim != 1:
             raise ValueError(f"src_row: expected a table of Tout entries, got shape {src_row.shape}")
-        if offsets.ndim != 1 or len(offsets) != fields["target"].shape[0] + 1:
-            raise ValueError(f"offsets: expected a table of M + 1 = {fields['target'].shape[0] + 1} entries, got shape {offsets.shape}")
+        M = target.shape[0]
+        if offsets.ndim != 1 or len(offsets) != M + 1:
+            raise ValueError(f"offsets: expected a table of M + 1 = {M + 1} entries, got shape {offsets.shape}")
         if (climo is None) != (group is None):
             raise ValueError(f"sd_downscale: sd_disagg: {'group without climo' if climo is None else 'climo without group'}")
         if group is not None:
             group = np.ascontiguousarray(group, dtype=np.int32)
-            if group.shape != (fields["target"].shape[0],):
-                raise ValueError(f"group: expected one climatology row per bin ({fields['target'].shape[0]}), got shape {group.shape}")
-        return fields["target"], obs, src_row, offsets, _lib.DISAGG_OPS[op], int(obs.dtype == np.float32), fields["climo"], group
+            if group.shape != (M,):
+                raise ValueError(f"group: expected one climatology row per bin ({M}), got shape {group.shape}")
+        return target, obs, src_row, offsets, _lib.DISAGG_OPS[op], climo, 0 if climo is None else climo.shape[0], group
 
     def disaggregate(self, target, obs, src_row, offsets, op="shift", climo=None, group=None, out=None):
         """target [M, C] float64 and obs [To, C] float32 / float64: host arrays or DeviceArrays (rows ``ld`` apart); src_row: host int64
         [Tout], the row of obs every output row borrows; offsets: host int64 [M + 1], bin m = output rows offsets[m] .. offsets[m + 1]
         - 1; climo [G, C] float64 with group: host int32 [M] when the target is an anomaly -> [Tout, C] float64 DeviceArray (``out``:
         a [Tout, C] DeviceArray, possibly a view of a wider or longer one).  op 'shift' | 'scale_mean' | 'scale_sum' (sd_disagg_dev)."""
-        target, obs, src_row, offsets, code, f32, climo, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
+        target, obs, src_row, offsets, code, climo, G, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
         To, Cc = obs.shape
         M, Tout = target.shape[0], len(src_row)
-        if min(To, Cc, Tout, M) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_disagg: bad sizes (To={To}, C={Cc}, Tout={Tout}, M={M})")
+        self._sizes("sd_disagg", To=To, C=Cc, Tout=Tout, M=M)
         out = self._result_buffer(out, (Tout, Cc), True)
         with self._uploads() as up:
-            target, obs, climo = up(target), up(obs, obs.dtype), up(climo)
+            target, obs, climo = up(target), up(obs), up(climo)
             self._same_context("sd_disagg", target=target, obs=obs, climo=climo, out=out)
-            check(self.lib.sd_disagg_dev(self.handle, code, target.vptr, target.ld, obs.vptr, f32, obs.ld, To, Cc, ptr(src_row), Tout, ptr(offsets),
-                                         M, None if climo is None else climo.vptr, 0 if climo is None else climo.ld,
-                                         0 if climo is None else climo.shape[0], None if group is None else ptr(group), out.vptr, out.ld))
+            check(self.lib.sd_disagg_dev(self.handle, code, target.vptr, target.ld, obs.vptr, _f32(obs), obs.ld, To, Cc, ptr(src_row), Tout,
+                                         ptr(offsets), M, vptr(climo), 0 if climo is None else climo.ld, G, ptr(group), out.vptr, out.ld))
         return out
 
     def disaggregate_host(self, target, obs, src_row, offsets, op="shift", climo=None, group=None):
         """host target [M, C], obs [To, C] -> host [Tout, C] through sd_disagg (upload, run, download in one call)"""
-        target, obs, src_row, offsets, code, f32, climo, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
-        if any(isinstance(a, DeviceArray) for a in (target, obs, climo)):
-            raise ValueError("disaggregate_host: expected host arrays")
+        target, obs, src_row, offsets, code, climo, G, group = self._disagg_args(target, obs, src_row, offsets, op, climo, group)
         To, Cc = obs.shape
         M, Tout = target.shape[0], len(src_row)
-        out = np.empty((Tout, Cc))
-        check(self.lib.sd_disagg(self.handle, code, ptr(target), ptr(obs), f32, To, Cc, ptr(src_row), Tout, ptr(offsets), M,
-                                 None if climo is None else ptr(climo), 0 if climo is None else climo.shape[0],
-                                 None if group is None else ptr(group), ptr(out)))
-        return out
+        return self._on_host("disaggregate", self.lib.sd_disagg, (Tout, Cc), code, target, obs, _f32(obs), To, Cc, src_row, Tout, offsets, M, climo,
+                             G, group, fields="host arrays")
 
     # ---- grouping of the time axis (GridArray.groupby) ----
     @staticmethod
@@ -1406,15 +1350,7 @@ class Context:
         if op not in ops:
             raise NotImplementedError(f"{who} op {op!r}: only {', '.join(repr(k) for k in ops)} are implemented")
         field = Context._time_field(field)
-        group = np.ascontiguousarray(group, dtype=np.int32)
-        if group.shape != (field.shape[0],):
-            raise ValueError(f"group: expected one group id per row ({field.shape[0]}), got shape {group.shape}")
-        T, Cc = field.shape
-        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
-            raise ValueError(f"sd_downscale: sd_{who}: bad sizes (T={T}, C={Cc})")
-        if int(G) < 1:
-            raise ValueError(f"sd_downscale: sd_{who}: bad sizes (G={int(G)})")
-        return field, group, int(G), ops[op], int(field.dtype == np.float32)
+        return (field, *Context._groups("sd_" + who, group, G, *field.shape), ops[op])
 
     def groupby_reduce(self, field, group, G, op="mean", acc=None, out=None, finish=True):
         """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); group:
@@ -1423,7 +1359,7 @@ class Context:
         continues, or None for new ones that start from zero.  -> ``(result, acc)``: with ``finish`` the [G, C] float64 DeviceArray
         of op 'mean' | 'sum' over everything added so far (``out``: a [G, C] DeviceArray, possibly a view of a wider or longer one),
         else None; NaN samples skipped (sd_groupby_reduce_dev).  Any cut of the rows into calls gives the bits of one call."""
-        field, group, G, code, f32 = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
+        field, group, G, code = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
         T, Cc = field.shape
         carry = acc is not None
         if carry:
@@ -1434,21 +1370,17 @@ class Context:
             s, n = self.empty((G, Cc)), self.empty((G, Cc), np.int32)
         out = self._result_buffer(out, (G, Cc), True) if finish else None
         with self._uploads() as up:
-            field = up(field, field.dtype)
+            field = up(field)
             self._same_context("sd_groupby_reduce", field=field, sum=s, count=n, out=out)
-            check(self.lib.sd_groupby_reduce_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, s.vptr, n.vptr, s.ld,
-                                                 int(carry), None if out is None else out.vptr, 0 if out is None else out.ld))
+            check(self.lib.sd_groupby_reduce_dev(self.handle, code, field.vptr, _f32(field), field.ld, T, Cc, ptr(group), G, s.vptr, n.vptr, s.ld,
+                                                 int(carry), vptr(out), 0 if out is None else out.ld))
         return out, (s, n)
 
     def groupby_reduce_host(self, field, group, G, op="mean"):
         """host [T, C] -> host [G, C] through sd_groupby_reduce (upload, run, download in one call)"""
-        field, group, G, code, f32 = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
-        if isinstance(field, DeviceArray):
-            raise ValueError("groupby_reduce_host: expected a host array")
+        field, group, G, code = self._groupby_args("groupby_reduce", field, group, G, op, _lib.GROUPBY_REDUCE_OPS)
         T, Cc = field.shape
-        out = np.empty((G, Cc))
-        check(self.lib.sd_groupby_reduce(self.handle, code, ptr(field), f32, T, Cc, ptr(group), G, ptr(out)))
-        return out
+        return self._on_host("groupby_reduce", self.lib.sd_groupby_reduce, (G, Cc), code, field, _f32(field), T, Cc, group, G)
 
     def groupby_apply(self, field, group, table, op, out=None):
         """field [T, C] as for ``groupby_reduce``; table [G, C] float64: a host array or DeviceArray; group: host int32 [T] in [0, G)
@@ -1458,27 +1390,26 @@ class Context:
             table = np.ascontiguousarray(table, dtype=np.float64)
         if len(table.shape) != 2 or table.dtype != np.float64:
             raise ValueError(f"table: expected a float64 [G, C] field, got shape {tuple(table.shape)} of {table.dtype}")
-        field, group, G, code, f32 = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
+        field, group, G, code = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
         if table.shape[1] != field.shape[1]:
             raise ValueError(f"table: expected a float64 [G, {field.shape[1]}] field, got shape {tuple(table.shape)}")
         T, Cc = field.shape
         out = self._result_buffer(out, (T, Cc), True)
         with self._uploads() as up:
-            field, table = up(field, field.dtype), up(table)
+            field, table = up(field), up(table)
             self._same_context("sd_groupby_apply", field=field, table=table, out=out)
-            check(self.lib.sd_groupby_apply_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, ptr(group), G, table.vptr, table.ld, out.vptr,
-                                                out.ld))
+            check(self.lib.sd_groupby_apply_dev(self.handle, code, field.vptr, _f32(field), field.ld, T, Cc, ptr(group), G, table.vptr, table.ld,
+                                                out.vptr, out.ld))
         return out
 
     def groupby_apply_host(self, field, group, table, op):
         """host field [T, C], table [G, C] -> host [T, C] through sd_groupby_apply (upload, run, download in one call)"""
         table = np.ascontiguousarray(table, dtype=np.float64)
-        field, group, G, code, f32 = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
+        field, group, G, code = self._groupby_args("groupby_apply", field, group, table.shape[0], op, _lib.GROUPBY_APPLY_OPS)
         if isinstance(field, DeviceArray) or table.ndim != 2 or table.shape[1] != field.shape[1]:
             raise ValueError("groupby_apply_host: expected a host [T, C] field and a host [G, C] table")
-        out = np.empty(field.shape)
-        check(self.lib.sd_groupby_apply(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], ptr(group), G, ptr(table), ptr(out)))
-        return out
+        T, Cc = field.shape
+        return self._on_host("groupby_apply", self.lib.sd_groupby_apply, (T, Cc), code, field, _f32(field), T, Cc, group, G, table)
 
     # ---- order statistics over the time axis (GridArray.quantile / .median) ----
     @staticmethod
@@ -1487,19 +1418,16 @@ class Context:
             raise ValueError(f"quantile method {method!r}: expected one of {', '.join(repr(k) for k in _lib.QUANTILE_METHODS)}")
         field = Context._time_field(field)
         T, Cc = field.shape
-        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusals)
-            raise ValueError(f"sd_downscale: sd_quantile: bad sizes (T={T}, C={Cc})")
+        Context._sizes("sd_quantile", T=T, C=Cc)
         if group is None:
             G = 1
         else:
-            group = np.ascontiguousarray(group, dtype=np.int32)
-            if group.shape != (T,):
-                raise ValueError(f"group: expected one group id per row ({T}), got shape {group.shape}")
+            group = Context._row_groups(group, T)
             G = int(group.max()) + 1 if G is None else int(G)
         q = np.ascontiguousarray([0.5] if method == "median" else np.atleast_1d(q), dtype=np.float64)
         if q.ndim != 1 or G < 1 or len(q) < 1:
             raise ValueError(f"sd_downscale: sd_quantile: bad sizes (G={G}, Q={q.size if q.ndim == 1 else q.shape})")
-        return field, q, group, G, _lib.QUANTILE_METHODS[method], int(field.dtype == np.float32)
+        return field, q, group, G, _lib.QUANTILE_METHODS[method]
 
     def quantile(self, field, q, group=None, G=None, method="linear", skipna=True, out=None):
         """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart); q: one
@@ -1508,26 +1436,22 @@ class Context:
         (``skipna=False``: np.quantile, NaN where the group holds one); method 'linear' | 'lower' | 'higher' | 'nearest' | 'midpoint',
         or 'median' (np.nanmedian; q is not read, Q = 1).  ``out``: a [Q * G, C] DeviceArray, possibly a view of a wider or longer
         one.  Groups of more than 19 456 rows are refused (sd_quantile_dev)."""
-        field, q, group, G, code, f32 = self._quantile_args(field, q, group, G, method)
+        field, q, group, G, code = self._quantile_args(field, q, group, G, method)
         T, Cc = field.shape
         out = self._result_buffer(out, (len(q) * G, Cc), True)
         with self._uploads() as up:
-            field = up(field, field.dtype)
+            field = up(field)
             self._same_context("sd_quantile", field=field, out=out)
-            check(self.lib.sd_quantile_dev(self.handle, code, int(bool(skipna)), field.vptr, f32, field.ld, T, Cc, None if group is None else ptr(group),
-                                           G, ptr(q), len(q), out.vptr, out.ld))
+            check(self.lib.sd_quantile_dev(self.handle, code, int(bool(skipna)), field.vptr, _f32(field), field.ld, T, Cc, ptr(group), G, ptr(q),
+                                           len(q), out.vptr, out.ld))
         return out
 
     def quantile_host(self, field, q, group=None, G=None, method="linear", skipna=True):
         """host [T, C] -> host [Q * G, C] through sd_quantile (upload, run, download in one call)"""
-        field, q, group, G, code, f32 = self._quantile_args(field, q, group, G, method)
-        if isinstance(field, DeviceArray):
-            raise ValueError("quantile_host: expected a host array")
+        field, q, group, G, code = self._quantile_args(field, q, group, G, method)
         T, Cc = field.shape
-        out = np.empty((len(q) * G, Cc))
-        check(self.lib.sd_quantile(self.handle, code, int(bool(skipna)), ptr(field), f32, T, Cc, None if group is None else ptr(group), G, ptr(q),
-                                   len(q), ptr(out)))
-        return out
+        return self._on_host("quantile", self.lib.sd_quantile, (len(q) * G, Cc), code, int(bool(skipna)), field, _f32(field), T, Cc, group, G, q,
+                             len(q))
 
     # ---- rolling windows over the time axis (GridArray.rolling) ----
     @staticmethod
@@ -1536,12 +1460,11 @@ class Context:
             raise NotImplementedError(f"rolling op {op!r}: only {', '.join(repr(k) for k in _lib.ROLLING_OPS)} are implemented")
         field = Context._time_field(field)
         T, Cc = field.shape
-        if min(T, Cc) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: sd_rolling: bad sizes (T={T}, C={Cc})")
+        Context._sizes("sd_rolling", T=T, C=Cc)
         window = int(window)
         back = window - 1 if back is None else int(back)
         min_periods = window if min_periods is None else int(min_periods)
-        return field, window, back, min_periods, int(ddof), _lib.ROLLING_OPS[op], int(field.dtype == np.float32)
+        return field, window, back, min_periods, int(ddof), _lib.ROLLING_OPS[op]
 
     def rolling(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False, t0=0, n_out=None, out=None):
         """field [T, C]: a float32 / float64 host array (any other dtype is taken as float64) or DeviceArray (rows ``ld`` apart) ->
@@ -1550,7 +1473,7 @@ class Context:
         defaults to ``window - 1``, pandas' trailing window; ``window // 2`` is ``center=True``), clipped to the field or, with
         ``wrap``, taken modulo T; NaN samples are skipped, fewer than ``min_periods`` (default ``window``) give NaN.  ``out``: a
         [n_out, C] DeviceArray, possibly a view of a wider or longer one.  O(window) work per output (sd_rolling_dev)."""
-        field, window, back, min_periods, ddof, code, f32 = self._rolling_args(field, window, op, back, min_periods, ddof)
+        field, window, back, min_periods, ddof, code = self._rolling_args(field, window, op, back, min_periods, ddof)
         T, Cc = field.shape
         t0 = int(t0)
         n_out = T - t0 if n_out is None else int(n_out)
@@ -1558,21 +1481,18 @@ class Context:
             raise ValueError(f"sd_downscale: sd_rolling: the output rows {t0} .. {t0 + n_out - 1} lie outside the {T} rows of the source")
         out = self._result_buffer(out, (n_out, Cc), True)
         with self._uploads() as up:
-            field = up(field, field.dtype)
+            field = up(field)
             self._same_context("sd_rolling", field=field, out=out)
-            check(self.lib.sd_rolling_dev(self.handle, code, field.vptr, f32, field.ld, T, Cc, window, back, min_periods, ddof, int(bool(wrap)), t0,
-                                          n_out, out.vptr, out.ld))
+            check(self.lib.sd_rolling_dev(self.handle, code, field.vptr, _f32(field), field.ld, T, Cc, window, back, min_periods, ddof,
+                                          int(bool(wrap)), t0, n_out, out.vptr, out.ld))
         return out
 
     def rolling_host(self, field, window, op="mean", back=None, min_periods=None, ddof=1, wrap=False):
         """host [T, C] -> host [T, C] through sd_rolling (upload, run, download in one call)"""
-        field, window, back, min_periods, ddof, code, f32 = self._rolling_args(field, window, op, back, min_periods, ddof)
-        if isinstance(field, DeviceArray):
-            raise ValueError("rolling_host: expected a host array")
-        out = np.empty(field.shape)
-        check(self.lib.sd_rolling(self.handle, code, ptr(field), f32, field.shape[0], field.shape[1], window, back, min_periods, ddof,
-                                  int(bool(wrap)), ptr(out)))
-        return out
+        field, window, back, min_periods, ddof, code = self._rolling_args(field, window, op, back, min_periods, ddof)
+        T, Cc = field.shape
+        return self._on_host("rolling", self.lib.sd_rolling, (T, Cc), code, field, _f32(field), T, Cc, window, back, min_periods, ddof,
+                             int(bool(wrap)))
 
     # ---- constructed analogs (ConstructedAnalogs) ----
     @staticmethod
@@ -1581,8 +1501,7 @@ class Context:
         L, Q = Context._field("L", L, "Tl", "Cc"), Context._field("Q", Q, "Tq", "Cc")
         if Q.shape[1] != L.shape[1]:
             raise ValueError(f"Q: expected a [Tq, {L.shape[1]}] field like L, got shape {tuple(Q.shape)}")
-        if min(L.shape + Q.shape) < 1:  # (nothing to allocate a result for; the words of the plan's refusal)
-            raise ValueError(f"sd_downscale: {who}: bad sizes (Tl={L.shape[0]}, Tq={Q.shape[0]}, Cc={L.shape[1]})")
+        Context._sizes(who, Tl=L.shape[0], Tq=Q.shape[0], Cc=L.shape[1])
         wc = _lib.as_f64(wc)
         if wc.shape != (L.shape[1],):
             raise ValueError(f"wc: expected {L.shape[1]} column weights, got shape {wc.shape}")
@@ -1599,10 +1518,33 @@ class Context:
             raise ValueError(f"{name}: expected one id per day ({n}), got shape {ids.shape}")
         return ids
 
-    def _ca_table(self, name, a, Tq, k, dtype):
+    @staticmethod
+    def _ca_idx(idx):
+        """the analogs of ``ca_select`` as far as Tq and k can be read from them -> (Tq, k); ``_ca_table`` checks the rest"""
+        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
+            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
+        return idx.shape
+
+    @staticmethod
+    def _ca_table(name, a, Tq, k, dtype):
         if not isinstance(a, DeviceArray) or tuple(a.shape) != (Tq, k) or a.dtype != dtype or a.ld != k:
             raise ValueError(f"{name}: expected a contiguous {np.dtype(dtype).name} DeviceArray of shape ({Tq}, {k})")
         return a
+
+    @staticmethod
+    def _ca_fine(F):
+        """the fine library -> (Tl, Cf)"""
+        if not isinstance(F, DeviceArray) or len(F.shape) != 2 or F.dtype not in (np.float32, np.float64):
+            raise ValueError("F: expected a float32 or float64 [Tl, Cf] DeviceArray")
+        return F.shape
+
+    @staticmethod
+    def _ca_rows(who, q0, q1, Tq):
+        """the targets [q0, q1) of an applying call (q1 None: to the last)"""
+        q0, q1 = int(q0), Tq if q1 is None else int(q1)
+        if not 0 <= q0 < q1 <= Tq:
+            raise ValueError(f"sd_downscale: {who}: rows [{q0}, {q1}) lie outside the {Tq} targets")
+        return q0, q1
 
     def ca_select(self, L, Q, wc, k, key_l=None, key_q=None, period=1, window=-1, excl_l=None, excl_q=None):
         """L [Tl, Cc], Q [Tq, Cc]: float64 host arrays or DeviceArrays (rows ``ld`` apart); wc [Cc] host column weights; key_*, excl_*:
@@ -1617,14 +1559,9 @@ class Context:
         with self._uploads() as up:
             L, Q = up(L), up(Q)
             self._same_context("sd_ca_select", L=L, Q=Q)
-            idx, dist, status = self.empty((Tq, k), np.int32), self.empty((Tq, k)), self.empty((Tq,), np.int32)
-            try:
+            with self._fresh(((Tq, k), np.int32), ((Tq, k), np.float64), ((Tq,), np.int32)) as (idx, dist, status):
                 check(self.lib.sd_ca_select_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, L.shape[1], ptr(wc), k, ptr(key_l), ptr(key_q),
                                                 int(period), int(window), ptr(excl_l), ptr(excl_q), idx.vptr, dist.vptr, status.vptr))
-            except BaseException:
-                for a in (idx, dist, status):
-                    a.free()
-                raise
         return idx, dist, status
 
     def ca_weights(self, L, Q, wc, idx, dist, status, kind="regression", ridge=1e-6):
@@ -1633,9 +1570,7 @@ class Context:
         pattern on the k library patterns) | 'mean' (1 / k) (sd_ca_weights_dev)."""
         if kind not in _lib.CA_KINDS:
             raise ValueError(f"kind={kind!r}: expected one of {', '.join(repr(s) for s in _lib.CA_KINDS)}")
-        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
-            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
-        L, Q, wc, k = self._ca_coarse("sd_ca_weights", L, Q, wc, idx.shape[1])
+        L, Q, wc, k = self._ca_coarse("sd_ca_weights", L, Q, wc, self._ca_idx(idx)[1])
         Tl, Tq = L.shape[0], Q.shape[0]
         idx, dist = self._ca_table("idx", idx, Tq, k, np.int32), self._ca_table("dist", dist, Tq, k, np.float64)
         if not isinstance(status, DeviceArray) or tuple(status.shape) != (Tq,) or status.dtype != np.int32:
@@ -1646,33 +1581,22 @@ class Context:
         with self._uploads() as up:
             L, Q = up(L), up(Q)
             self._same_context("sd_ca_weights", L=L, Q=Q, idx=idx, dist=dist, status=status)
-            weights = self.empty((Tq, k))
-            try:
+            with self._fresh(((Tq, k), np.float64)) as (weights,):
                 check(self.lib.sd_ca_weights_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, L.shape[1], ptr(wc), k, _lib.CA_KINDS[kind], ridge,
                                                  idx.vptr, dist.vptr, weights.vptr, status.vptr))
-            except BaseException:
-                weights.free()
-                raise
         return weights
 
     def ca_apply(self, F, idx, weights, q0=0, q1=None, out=None):
         """F [Tl, Cf]: the fine library, a float32 / float64 DeviceArray (rows ``ld`` apart); idx, weights: the [Tq, k] tables ->
         float64 [q1 - q0, Cf] DeviceArray: rows [q0, q1) of ``out[q] = sum_i weights[q, i] * F[idx[q, i]]`` in analog order
         (sd_ca_apply_dev).  ``out``: that DeviceArray, possibly a view of a wider or longer one."""
-        if not isinstance(F, DeviceArray) or len(F.shape) != 2 or F.dtype not in (np.float32, np.float64):
-            raise ValueError("F: expected a float32 or float64 [Tl, Cf] DeviceArray")
-        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
-            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
-        Tq, k = idx.shape
+        Tl, Cf = self._ca_fine(F)
+        Tq, k = self._ca_idx(idx)
         idx, weights = self._ca_table("idx", idx, Tq, k, np.int32), self._ca_table("weights", weights, Tq, k, np.float64)
-        q0, q1 = int(q0), Tq if q1 is None else int(q1)
-        if not 0 <= q0 < q1 <= Tq:
-            raise ValueError(f"sd_downscale: sd_ca_apply: rows [{q0}, {q1}) lie outside the {Tq} targets")
-        Tl, Cf = F.shape
+        q0, q1 = self._ca_rows("sd_ca_apply", q0, q1, Tq)
         out = self._result_buffer(out, (q1 - q0, Cf), True)
         self._same_context("sd_ca_apply", F=F, idx=idx, weights=weights, out=out)
-        check(self.lib.sd_ca_apply_dev(self.handle, F.vptr, int(F.dtype == np.float32), F.ld, Tl, Cf, idx.vptr, weights.vptr, Tq, k, q0, q1,
-                                       out.vptr, out.ld))
+        check(self.lib.sd_ca_apply_dev(self.handle, F.vptr, _f32(F), F.ld, Tl, Cf, idx.vptr, weights.vptr, Tq, k, q0, q1, out.vptr, out.ld))
         return out
 
     # ---- localized analogs (LocalizedAnalogs) ----
@@ -1681,9 +1605,7 @@ class Context:
         cells; idx: the int32 [Tq, k] DeviceArray of ``ca_select`` -> (local_idx int32 [Tq, ny * nx], local_dist float64
         [Tq, ny * nx]) DeviceArrays: per coarse cell the analog whose distance over the cell's neighbourhood is smallest, ties to the
         lower slot (sd_ca_local_dev; the rule is in include/sd_downscale.h)."""
-        if not isinstance(idx, DeviceArray) or len(idx.shape) != 2:
-            raise ValueError("idx: expected the int32 [Tq, k] DeviceArray of ca_select")
-        L, Q, wc, k = self._ca_coarse("sd_ca_local", L, Q, wc, idx.shape[1])
+        L, Q, wc, k = self._ca_coarse("sd_ca_local", L, Q, wc, self._ca_idx(idx)[1])
         Tl, Tq, Cc = L.shape[0], Q.shape[0], L.shape[1]
         try:
             (ny, nx), (ry, rx) = (int(n) for n in grid), (int(r) for r in radius)
@@ -1697,13 +1619,9 @@ class Context:
         with self._uploads() as up:
             L, Q = up(L), up(Q)
             self._same_context("sd_ca_local", L=L, Q=Q, idx=idx)
-            local_idx, local_dist = self.empty((Tq, Cc), np.int32), self.empty((Tq, Cc))
-            try:
+            with self._fresh(((Tq, Cc), np.int32), ((Tq, Cc), np.float64)) as (local_idx, local_dist):
                 check(self.lib.sd_ca_local_dev(self.handle, L.vptr, L.ld, Tl, Q.vptr, Q.ld, Tq, ny, nx, ptr(wc), k, ry, rx, idx.vptr,
                                                local_idx.vptr, local_dist.vptr))
-            except BaseException:
-                local_idx.free(), local_dist.free()
-                raise
         return local_idx, local_dist
 
     def ca_local_apply(self, F, cell_of, local_idx, L=None, Q=None, adjust="none", max_scale=0.0, q0=0, q1=None, out=None):
@@ -1712,9 +1630,7 @@ class Context:
         DeviceArrays, needed unless adjust is 'none' -> float64 [q1 - q0, Cf] DeviceArray: rows [q0, q1) of
         ``out[q, f] = F[local_idx[q, cell_of[f]], f]``, shifted by Q - L or scaled by Q / L (at most ``max_scale``; 0: no limit) of
         that day and coarse cell (sd_ca_local_apply_dev).  ``out``: that DeviceArray, possibly a view of a wider or longer one."""
-        if not isinstance(F, DeviceArray) or len(F.shape) != 2 or F.dtype not in (np.float32, np.float64):
-            raise ValueError("F: expected a float32 or float64 [Tl, Cf] DeviceArray")
-        Tl, Cf = F.shape
+        Tl, Cf = self._ca_fine(F)
         if not isinstance(cell_of, DeviceArray) or tuple(cell_of.shape) != (Cf,) or cell_of.dtype != np.int32:
             raise ValueError(f"cell_of: expected an int32 DeviceArray of shape ({Cf},)")
         if not isinstance(local_idx, DeviceArray) or len(local_idx.shape) != 2:
@@ -1732,14 +1648,12 @@ class Context:
             for name, a, rows, what in (("L", L, Tl, "Tl"), ("Q", Q, Tq, "Tq")):
                 if not isinstance(a, DeviceArray) or tuple(a.shape) != (rows, Cc) or a.dtype != np.float64:
                     raise ValueError(f"{name}: adjust={adjust!r} needs a float64 DeviceArray of shape ({rows}, {Cc}) [{what}, Cc]")
-        q0, q1 = int(q0), Tq if q1 is None else int(q1)
-        if not 0 <= q0 < q1 <= Tq:
-            raise ValueError(f"sd_downscale: sd_ca_local_apply: rows [{q0}, {q1}) lie outside the {Tq} targets")
+        q0, q1 = self._ca_rows("sd_ca_local_apply", q0, q1, Tq)
         out = self._result_buffer(out, (q1 - q0, Cf), True)
         self._same_context("sd_ca_local_apply", F=F, cell_of=cell_of, local_idx=local_idx, L=L, Q=Q, out=out)
-        check(self.lib.sd_ca_local_apply_dev(self.handle, F.vptr, int(F.dtype == np.float32), F.ld, Tl, Cf, cell_of.vptr, local_idx.vptr, Cc,
-                                             vptr(L), 0 if L is None else L.ld, vptr(Q), 0 if Q is None else Q.ld, _lib.CA_ADJUST[adjust],
-                                             max_scale, Tq, q0, q1, out.vptr, out.ld))
+        check(self.lib.sd_ca_local_apply_dev(self.handle, F.vptr, _f32(F), F.ld, Tl, Cf, cell_of.vptr, local_idx.vptr, Cc, vptr(L),
+                                             0 if L is None else L.ld, vptr(Q), 0 if Q is None else Q.ld, _lib.CA_ADJUST[adjust], max_scale, Tq, q0,
+                                             q1, out.vptr, out.ld))
         return out
 
 
